@@ -14,7 +14,14 @@ Workloads (--workload):
   flat  FAISS Flat L2 over 10M x 768 (exact: recall 1.0), rows sharded contiguously over the ranks.
   diskann  DiskProvider batch path, 1M x 1536 SQ8, L_search=128 (C4); replicas (weak scaling).
 
-At N = 1 the default line also carries, from the same run, every other BASELINE configuration as a
+A plain run (no --full) does what the headline figure needs and nothing else: set up the index, warm up, time
+--steps searches, write the last timed step's results when --dump-outputs DIR is given (DIR/distances.npy fp32,
+DIR/labels.npy fp64: the (nq, k) arrays the caller of the timed search receives; the inputs are seeded, so two
+builds run with the same arguments can be compared array for array), print the line.  Recall against exact
+search, the kernel-timer roofline, the PCIe-inclusive rate, the other distance forms, the CPU baselines and
+parity, and the sub-configurations below all take runs of their own and sit behind --full.
+
+With --full, at N = 1 the default line also carries, from the same run, every other BASELINE configuration as a
 sub-object of ``configs`` (each with its own roofline and CPU baseline): C1 (Flat 10k x 128, the CPU
 path), C2 (Flat L2 1M x 768), Flat L2 10M x 768, C4 (DiskANN), the extension's real call shape
 (nq = 1 / 4 latency, Flat and IVF), the reference's published batch-distance microbenchmark shapes
@@ -22,7 +29,7 @@ path), C2 (Flat L2 1M x 768), Flat L2 10M x 768, C4 (DiskANN), the extension's r
 ranks 16/24/32.  --no-suite skips them.  At every N the IVF line also carries C5 (Flat IP, 12.5M rows
 per GPU, sharded: exactly C5's 100M x 768 at N = 8); --no-c5 skips it.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  N > 1 runs one process per GPU over RCCL: under
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  N > 1 runs one process per GPU over RCCL: under
 torch.distributed.run (the driver's launch) the ranks read RANK / WORLD_SIZE; started directly, bench.py
 starts the N ranks itself (a torch.distributed.run child process — the parent never touches the GPU and never
 re-execs) and exits with their status.  ``--workload selftest`` checks that launcher on the CPU (gloo): N
@@ -195,9 +202,15 @@ def compact_line(full):
     return line
 
 
-def emit(full, rank):
-    """Rank 0: the full record to DETAIL_PATH, the compact line to stdout."""
+def emit(full, rank, detail=True):
+    """Rank 0: the full record to DETAIL_PATH, the compact line to stdout.  detail=False (a plain run: the record
+    holds nothing the line does not) prints the line alone."""
     if rank != 0:
+        return
+    if not detail:
+        line = compact_line(full)
+        line.pop("detail", None)
+        print(json.dumps(line), flush=True)
         return
     try:
         DETAIL_PATH.parent.mkdir(parents=True, exist_ok=True)
@@ -264,7 +277,15 @@ def parse():
     p.add_argument("--only", default=None, help="with the suite: run only these comma-separated configurations "
                    "(profiling runs; e.g. C3_ivf_survey_mixture)")
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU sample duration (main line)")
+    p.add_argument("--full", action="store_true",
+                   help="beside the timed steps: recall, kernel-timer roofline, PCIe-inclusive rate, the other forms, "
+                        "CPU baselines + parity, the suite and C5 (the --suite / --no-* options choose among these)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed step's results to DIR/distances.npy (fp32) and "
+                        "DIR/labels.npy (fp64)")
     a = p.parse_args()
+    if not a.full:  # a plain run: set up, warm up, time the steps, print the line
+        a.suite, a.no_c5, a.no_cpu_baseline, a.no_alt_forms = False, True, True, True
     if a.n is None:
         a.n = 1_000_000 if a.workload == "diskann" else 10_000_000
     if a.d is None:
@@ -344,15 +365,16 @@ def uniform_queries(torch, nq, d, dev):
 # timing helpers
 # ------------------------------------------------------------------------------------------------
 def timed_steps(torch, dist, world, fn, steps, gpu=True):
-    """Barrier + sync, `steps` calls, sync + barrier; max over ranks.  Returns seconds.  gpu=False: the CPU
-    self-test (gloo, no device synchronisation)."""
+    """Barrier + sync, `steps` calls, sync + barrier; max over ranks.  Returns (seconds, what the last call
+    returned).  gpu=False: the CPU self-test (gloo, no device synchronisation)."""
     sync = torch.cuda.synchronize if gpu else (lambda: None)
+    last = None
     if world > 1:
         dist.barrier()
     sync()
     t0 = time.perf_counter()
     for _ in range(steps):
-        fn()
+        last = fn()
     sync()
     if world > 1:
         dist.barrier()
@@ -362,7 +384,19 @@ def timed_steps(torch, dist, world, fn, steps, gpu=True):
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
-    return el
+    return el, last
+
+
+def dump_outputs(args, rank, D, I):
+    """--dump-outputs DIR: the (nq, k) distances and labels the last timed step returned (device tensors or host
+    arrays), as DIR/distances.npy (fp32) and DIR/labels.npy (fp64: exact for every label below 2^53)."""
+    if not args.dump_outputs or rank != 0:
+        return
+    host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)  # noqa: E731
+    out = Path(args.dump_outputs)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "distances.npy", host(D).astype(np.float32))
+    np.save(out / "labels.npy", host(I).astype(np.float64))
 
 
 def host_pointer_rate(torch, search_dev, xq, nq, k, steps):
@@ -486,7 +520,10 @@ FLAT_FORMS = {5: ("flat_bf16_k64<I8>", 1, I8_MFMA_PEAK_TOPS,
 
 
 def flat_config(args, torch, dist, hipann, rank, world, dev, n, d, nq, k, metric, steps, warmup, alt_forms=True,
-                cpu_seconds=0.0, oracle_queries=0, latency=False, host_rate=True, request_k=False):
+                cpu_seconds=0.0, oracle_queries=0, latency=False, host_rate=True, request_k=False, full=True,
+                dump=False):
+    """full=False (the headline of a plain run): only the set-up, the warm-up and the timed steps.  dump: this is the
+    run's headline configuration, whose last timed step --dump-outputs writes."""
     from sharded import ShardedSearch, merge_packed_device_torch, shard_bounds
 
     lo, hi = shard_bounds(n, rank, world)
@@ -510,7 +547,14 @@ def flat_config(args, torch, dist, hipann, rank, world, dev, n, d, nq, k, metric
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
-    el = timed_steps(torch, dist, world, step, steps)
+    el, (Dl, Il) = timed_steps(torch, dist, world, step, steps)
+    if dump:
+        dump_outputs(args, rank, Dl, Il)
+    del Dl, Il
+    if not full:
+        return {"workload": f"FAISS Flat {'L2' if metric == 0 else 'IP'}, {n}x{d} fp32, batch={nq}, k={k}",
+                "value": round(nq * steps / el, 1), "unit": "queries/s", "ms_per_step": round(el * 1e3 / steps, 3),
+                "steps": steps, "setup_s": round(setup_s, 1), "form": index.last_search_path()["form"]}, index, xb
     kern_ms, merge_ms = kernel_timing_steps(torch, index, step, steps)
     Dr, Ir = step()
     torch.cuda.synchronize()
@@ -817,6 +861,13 @@ def ivf_config(args, torch, dist, hipann, rank, world, dev, steps, warmup, suite
     torch.cuda.synchronize()
     info["coarse_step"] = "partitioned over ranks + one all-gather of the probe lists" if pp is not None else \
         "replicated on every rank" if world > 1 else "single GPU"
+    if not args.full:  # a plain run: the timed steps and the line
+        el, (Dl, Il) = timed_steps(torch, dist, world, step, steps)
+        dump_outputs(args, rank, Dl, Il)
+        return {"workload": f"FAISS IVFFlat nlist={nlist} nprobe={nprobe}, {n}x{d} fp32 ({data_desc}), batch={nq}, "
+                            f"k={k}",
+                "value": round(nq * steps / el, 1), "ms_per_step": round(el * 1e3 / steps, 3),
+                "setup_s": round(setup_s, 1), "ivf": info}, index
     probes = index.last_probes(nq)
     info.update(ivf_scan_stats(index, probes, d, nlist, ivf_row_bytes(index.form, d, metric)))
     if world == 1:  # the list sizes and this batch's probe lists (tests/golden/c3_lists_*.npz: sharding balance tests)
@@ -826,7 +877,9 @@ def ivf_config(args, torch, dist, hipann, rank, world, dev, steps, warmup, suite
                                 probes=probes.astype(np.int16 if nlist < 32768 else np.int32))
         except OSError:
             pass
-    el = timed_steps(torch, dist, world, step, steps)
+    el, (Dl, Il) = timed_steps(torch, dist, world, step, steps)
+    dump_outputs(args, rank, Dl, Il)
+    del Dl, Il
     kern_ms, merge_ms = kernel_timing_steps(torch, index, step, steps)
     Dr, Ir = step()
     torch.cuda.synchronize()
@@ -1104,7 +1157,7 @@ def ivf_clustered_config(args, torch, dist, hipann, dev):
         call()
     torch.cuda.synchronize()
     f0 = index.rerank_fallbacks()
-    el = timed_steps(torch, dist, 1, call, steps)
+    el, _ = timed_steps(torch, dist, 1, call, steps)
     flagged = (index.rerank_fallbacks() - f0) / steps
     kern_ms, merge_ms = kernel_timing_steps(torch, index, call, steps)
     call()
@@ -1180,8 +1233,10 @@ def ivf_robustness(args, torch, dist, hipann, dev):
 # DiskANN (C4)
 # ------------------------------------------------------------------------------------------------
 def diskann_config(args, torch, dist, hipann, rank, world, dev, n, d, nq, k, L, R, steps, warmup, cpu=True,
-                   resident=True):
-    """C4 (SURVEY §8d): DiskProvider::search_batch over n x d SQ8, L_search, R, nq queries.
+                   resident=True, full=True, dump=False):
+    """C4 (SURVEY §8d): DiskProvider::search_batch over n x d SQ8, L_search, R, nq queries.  full=False (the
+    headline of a plain run): the set-up, the warm-up and the timed steps only; dump: the run's headline
+    configuration, whose last timed step --dump-outputs writes.
 
     Graph traversal does not shard, so N GPUs run N replicas (each holds the whole SQ8 DB and answers
     its own batch; weak scaling, no collective).  A step = one BFS batch of nq queries:
@@ -1248,6 +1303,21 @@ def diskann_config(args, torch, dist, hipann, rank, world, dev, n, d, nq, k, L, 
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    qps = world * nq * steps / elapsed
+    if dump:
+        dump_outputs(args, rank, D_dev if resident else dd, I_dev if resident else ids)
+    data_desc = (f"low-rank gaussian rows, intrinsic dim {r_dim}, noise {eta}; SQ8-encoded; graph = {R - R // 4} "
+                 f"exact cell-local nearest neighbours + {R // 4} random edges, medoid entry point")
+    workload = f"DISKANN DiskProvider batch-distance, {n}x{d} sq8, L_search={L}, R={R}, batch={nq}, k={k}"
+    if not full:
+        db.close()
+        return {"workload": workload, "value": round(qps, 1), "unit": "queries/s",
+                "ms_per_step": round(elapsed * 1e3 / steps, 3), "steps": steps, "setup_s": round(setup_s, 1),
+                "data": data_desc}
     tsteps = max(1, min(steps, 3))
     db.set_kernel_timing(True)
     evals_t = pops_t = 0
@@ -1258,11 +1328,6 @@ def diskann_config(args, torch, dist, hipann, rank, world, dev, n, d, nq, k, L, 
     torch.cuda.synchronize()
     kern_total_ms, launches = db.kernel_stats()
     db.set_kernel_timing(False)
-    if world > 1:
-        t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    qps = world * nq * steps / elapsed
     if resident:
         ids = I_dev.cpu().numpy()
     gt = DB.exact_topk(torch, xb, xq, k, metric).cpu().numpy()
@@ -1286,11 +1351,10 @@ def diskann_config(args, torch, dist, hipann, rank, world, dev, n, d, nq, k, L, 
             "algorithmic": alg}
     if world == 1:
         attach_traffic(roof, f"diskann_{n}x{d}", b_alg / max(launches, 1))
-    out = {"workload": f"DISKANN DiskProvider batch-distance, {n}x{d} sq8, L_search={L}, R={R}, batch={nq}, k={k}",
+    out = {"workload": workload,
            "value": round(qps, 1), "unit": "queries/s", "ms_per_step": round(elapsed * 1e3 / steps, 3),
            "steps": steps, "recall_at_10": recall, "roofline": roof, "setup_s": round(setup_s, 1),
-           "data": f"low-rank gaussian rows, intrinsic dim {r_dim}, noise {eta}; SQ8-encoded; graph = {R - R // 4} "
-                   f"exact cell-local nearest neighbours + {R // 4} random edges, medoid entry point",
+           "data": data_desc,
            "diskann": {"graph_build_s": round(t_graph, 1), "bfs_steps_per_batch": int(np.mean(bfs_steps)),
                        "traversal": "GPU-resident (one 2-wavefront workgroup per query)" if resident else
                                     f"host lock-step BFS ({os.environ.get('HIPANN_BFS_THREADS', '16')} threads) + "
@@ -1581,7 +1645,7 @@ def selftest(args, torch, dist, world, rank):
     step = (lambda: dist.all_gather(seen, mine)) if world > 1 else (lambda: seen[0].copy_(mine))  # noqa: E731
     for _ in range(args.warmup):
         step()
-    el = timed_steps(torch, dist, world, step, args.steps, gpu=False)
+    el, _ = timed_steps(torch, dist, world, step, args.steps, gpu=False)
     ranks_seen = sorted(int(t.item()) for t in seen)
     if ranks_seen != list(range(world)):
         raise SystemExit(f"launcher self-test: ranks seen {ranks_seen} != 0..{world - 1}")
@@ -1590,6 +1654,9 @@ def selftest(args, torch, dist, world, rank):
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
             "config": {"workload": "selftest", "parallelism": f"ranks{world}"},
             "world_check": {"backend": dist.get_backend() if world > 1 else None, "ranks_seen": ranks_seen}}
+    if rank == 0 and args.dump_outputs:  # what the last timed all-gather left: the ranks it saw
+        Path(args.dump_outputs).mkdir(parents=True, exist_ok=True)
+        np.save(Path(args.dump_outputs) / "ranks_seen.npy", np.array([int(t.item()) for t in seen], np.float64))
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -1638,7 +1705,7 @@ def main():
     if args.workload == "diskann":
         sub = diskann_config(args, torch, dist, hipann, rank, world, dev, args.n, args.d, args.nq, args.k,
                              args.l_search, args.degree, args.steps, args.warmup, cpu=not args.no_cpu_baseline,
-                             resident=not args.diskann_host_bfs)
+                             resident=not args.diskann_host_bfs, full=args.full, dump=True)
         line = {"metric": "queries/sec @ recall@10>=0.95 (DiskANN DiskProvider batch path, 1Mx1536 sq8, L_search=128)",
                 "value": sub.pop("value"), "unit": "queries/s", "n_gpus": world, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": sub.pop("ms_per_step"), "higher_is_better": True,
@@ -1651,7 +1718,8 @@ def main():
         if args.workload == "flat":
             sub, index, xb_keep = flat_config(args, torch, dist, hipann, rank, world, dev, args.n, args.d, args.nq, args.k,
                                         metric, args.steps, args.warmup, alt_forms=not args.no_alt_forms,
-                                        cpu_seconds=0.0 if args.no_cpu_baseline else args.cpu_seconds)
+                                        cpu_seconds=0.0 if args.no_cpu_baseline else args.cpu_seconds,
+                                        full=args.full, dump=True)
             dtype = ("f32 results (int8-image certified filter, int32 sums + exact fp32 rerank)" if sub.get("form") == 5
                      else "f32 results (bf16-image certified filter + exact fp32 rerank)" if sub.get("form") == 4 else "f32")
             data = "U(-1,1) rows"
@@ -1712,7 +1780,7 @@ def main():
             names = {0: "setup", 1: "loads", 5: "bound_count", 2: "select_sort", 3: "distances", 4: "order_ties", 8: "write"}
             log("rerank phase clocks per query (wave 0):", {v: round(buf[i] / buf[7]) for i, v in names.items()},
                 "compaction-path", buf[6], "list-path", buf[9], "queries", buf[7])
-    emit(line, rank)
+    emit(line, rank, detail=args.full)
     if world > 1:
         dist.destroy_process_group()
     reap_children()

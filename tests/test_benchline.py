@@ -64,3 +64,42 @@ def test_emit_writes_detail_and_prints_one_line(tmp_path, capsys, monkeypatch):
     assert json.loads((tmp_path / "detail.json").read_text())["configs"].keys() == full["configs"].keys()
     bench.emit(full, 1)  # other ranks print nothing
     assert capsys.readouterr().out == ""
+
+
+def test_plain_run_line_has_no_detail_file(tmp_path, capsys, monkeypatch):
+    """A plain run (no --full) prints the line alone: nothing is written, the line names no detail file."""
+    monkeypatch.setattr(bench, "DETAIL_PATH", tmp_path / "detail.json")
+    full = _full()
+    bench.emit(full, 0, detail=False)
+    out = capsys.readouterr().out.strip().splitlines()
+    assert len(out) == 1
+    line = json.loads(out[0])
+    assert "detail" not in line and not (tmp_path / "detail.json").exists()
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[k] == full[k], k
+
+
+def test_plain_run_measures_only_the_headline(monkeypatch):
+    """Without --full every extra measurement is off, whatever the other options say; --full keeps the defaults."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--suite"])
+    a = bench.parse()
+    assert (a.full, a.suite, a.no_c5, a.no_cpu_baseline, a.no_alt_forms) == (False, False, True, True, True)
+    assert (a.steps, a.warmup, a.dump_outputs) == (7, 2, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert (a.full, a.suite, a.no_c5, a.no_cpu_baseline, a.no_alt_forms) == (True, True, False, False, False)
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path, monkeypatch):
+    import numpy as np
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", str(tmp_path / "o")])
+    a = bench.parse()
+    D = np.arange(12, dtype=np.float32).reshape(4, 3)
+    I = np.array([[2**40 + 1, -1, 5]] * 4, np.int64)
+    bench.dump_outputs(a, 1, D, I)  # other ranks write nothing
+    assert not (tmp_path / "o").exists()
+    bench.dump_outputs(a, 0, D, I)
+    d, i = np.load(tmp_path / "o" / "distances.npy"), np.load(tmp_path / "o" / "labels.npy")
+    assert d.dtype == np.float32 and i.dtype == np.float64
+    assert np.array_equal(d, D) and np.array_equal(i.astype(np.int64), I)

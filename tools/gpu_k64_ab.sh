@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 vs="${*:-0 1 2}"
 for rep in 1 2; do
 for v in $vs; do
-  HIPANN_K64_V=$v timeout -k 10 300 python3 bench.py --workload flat --no-cpu-baseline --no-alt-forms --no-suite \
+  HIPANN_K64_V=$v timeout -k 10 300 python3 bench.py --full --workload flat --no-cpu-baseline --no-alt-forms --no-suite \
       --no-c5 --steps 10 --warmup 2 ${K64_EXTRA:-} > gpurun_out/ab.json 2> gpurun_out/ab.err \
       || { tail -20 gpurun_out/ab.err; exit 1; }
   python3 - "$v" <<'PY'

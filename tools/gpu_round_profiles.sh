@@ -15,8 +15,10 @@ if [ "${1:-}" != "--no-tests" ]; then
     tail -1 gpurun_out/pytest_gpu.log
 fi
 if [ "${1:-}" != "--no-tests" ]; then
-timeout -k 10 900 python -u bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err \
-    || { tail -20 gpurun_out/bench_default.err; exit 1; }
+# the line with every configuration (--full), next to the detail file bench.py writes
+out="$(python -c 'import bench; print(bench.DETAIL_PATH.parent)')"
+timeout -k 10 900 python -u bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err" \
+    || { tail -20 "$out/bench_default.err"; exit 1; }
 exit 0
 fi
 bash tools/gpu_profile.sh ivf ivf_scan_mfma_h ivf_10000000x768 --no-alt-forms --no-c5 --steps 10 || exit 1
