@@ -82,6 +82,18 @@ public:
         check(hipann_flat_search(handle_->h, n, x, k, distances, reinterpret_cast<int64_t *>(labels), err, sizeof err),
               err);
     }
+    // IndexFlatCodes::remove_ids with an IDSelectorBatch over `labels` on the GPU copy (hipann_flat_remove_ids): the
+    // survivors keep their order and are relabelled 0..ntotal'-1 — what FaissIndex::Vacuum rebuilds for a Flat index
+    // (faiss_index.cpp:861-892).  Returns the rows removed.  A plain member, not the remove_ids override: the selector
+    // type is not needed to pass a label list.
+    size_t remove_labels(const faiss::idx_t *labels, size_t n) {
+        char err[512] = {0};
+        const int64_t r = hipann_flat_remove_ids(handle_->h, reinterpret_cast<const int64_t *>(labels), (int64_t)n, err,
+                                                 sizeof err);
+        if (r < 0) throw std::runtime_error(std::string("hipann_flat_remove_ids: ") + err);
+        ntotal -= r;
+        return (size_t)r;
+    }
     void reset() override { throw std::runtime_error("HipIndexFlat::reset: rebuild from the CPU index"); }
     void reconstruct(faiss::idx_t key, float *recons) const override {
         char err[512] = {0};
@@ -141,6 +153,17 @@ public:
         check(hipann_ivf_search_np(handle_->h, np, n, x, k, distances, reinterpret_cast<int64_t *>(labels), err,
                                    sizeof err),
               err);
+    }
+    // IndexIVF::remove_ids with an IDSelectorBatch over `labels` on the GPU copy (hipann_ivf_remove_ids): FAISS's
+    // list order, ids and centroids unchanged, so the same call on the CPU index keeps both copies equal.  Returns the
+    // rows removed.  Adds after a removal must carry explicit ids (add_with_ids).
+    size_t remove_labels(const faiss::idx_t *labels, size_t n) {
+        char err[512] = {0};
+        const int64_t r = hipann_ivf_remove_ids(handle_->h, reinterpret_cast<const int64_t *>(labels), (int64_t)n, err,
+                                                sizeof err);
+        if (r < 0) throw std::runtime_error(std::string("hipann_ivf_remove_ids: ") + err);
+        ntotal -= r;
+        return (size_t)r;
     }
     void reset() override { throw std::runtime_error("HipIndexIVFFlat::reset: rebuild from the CPU index"); }
     void set_nprobe(size_t np) { nprobe_ = np; }

@@ -218,6 +218,113 @@ void shard_append(FlatShard &sh, int d, int metric, const float *x_host, const f
     }
 }
 
+// faiss::IndexFlatCodes::remove_ids on one shard, in two steps so that a call over several shards changes none of
+// them unless every shard's new storage exists.  flat_remove_prepare compacts the rows from the first removed one to
+// the end (remove_kernels.hip: keep mask, prefix sum, gather) into FRESH buffers — rows, ‖x‖² and, when the int8
+// image is built, its per-row scales: gathered bits equal recomputed ones — and copies the unmoved prefix beside them;
+// nothing a search reads has changed when it returns or throws.  flat_remove_commit re-tiles the int8 / bf16 images
+// in place from the first 256-row tile holding a moved row (tiles before it stay, as in shard_append) and swaps the
+// buffers in; it allocates nothing.  The bound terms (xmax2, i8_rxmax, bf16_rxmax) keep their pre-removal values:
+// maxima over a superset of the rows, still upper bounds.  A borrowed table becomes owned, as at its first add.
+struct FlatRemoval {
+    int64_t m = 0, first = 0, n_new = 0, cap = 0;
+    DevBuf xb, xn, xscale;
+};
+
+void flat_remove_prepare(FlatShard &sh, int d, int metric, const std::vector<int64_t> &rows, FlatRemoval &rm) {
+    rm.m = (int64_t)rows.size();
+    if (!rm.m) return;
+    DeviceGuard g(sh.device);
+    FenceScope fs(sh.fence, sh.stream, sh.device);  // searches still running on other streams read sh.xb
+    hipStream_t st = sh.stream;
+    const int R = flat_bf16_tile_rows();
+    const int64_t first = rows.front(), cnt = sh.n - first, kept = cnt - rm.m;
+    rm.first = first;
+    rm.n_new = sh.n - rm.m;
+    rm.cap = std::max<int64_t>(rm.n_new, 1);
+    rm.xb.ensure((size_t)rm.cap * d * sizeof(float), sh.device);
+    if (metric == kL2) rm.xn.ensure((size_t)rm.cap * sizeof(float), sh.device);
+    if (sh.xi8_ok) rm.xscale.ensure(sizeof(float) * (size_t)(ceil_div(rm.cap, (int64_t)R) * R), sh.device);
+    DevBuf d_rows, keep, sums, src;
+    d_rows.ensure(sizeof(int64_t) * (size_t)rm.m, sh.device);
+    keep.ensure((size_t)cnt, sh.device);
+    sums.ensure(sizeof(int64_t) * (size_t)flat_remove_scan_blocks(cnt), sh.device);
+    src.ensure(sizeof(int64_t) * (size_t)std::max<int64_t>(kept, 1), sh.device);
+    HIPANN_CHECK(hipMemcpyAsync(d_rows.p, rows.data(), sizeof(int64_t) * (size_t)rm.m, hipMemcpyHostToDevice, st));
+    launch_flat_remove_plan(d_rows.get<int64_t>(), rm.m, first, cnt, keep.get<unsigned char>(), sums.get<int64_t>(),
+                            src.get<int64_t>(), st);
+    if (first > 0) {
+        HIPANN_CHECK(hipMemcpyAsync(rm.xb.p, sh.xb, (size_t)first * d * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (metric == kL2)
+            HIPANN_CHECK(hipMemcpyAsync(rm.xn.p, sh.xn.p, (size_t)first * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (sh.xi8_ok)
+            HIPANN_CHECK(hipMemcpyAsync(rm.xscale.p, sh.xscale.p, (size_t)first * sizeof(float), hipMemcpyDeviceToDevice,
+                                        st));
+    }
+    launch_flat_gather_rows(sh.xb + first * (int64_t)d, src.get<int64_t>(), kept, d,
+                            rm.xb.get<float>() + first * (int64_t)d, st);
+    if (metric == kL2)
+        launch_flat_gather_f32(sh.xn.get<float>() + first, src.get<int64_t>(), kept, rm.xn.get<float>() + first, st);
+    if (sh.xi8_ok)
+        launch_flat_gather_f32(sh.xscale.get<float>() + first, src.get<int64_t>(), kept,
+                               rm.xscale.get<float>() + first, st);
+    HIPANN_CHECK(hipStreamSynchronize(st));  // the plan's scratch is freed on return
+}
+
+void flat_remove_commit(FlatShard &sh, int d, int metric, FlatRemoval &rm) {
+    if (!rm.m) return;
+    DeviceGuard g(sh.device);
+    FenceScope fs(sh.fence, sh.stream, sh.device);
+    hipStream_t st = sh.stream;
+    const int R = flat_bf16_tile_rows();
+    const int64_t t0 = rm.first / R, r0 = t0 * R;  // first tile with a moved row
+    try {
+        if (sh.xi8_ok && rm.n_new > r0)
+            launch_i8_tile_rows(rm.xb.get<float>() + r0 * (int64_t)d, rm.xscale.get<float>() + r0, rm.n_new - r0, d, R,
+                                static_cast<char *>(sh.xi8.p) + (size_t)t0 * flat_i8_img_bytes(R, d, R), st);
+        if (sh.xb16_ok && rm.n_new > r0)
+            launch_b16_tile_rows(rm.xb.get<float>() + r0 * (int64_t)d, rm.n_new - r0, d, R,
+                                 static_cast<char *>(sh.xb16.p) + (size_t)t0 * flat_bf16_img_bytes(R, d, R), st);
+        HIPANN_CHECK(hipStreamSynchronize(st));
+    } catch (...) {  // the rows are still the old ones: the images are rebuilt from them at the next search
+        sh.xi8_ok = false;
+        sh.xb16_ok = false;
+        throw;
+    }
+    auto take = [](DevBuf &dst, DevBuf &src) {
+        std::swap(dst.p, src.p);
+        std::swap(dst.bytes, src.bytes);
+        std::swap(dst.device, src.device);
+    };
+    take(sh.xb_buf, rm.xb);  // rm now holds the old storage (nothing, when the table was borrowed): freed with it
+    sh.xb = sh.xb_buf.get<float>();
+    sh.owns = true;
+    sh.cap = rm.cap;
+    sh.n = rm.n_new;
+    if (metric == kL2) take(sh.xn, rm.xn);
+    if (sh.xi8_ok) take(sh.xscale, rm.xscale);
+}
+
+// The labels of a removal call as FAISS's IDSelectorBatch sees them: a set (sorted here, duplicates dropped).
+std::vector<int64_t> sorted_unique_labels(const int64_t *labels, int64_t n) {
+    std::vector<int64_t> v(labels, labels + n);
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    return v;
+}
+
+template <typename F>
+int64_t guard_i64(char *eb, int el, F &&f) {
+    try {
+        return f();
+    } catch (const std::exception &e) {
+        set_err(eb, el, e.what());
+    } catch (...) {
+        set_err(eb, el, "hipann: unknown error");
+    }
+    return -1;
+}
+
 }  // namespace
 
 namespace hipann {
@@ -1017,6 +1124,50 @@ int hipann_flat_add(void *h, const float *xb, int64_t n, char *eb, int el) {
         auto &sh = *fx->shards.back();
         shard_append(sh, fx->d, fx->metric, xb, nullptr, n);
         return 0;
+    });
+}
+
+int64_t hipann_flat_remove_ids(void *h, const int64_t *labels, int64_t n, char *eb, int el) {
+    return guard_i64(eb, el, [&]() -> int64_t {
+        HIPANN_REQUIRE(h, "null index");
+        auto *ix = static_cast<IndexBase *>(h);
+        HIPANN_REQUIRE(ix->kind == Kind::Flat, "not a Flat index");
+        HIPANN_REQUIRE(n >= 0 && (n == 0 || labels), "invalid labels");
+        if (n == 0) return 0;
+        auto *fx = static_cast<FlatIndex *>(ix);
+        std::lock_guard<std::mutex> lk(fx->mu);
+        const std::vector<int64_t> lab = sorted_unique_labels(labels, n);
+        // per shard, the local rows that leave (label − label_offset; labels outside every shard are ignored)
+        const size_t ns = fx->shards.size();
+        std::vector<std::vector<int64_t>> rows(ns);
+        int64_t removed = 0;
+        for (size_t s = 0; s < ns; ++s) {
+            const FlatShard &sh = *fx->shards[s];
+            auto lo = std::lower_bound(lab.begin(), lab.end(), sh.label_offset);
+            auto hi = std::lower_bound(lo, lab.end(), sh.label_offset + sh.n);
+            rows[s].reserve((size_t)(hi - lo));
+            for (auto it = lo; it != hi; ++it) rows[s].push_back(*it - sh.label_offset);
+            removed += (int64_t)rows[s].size();
+        }
+        if (!removed) return 0;
+        // every shard's new storage first (nothing a search reads changes), then the swaps
+        std::vector<FlatRemoval> rm(ns);
+        for (size_t s = 0; s < ns; ++s) flat_remove_prepare(*fx->shards[s], fx->d, fx->metric, rows[s], rm[s]);
+        auto relabel = [&]() {  // the later shards' labels shift down
+            int64_t off = fx->shards[0]->label_offset;
+            for (auto &shp : fx->shards) {
+                shp->label_offset = off;
+                off += shp->n;
+            }
+        };
+        try {
+            for (size_t s = 0; s < ns; ++s) flat_remove_commit(*fx->shards[s], fx->d, fx->metric, rm[s]);
+        } catch (...) {  // (a failed launch with every buffer in hand: the shards already swapped keep contiguous labels)
+            relabel();
+            throw;
+        }
+        relabel();
+        return removed;
     });
 }
 

@@ -858,6 +858,99 @@ static void ivf_add_block(IvfIndex &ix, int64_t n, const float *xb, const int64_
     }
 }
 
+// What one shard's removal needs on the device, allocated for every shard before any shard's rows move.
+struct IvfRemoval {
+    DevBuf labels, mark, plan, pass_ids, out;  // out: [npass u64 | newlen int × nlist]
+    bool img_h = false, img_t = false;
+};
+
+// faiss::IndexIVF::remove_ids (FAISS 1.13.2, DirectMap NoMap: per list j = 0, l = len; while (j < l) { if
+// member(id[j]) { --l; entry[j] = entry[l]; } else ++j; }) on the GPU copy.  Each shard works on the lists it owns,
+// on the device (ivf_remove_rows: one block per list marks, plans the moves in closed form, moves code row, id and
+// norm, zeroes the vacated rows — the slack stays zero for the whole-table maxima — and writes the new length); the
+// host reads back only the new lengths and the count of tiled passes to re-tile.  List starts do not change: the
+// freed rows are append slack a later add reuses.  The fp16 / fp32 tiled images are re-tiled at the passes holding a
+// destination or a vacated row; the int8 image is released, as an add releases it.  xmax2, half_rxmax and the fp16
+// scale stay: maxima over a superset of the rows, still upper bounds.  A borrowed handle moves into owned storage
+// first (ivf_relayout, as at its first add).  Every buffer of every shard is allocated before the first kernel that
+// moves a row; the cost is the label lookup (8 B per live row) plus the rows moved.
+static int64_t ivf_remove_rows(IvfIndex &ix, const std::vector<int64_t> &lab) {
+    const int nlist = ix.nlist, d = ix.d;
+    const int64_t m = (int64_t)lab.size();
+    const int64_t before = ix.ntotal();
+    // every shard's pending searches (possibly on other streams) finish before its rows move
+    std::vector<std::unique_ptr<FenceScope>> fences;
+    for (auto &shp : ix.shards) fences.push_back(std::make_unique<FenceScope>(shp->fence, shp->stream, shp->device));
+    const size_t ns = ix.shards.size();
+    std::vector<IvfRemoval> rm(ns);
+    for (size_t s = 0; s < ns; ++s) {
+        IvfShard &sh = *ix.shards[s];
+        if (!sh.live) continue;
+        DeviceGuard g(sh.device);
+        if (!sh.owns_codes) ivf_relayout(ix, sh, std::vector<int64_t>(nlist, 0));  // same rows, owned storage
+        IvfRemoval &r = rm[s];
+        r.img_h = sh.half_state > 0 && sh.codes_h.p;
+        r.img_t = sh.codes_t.p != nullptr;
+        r.labels.ensure(sizeof(int64_t) * (size_t)m, sh.device);
+        r.mark.ensure((size_t)sh.n, sh.device);
+        r.plan.ensure(sizeof(int) * (size_t)sh.n, sh.device);
+        r.out.ensure(sizeof(unsigned long long) + sizeof(int) * (size_t)nlist, sh.device);
+        if (r.img_h || r.img_t) {
+            HIPANN_REQUIRE(sh.tpass_off.p, "tiled image without pass offsets");
+            int64_t tp = 0;
+            for (int l = 0; l < nlist; ++l) tp += ceil_div(sh.h_off[l + 1] - sh.h_off[l], 32);
+            r.pass_ids.ensure(sizeof(int64_t) * (size_t)std::max<int64_t>(tp, 1), sh.device);  // each pass at most once
+        }
+    }
+    for (size_t s = 0; s < ns; ++s) {
+        IvfShard &sh = *ix.shards[s];
+        if (!sh.live) continue;
+        IvfRemoval &r = rm[s];
+        DeviceGuard g(sh.device);
+        hipStream_t st = sh.stream;
+        unsigned long long *npass = r.out.get<unsigned long long>();
+        int *newlen = reinterpret_cast<int *>(npass + 1);
+        HIPANN_CHECK(hipMemcpyAsync(r.labels.p, lab.data(), sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, st));
+        HIPANN_CHECK(hipMemsetAsync(npass, 0, sizeof(unsigned long long), st));
+        launch_ivf_remove_rows(r.labels.get<int64_t>(), m, sh.list_off.get<int64_t>(), sh.list_len.get<int>(), nlist, d,
+                               sh.codes_buf.get<float>(), sh.ids_buf.get<int64_t>(),
+                               ix.metric == kL2 ? sh.xnorm.get<float>() : nullptr, r.mark.get<unsigned char>(),
+                               r.plan.get<int>(), r.pass_ids.p ? sh.tpass_off.get<int64_t>() : nullptr,
+                               r.pass_ids.get<int64_t>(), npass, newlen, st);
+        std::vector<char> host(sizeof(unsigned long long) + sizeof(int) * (size_t)nlist);
+        HIPANN_CHECK(hipMemcpyAsync(host.data(), r.out.p, host.size(), hipMemcpyDeviceToHost, st));
+        HIPANN_CHECK(hipStreamSynchronize(st));
+        unsigned long long np = 0;
+        std::memcpy(&np, host.data(), sizeof(np));
+        const int *hl = reinterpret_cast<const int *>(host.data() + sizeof(unsigned long long));
+        int64_t live = 0, maxlen = 0;
+        for (int l = 0; l < nlist; ++l) {
+            sh.h_len[l] = hl[l];
+            live += hl[l];
+            maxlen = std::max<int64_t>(maxlen, hl[l]);
+        }
+        const bool changed = live != sh.live;
+        sh.live = live;
+        sh.max_nch = (int)std::max<int64_t>(1, ceil_div(maxlen, ivf_chunk_rows()));
+        if (!changed) continue;
+        // the touched passes of the tiled images, re-tiled from the shortened lists
+        if (np > 0 && r.img_h)
+            launch_ivf_tile_half(sh.codes, sh.list_off.get<int64_t>(), sh.list_len.get<int>(), sh.tpass_off.get<int64_t>(),
+                                 nlist, (int64_t)np, d, std::ldexp(1.f, sh.half_es), sh.codes_h.p, st,
+                                 r.pass_ids.get<int64_t>());
+        if (np > 0 && r.img_t)
+            launch_ivf_tile_codes(sh.codes, sh.list_off.get<int64_t>(), sh.list_len.get<int>(),
+                                  sh.tpass_off.get<int64_t>(), nlist, (int64_t)np, d, sh.codes_t.get<float>(), st,
+                                  r.pass_ids.get<int64_t>());
+        HIPANN_CHECK(hipStreamSynchronize(st));  // synchronous: the staging buffers are freed on return
+        // the int8 image (kFormI8Exact, opt-in) is not maintained in place: released, rebuilt at its next search
+        sh.i8_state = 0;
+        sh.codes_i8.release();
+        sh.xs8.release();
+    }
+    return before - ix.ntotal();
+}
+
 }  // namespace hipann
 
 extern "C" {
@@ -1183,6 +1276,27 @@ int hipann_ivf_add(void *h, int64_t n, const float *xb, const int64_t *ids, char
         if (n > 0) ivf_add_rows(*vx, n, xb, ids);
         return 0;
     });
+}
+
+int64_t hipann_ivf_remove_ids(void *h, const int64_t *labels, int64_t n, char *eb, int el) {
+    try {
+        HIPANN_REQUIRE(h, "null index");
+        auto *ix = static_cast<IndexBase *>(h);
+        HIPANN_REQUIRE(ix->kind == Kind::IVF, "not an IVFFlat index");
+        HIPANN_REQUIRE(n >= 0 && (n == 0 || labels), "invalid labels");
+        if (n == 0) return 0;
+        auto *vx = static_cast<IvfIndex *>(ix);
+        std::lock_guard<std::mutex> lk(vx->mu);
+        std::vector<int64_t> lab(labels, labels + n);  // FAISS's IDSelectorBatch: a set
+        std::sort(lab.begin(), lab.end());
+        lab.erase(std::unique(lab.begin(), lab.end()), lab.end());
+        return ivf_remove_rows(*vx, lab);
+    } catch (const std::exception &e) {
+        set_err(eb, el, e.what());
+    } catch (...) {
+        set_err(eb, el, "hipann: unknown error");
+    }
+    return -1;
 }
 
 int hipann_ivf_nlist(void *h) {

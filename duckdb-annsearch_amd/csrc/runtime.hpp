@@ -622,6 +622,21 @@ void launch_ivf_gather_queries(const float *Q, const int *idx, int nf, int d, fl
 void launch_ivf_append_rows(const float *rows, const float *norms, const int64_t *dst, const int64_t *ids_in, int64_t n,
                             int d, float *codes, int64_t *ids, float *xnorm, const int *newlen, int *list_len, int nlist,
                             float hscale, unsigned *stat, hipStream_t st);
+// remove_kernels.hip — hipann_flat_remove_ids: the plan over rows [first, first + cnt) of a shard (keep mask from the
+// sorted unique removed rows, exclusive prefix sum, src[j] = range-relative source of the j-th survivor; keep: cnt
+// bytes, sums: flat_remove_scan_blocks(cnt) int64, src: cnt − m int64) and the gathers into fresh buffers
+int64_t flat_remove_scan_blocks(int64_t cnt);
+void launch_flat_remove_plan(const int64_t *rows, int64_t m, int64_t first, int64_t cnt, unsigned char *keep,
+                             int64_t *sums, int64_t *src, hipStream_t st);
+void launch_flat_gather_rows(const float *X, const int64_t *idx, int64_t cnt, int d, float *out, hipStream_t st);
+void launch_flat_gather_f32(const float *v, const int64_t *idx, int64_t cnt, float *out, hipStream_t st);
+// hipann_ivf_remove_ids: every live row whose id is in labels (device, sorted unique) leaves its list in FAISS's
+// order (one block per list: mark, closed-form plan, move, zero the vacated rows, new length); mark: one byte, plan:
+// one int per physical row; pass_ids / npass (optional, npass zeroed by the caller): the tiled passes to re-tile
+void launch_ivf_remove_rows(const int64_t *labels, int64_t m, const int64_t *list_off, int *list_len, int nlist, int d,
+                            float *codes, int64_t *ids, float *xnorm, unsigned char *mark, int *plan,
+                            const int64_t *tpass_off, int64_t *pass_ids, unsigned long long *npass, int *newlen,
+                            hipStream_t st);
 void launch_ivf_scatter_results(const float *Df, const int64_t *If, const int *idx, int nf, int kout, float *D,
                                 int64_t *I, hipStream_t st);
 void launch_ivf_scan_mfma_bf(int np, const float *Q, int64_t nq, void *qsplit, const float *qn, int d, int metric,

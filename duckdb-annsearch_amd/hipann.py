@@ -89,6 +89,7 @@ def lib() -> C.CDLL:
             "hipann_peer_access": ([vp, C.POINTER(C.c_int), i32, cp, i32], i32),
             "hipann_flat_create": ([i32, i32, f, i64, C.POINTER(C.c_int), i32, cp, i32], vp),
             "hipann_flat_add": ([vp, f, i64, cp, i32], i32),
+            "hipann_flat_remove_ids": ([vp, i64p, i64, cp, i32], i64),
             "hipann_flat_search": ([vp, i64, f, i64, f, i64p, cp, i32], i32),
             "hipann_flat_reconstruct": ([vp, i64, f, cp, i32], i32),
             "hipann_flat_create_device": ([i32, i32, vp, i64, i32, i32, i64, cp, i32], vp),
@@ -112,6 +113,7 @@ def lib() -> C.CDLL:
             "hipann_ivf_nlist": ([vp], i32),
             "hipann_ivf_search_np": ([vp, i32, i64, f, i64, f, i64p, cp, i32], i32),
             "hipann_ivf_add": ([vp, i64, f, i64p, cp, i32], i32),
+            "hipann_ivf_remove_ids": ([vp, i64p, i64, cp, i32], i64),
             "hipann_ivf_export": ([vp, f, i64p, i64p, f, cp, i32], i32),
             "hipann_ivf_train": ([i32, i32, i32, i64, f, i64, i32, C.c_uint64, i32, i32, f, i64p, cp, i32], i32),
             "hipann_ivf_train_device": ([i32, i32, i32, i64, vp, i64, i32, C.c_uint64, i32, i32, vp, vp, cp, i32],
@@ -305,6 +307,15 @@ class HipIndexFlat(_FlatForm, _Handle):
         eb = _err()
         _check(lib().hipann_flat_add(self._h, _ptr(x, C.c_float), x.shape[0], eb, 1024), eb)
 
+    def remove_ids(self, labels) -> int:
+        """faiss::IndexFlatCodes::remove_ids on the resident copy (hipann_flat_remove_ids): the rows whose label is in
+        ``labels`` leave, the survivors keep their order and are relabelled 0..ntotal'-1.  Returns the rows removed."""
+        lab = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
+        eb = _err()
+        rc = int(lib().hipann_flat_remove_ids(self._h, _ptr(lab, C.c_int64), lab.size, eb, 1024))
+        _check(min(rc, 0), eb)
+        return rc
+
     def search(self, x, k: int) -> Tuple[np.ndarray, np.ndarray]:
         x = _f32_2d(x, self.d)
         n = x.shape[0]
@@ -465,6 +476,16 @@ class HipIndexIVFFlat(_Handle):
             raise ValueError("ids must hold one label per row")
         eb = _err()
         _check(lib().hipann_ivf_add(self._h, x.shape[0], _ptr(x, C.c_float), _ptr(idv, C.c_int64), eb, 1024), eb)
+
+    def remove_ids(self, labels) -> int:
+        """faiss::IndexIVF::remove_ids on the resident copy (hipann_ivf_remove_ids): rows whose id is in ``labels``
+        leave their lists in FAISS's order (each hole filled by the list's last entry); surviving ids and the centroids
+        are unchanged.  Returns the rows removed.  Pass explicit ids to every ``add`` after a removal."""
+        lab = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
+        eb = _err()
+        rc = int(lib().hipann_ivf_remove_ids(self._h, _ptr(lab, C.c_int64), lab.size, eb, 1024))
+        _check(min(rc, 0), eb)
+        return rc
 
     def export(self) -> dict:
         """The index in FAISS ArrayInvertedLists CSR form (hipann_ivf_export): centroids, list_offsets,

@@ -78,6 +78,19 @@ void *hipann_flat_create(int d, int metric, const float *xb, int64_t n, const in
 /* Append n more vectors (labels continue from ntotal) — MetalIndexFlat::add (MetalIndexFlat.mm:173-292). */
 int hipann_flat_add(void *index, const float *xb, int64_t n, char *err_buf, int err_len);
 
+/* faiss::IndexFlatCodes::remove_ids with an IDSelectorBatch: remove the rows whose label is in labels[0..n)
+ * (host, any order, duplicates and labels outside [0, ntotal) ignored); surviving rows keep their order and
+ * are relabelled 0..ntotal'-1 (new label = old label − number of removed labels below it) — row for row what the
+ * extension's VACUUM of a Flat index rebuilds (faiss_index.cpp:861-892), so VACUUM can keep the GPU copy.  Returns the
+ * number of rows removed, or -1.  Synchronous; n == 0 returns 0.  Per shard with a removed row the rows from the first
+ * removed one on are compacted on the device into fresh buffers that are then swapped in (a borrowed table,
+ * hipann_flat_create_device with copy = 0, becomes owned, as at its first add; the new capacity is the new size),
+ * and the int8 / bf16 search images, when built, are re-tiled from the first 256-row tile holding a moved row.
+ * Peak extra HBM during the call: one copy of the shard's surviving rows (ntotal'·d·4 bytes, + 4 bytes per row of
+ * norms and of int8 scales) plus 9 bytes per row from the first removed one on.  All-or-nothing: every shard's new
+ * buffers are allocated and filled before any shard changes; on failure (-1) the handle answers as before the call. */
+int64_t hipann_flat_remove_ids(void *index, const int64_t *labels, int64_t n, char *err_buf, int err_len);
+
 /* Search nq queries `xq` (nq*d floats, host).  D: nq*k floats, I: nq*k int64 (host). */
 int hipann_flat_search(void *index, int64_t nq, const float *xq, int64_t k, float *D, int64_t *I,
                        char *err_buf, int err_len);
@@ -232,6 +245,20 @@ int hipann_ivf_nlist(void *index);
  * of 65536 rows as FAISS assigns them) and appended to their lists in insertion order, labels `ids`
  * (NULL: ntotal + i).  Replaces the reference's invalidate-on-append (faiss_index.cpp:469). */
 int hipann_ivf_add(void *index, int64_t n, const float *xb, const int64_t *ids, char *err_buf, int err_len);
+
+/* faiss::IndexIVF::remove_ids (DirectMap NoMap branch): every row whose id is in labels[] (host, any order,
+ * duplicates and absent ids ignored) leaves its list; per list, FAISS's order: j = 0, l = len; while (j < l) {
+ * if member(id[j]) { --l; entry[j] = entry[l]; } else ++j; }.  Ids of surviving rows and the centroids are unchanged,
+ * so the call can be made on the CPU index and the GPU copy alike (at DELETE or VACUUM time) and hipann_ivf_export
+ * stays equal to the CPU index's lists.  Returns rows removed, or -1.  Synchronous; n == 0 returns 0.  The work runs
+ * on the device, on the lists each shard owns: the cost is the id lookup (8 bytes per live row) plus the rows moved,
+ * not the table; the freed rows become append slack that a later hipann_ivf_add reuses.  The fp16 / fp32 tiled images
+ * are re-tiled only where rows moved; the int8 image (form 7) is rebuilt at its next search.  A borrowed handle
+ * (hipann_ivf_create_device with copy = 0) moves into owned storage first, as at its first add.  Extra HBM during the
+ * call: 5 bytes per physical row, 8 per label and 8 per 32-row pass of a built image, all allocated before a row moves.
+ * NOTE: hipann_ivf_add with ids == NULL still labels its rows ntotal + i, as FAISS does; after a removal that can
+ * repeat a surviving id — pass explicit ids to every add that follows a remove. */
+int64_t hipann_ivf_remove_ids(void *index, const int64_t *labels, int64_t n, char *err_buf, int err_len);
 
 /* IVF training on the GPU — the k-means behind IndexIVFFlat::train (FAISS 1.13.2 IndexIVF::train_q1 →
  * Clustering::train), which the extension runs on the CPU at CREATE INDEX on a stride sample
