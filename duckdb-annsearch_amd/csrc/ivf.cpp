@@ -183,32 +183,54 @@ bool ensure_half_codes(IvfShard &sh, int d, int nlist, hipStream_t st) {
     return true;
 }
 
-// kFormI8Exact: the tiled int8 image (one scale per row, ivf_mfma.hip) and its largest row residual, built at the
-// first search that needs them (and again after an append: appends release it)
+void release_i8_codes(IvfShard &sh, int state) {
+    sh.i8_state = state;
+    sh.i8_rxmax = -1.f;
+    sh.codes_i8.release();
+    sh.xs8.release();
+    sh.xr8.release();
+}
+
+// kFormI8Exact: the tiled int8 image with one scale and one residual per row (ivf_mfma.hip), built at the first search
+// that needs it and kept across adds and removes (they re-tile the passes they touch: no whole-table statistic
+// belongs to the L2 certificate).  A non-finite row: the form does not apply (kFormSplit2Exact runs), as the fp16 image.
 bool ensure_i8_codes(IvfShard &sh, int d, int nlist, hipStream_t st) {
     if (sh.i8_state != 0) return sh.i8_state > 0;
     if (sh.n == 0) return false;
     const int64_t np = ensure_tpass(sh, nlist, st);
     sh.codes_i8.ensure((size_t)std::max<int64_t>(np, 1) * (size_t)ivf_i8_pass_bytes(d), sh.device);
     sh.xs8.ensure(sizeof(float) * (size_t)sh.n, sh.device);
-    launch_ivf_tile_i8(sh.codes, sh.list_off.get<int64_t>(), sh.list_len.get<int>(), sh.tpass_off.get<int64_t>(), nlist, np,
-                       d, sh.codes_i8.p, sh.xs8.get<float>(), st);
+    sh.xr8.ensure(sizeof(float) * (size_t)sh.n, sh.device);
+    // rows no pass covers (none today: a list's passes span its capacity) read as scale 0, residual 0
+    HIPANN_CHECK(hipMemsetAsync(sh.xs8.p, 0, sh.xs8.bytes, st));
+    HIPANN_CHECK(hipMemsetAsync(sh.xr8.p, 0, sh.xr8.bytes, st));
     sh.nflag.ensure(sizeof(int), sh.device);
-    launch_ivf_i8_residual(sh.codes, sh.n, d, sh.nflag.get<unsigned>(), st);
+    launch_ivf_tile_i8(sh.codes, sh.list_off.get<int64_t>(), sh.list_len.get<int>(), sh.tpass_off.get<int64_t>(), nlist, np,
+                       d, sh.codes_i8.p, sh.xs8.get<float>(), sh.xr8.get<float>(), sh.nflag.get<unsigned>(), st);
+    sh.i8_tiled += np;
+    unsigned nonfin = 0;
+    HIPANN_CHECK(hipMemcpyAsync(&nonfin, sh.nflag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPANN_CHECK(hipStreamSynchronize(st));
+    if (nonfin) {
+        release_i8_codes(sh, -1);
+        return false;
+    }
+    sh.i8_rxmax = -1.f;
+    sh.i8_state = 1;
+    return true;
+}
+
+// the IP bound's largest row residual of the int8 image: the maximum of the residual plane (its slack rows are 0),
+// taken again after an add (removes leave it: a maximum over a superset of the rows is still an upper bound)
+float shard_i8_rxmax(IvfShard &sh, hipStream_t st) {
+    if (sh.i8_rxmax >= 0.f) return sh.i8_rxmax;
+    sh.nflag.ensure(sizeof(int), sh.device);
+    launch_ivf_max_abs(sh.xr8.get<float>(), sh.n, sh.nflag.get<unsigned>(), st);
     unsigned bits = 0;
     HIPANN_CHECK(hipMemcpyAsync(&bits, sh.nflag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIPANN_CHECK(hipStreamSynchronize(st));
-    float r2;
-    std::memcpy(&r2, &bits, sizeof(r2));
-    if (bits >= 0x7f800000u) {  // a non-finite row: the form does not apply (kFormSplit2Exact runs), as the fp16 image
-        sh.i8_state = -1;
-        sh.codes_i8.release();
-        sh.xs8.release();
-        return false;
-    }
-    sh.i8_rxmax = std::sqrt(r2) * 1.0001f;
-    sh.i8_state = 1;
-    return true;
+    std::memcpy(&sh.i8_rxmax, &bits, sizeof(float));  // (the plane's entries already carry the ×1.0001 of their fp32 sums)
+    return sh.i8_rxmax;
 }
 
 // ‖x‖² of every stored row (L2 only): the decomposed scan form reads it with the codes
@@ -266,6 +288,65 @@ float shard_xmax2(IvfShard &sh, int d, hipStream_t st) {
     return v;
 }
 
+// ---- the exact fp16 form's filter image (hipann_ivf_set_filter_image) ----
+// Batches below this many queries keep the fp16 image under auto.  Measured on the 10M x 768 index (nlist 1024,
+// nprobe 32, profiles/ivf_i8_auto/): nq 64 / 128 / 256 / 1024 run 2.11 / 2.41 / 2.46 / 2.55 ms on the fp16 image and
+// 1.24 / 1.40 / 1.45 / 2.11 ms on the int8 image, run-to-run spread below 0.04 ms — the int8 image wins at every
+// measured size; smaller batches (the extension's nq = 1 call is latency-bound, not byte-bound) are left as they were.
+constexpr int64_t kAutoI8MinBatch = 64;
+
+// the setting, or the one environment override HIPANN_IVF_FILTER_IMAGE = 0 / 1 / 2 (A/B)
+static int filter_image_mode(const IvfIndex &ix) {
+    static const int env = [] { const char *e = std::getenv("HIPANN_IVF_FILTER_IMAGE"); return e && *e ? std::atoi(e) : -1; }();
+    return env >= 0 && env <= 2 ? env : ix.filter_image;
+}
+
+// The byte rule of the auto choice.  A flagged query is re-run in the direct form over its nprobe lists of fp32 rows:
+// flagged · nprobe · mean_list_rows · 4d bytes, mean_list_rows = live / nlist.  Against the fp16 image (2d + 4 B per
+// row) the int8 image (d + 8 B) saves about d bytes per row, n · d over the table a large batch streams once.  The
+// int8 image stays only while the re-runs cost less than a quarter of that saving:
+//     flagged · nprobe · mean_list_rows · 4d < 0.25 · n · d   ⇔   flagged < nlist / (16 · nprobe)
+// — fewer than 2 of 1024 queries at nlist 1024, nprobe 32.
+static bool auto8_over_rule(int64_t flagged, int nprobe, int nlist, int64_t live, int d) {
+    const double mean_list_rows = (double)live / (double)nlist;
+    return (double)flagged * nprobe * mean_list_rows * 4.0 * d >= 0.25 * (double)live * d;
+}
+
+static unsigned long long *auto8_host_word(IvfShard &sh) {
+    if (sh.fb_host.ensure(sizeof(uint64_t))) {
+        *sh.fb_host.get<uint64_t>() = 0;
+        sh.fb_seen = 0;
+    }
+    return static_cast<unsigned long long *>(host_device_ptr(sh.fb_host.p));
+}
+
+// Probation: the batch has been answered through the fp16 image; the same batch runs once more on the same stream
+// through the int8 image into scratch outputs, counting only (no flagged query is re-run, nothing the caller sees is
+// written).  The flag count is read back — probation's one host synchronisation — and decides by the byte rule.
+static void auto8_probation(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, int k, int kout, hipStream_t st,
+                            const int64_t *probes_in) {
+    sh.auto8_live = sh.live;
+    sh.auto8_over = 0;
+    sh.auto8 = -1;
+    if (!ensure_i8_codes(sh, ix.d, ix.nlist, st)) return;
+    sh.probe_D.ensure(sizeof(float) * (size_t)nq * kout, sh.device);
+    sh.probe_I.ensure(sizeof(int64_t) * (size_t)nq * kout, sh.device);
+    sh.count_only = true;
+    try {
+        TimerPause p0(ix.timer_main), p1(ix.timer_merge);
+        ivf_shard_search(ix, sh, nq, xq, k, kout, sh.probe_D.get<float>(), sh.probe_I.get<int64_t>(), st, kFormI8Exact,
+                         probes_in);
+    } catch (...) {
+        sh.count_only = false;
+        throw;
+    }
+    sh.count_only = false;
+    int nf = 0;
+    HIPANN_CHECK(hipMemcpyAsync(&nf, sh.nflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPANN_CHECK(hipStreamSynchronize(st));
+    if (!auto8_over_rule(nf, std::min(ix.nprobe, ix.nlist), ix.nlist, sh.live, ix.d)) sh.auto8 = 1;
+}
+
 void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, int k, int kout, float *D, int64_t *I,
                       hipStream_t st, int form_override, const int64_t *probes_in) {
     RoctxRange r_all("hipann.ivf.search_shard");
@@ -312,6 +393,36 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
     // the decomposed forms need float4 rows (else the direct kernel, also on the GPU); the MFMA kernel
     // keeps 16-lane lists (k <= 16) and the item's queries in LDS (else the VALU decomposed kernel)
     int req = form_override >= 0 ? form_override : ix.form;
+    // The exact fp16 form may filter through the int8 image instead (hipann_ivf_set_filter_image): the same exact
+    // rerank certifies either filter, so the results are the same rows and the same direct-form distances, and the int8
+    // image is half the bytes.  Eligible: L2 (the per-row certificate), kout <= kRerankMaxK without a sub-list
+    // request, a shape the int8 scan holds, the device fallback.  Mode 1 always takes it; auto (2) from kAutoI8MinBatch
+    // queries on, per shard: untested -> on / off by probation (below, after this batch's answer), on -> off after two
+    // consecutive batches over the byte rule, read from fb_host (the previous int8 batch's flag count: no host
+    // synchronisation), and probation again once the shard has grown by a quarter.
+    bool as_half = false, probation = false;
+    if (form_override < 0 && req == kFormHalfExact && metric == kL2 && kout <= kRerankMaxK && !bigk && !host_fallback() &&
+        ivf_mfma_i8_supported(d, kRerankK) && sh.n > 0 && sh.i8_state >= 0) {
+        const int mode = filter_image_mode(ix);
+        if (mode == 1) {
+            as_half = true;
+        } else if (mode == 2 && nq >= kAutoI8MinBatch) {
+            if (sh.auto8 == 1 && sh.fb_host.p) {
+                const uint64_t w = __atomic_load_n(sh.fb_host.get<uint64_t>(), __ATOMIC_RELAXED);
+                if (w != sh.fb_seen) {  // a batch not yet judged
+                    sh.fb_seen = w;
+                    sh.auto8_over = auto8_over_rule((int64_t)(w & 0xffffffffu), np, nlist, sh.live, d) ? sh.auto8_over + 1 : 0;
+                    if (sh.auto8_over >= 2) sh.auto8 = -1;
+                }
+            }
+            if (sh.auto8 != 0 && sh.live >= sh.auto8_live + sh.auto8_live / 4 + 1) sh.auto8 = 0;
+            as_half = sh.auto8 == 1;
+            probation = sh.auto8 == 0;
+        }
+        if (as_half && !ensure_i8_codes(sh, d, nlist, st)) as_half = false;  // a non-finite row: the fp16 path's rules
+        if (as_half) req = kFormI8Exact;
+    }
+    if (form_override < 0) ix.last_filter_image = 0;
     // request_k above kRerankMaxK on the exact forms (k + |tombstones|, faiss_index.cpp:713-715): the scans keep
     // their 16-lane lists but write every wave's list as a sub-list of the slot (mf_finish_item), and the rerank
     // takes the kf best candidates, certified against its kf-th merged key AND the smallest full sub-list's
@@ -349,15 +460,21 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
     const int kslot = sub ? ivf_scan_sublists() * k : k;
     const int kfilt = sub ? (i8 ? 64 : std::min(64, std::max(kout + 4, 2 * kout))) : k;
     if (form_override < 0) {
-        ix.last_form = exact ? (i8 ? kFormI8Exact : half ? kFormHalfExact : kFormSplit2Exact) : form;
+        ix.last_form = exact ? (i8 ? (as_half ? kFormHalfExact : kFormI8Exact) : half ? kFormHalfExact : kFormSplit2Exact) : form;
+        ix.last_filter_image = exact && i8 ? 1 : 0;
         ix.last_kfilt = exact ? kfilt : 0;
         ix.last_sublists = sub ? ivf_scan_sublists() : 0;
     }
     const bool tiled = form == kFormDecomposed || ivf_form_split(form);  // the matrix-core scans
     const int group = i8 ? ivf_mfma_i8_group(d) : half ? ivf_mfma_h_group(d) : ivf_group_size(form, d);
     float xmax2 = 0.f;
+    // the int8 image's L2 certificate: lower-bound scan keys from every row's own residual (ivf_rerank_topk); IP
+    // keeps the Cauchy-Schwarz bound with the largest row residual
+    const bool cert8 = i8 && metric == kL2;
+    float rxmax8 = -1.f;
     if (exact) {  // max‖x‖² (once per row set; nflag is its scratch, so before the plan resets the flag count)
         xmax2 = shard_xmax2(sh, d, st);
+        if (i8 && !cert8) rxmax8 = shard_i8_rxmax(sh, st);
         sh.nflag.ensure(sizeof(int), sh.device);
         sh.flagged.ensure(sizeof(int) * (size_t)nq, sh.device);
     }
@@ -388,6 +505,8 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
         sh.qi8.ensure((size_t)ivf_i8_qimg_bytes(nq, d), sh.device);
         sh.qs8.ensure(sizeof(float) * (size_t)nq, sh.device);
         sh.qres8.ensure(sizeof(float) * (size_t)nq, sh.device);
+        sh.qhn2.ensure(sizeof(float) * (size_t)nq, sh.device);
+        sh.qhn.ensure(sizeof(float) * (size_t)nq, sh.device);
         float *qn_out = nullptr;
         if (metric == kL2) {
             qsh0.qn.ensure(sizeof(float) * (size_t)nq, sh.device);
@@ -395,7 +514,8 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
             launch_row_norms(xq, nq, d, qn_out, st);
         }
         RoctxRange rr("hipann.ivf.prepare");
-        launch_ivf_split_queries_i8(xq, nq, d, sh.qi8.p, sh.qs8.get<float>(), sh.qres8.get<float>(), st);
+        launch_ivf_split_queries_i8(xq, nq, d, sh.qi8.p, sh.qs8.get<float>(), sh.qres8.get<float>(),
+                                    sh.qhn2.get<float>(), sh.qhn.get<float>(), st);
         qsh0.qn_given = qn_out ? xq : nullptr;
         qsh0.qn_given_nq = nq;
     }
@@ -483,15 +603,18 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
                     HIPANN_CHECK(hipMemsetAsync(sh.prog.p, 0, sh.prog.bytes, st));
                 }
             }
-            // (int8: its query units, scales and residuals in the fp16 form's slots)
+            // (int8: its query units, scales and residuals in the fp16 form's slots; L2: ‖q̂‖² of the dequantised
+            // queries as the key's query term)
             launch_ivf_scan_mfma_h(xq, nq, i8 ? sh.qi8.p : sh.hsplit.p, i8 ? sh.qs8.get<float>() : sh.hits.get<float>(),
-                                   i8 ? sh.qres8.get<float>() : sh.hres.get<float>(), sh.half_es, qn, d,
+                                   i8 ? sh.qres8.get<float>() : sh.hres.get<float>(), sh.half_es,
+                                   cert8 ? sh.qhn2.get<float>() : qn, d,
                                    metric, i8 ? sh.codes_i8.p : sh.codes_h.p, sh.tpass_off.get<int64_t>(), sh.xnorm.get<float>(),
                                    sh.list_off.get<int64_t>(), sh.list_len.get<int>(), sh.cnt.get<int>(), sh.bucket_off.get<int>(),
                                    sh.item_off.get<int>(), sh.bucket.get<int>(), sh.slot_off.get<int>(), nlist, np, k,
                                    max_items, qbound, sh.part_d.get<float>(), sh.part_i.get<int>(), st, true,
                                    sub ? 1 : 0, follow ? sh.prog.get<unsigned>() : nullptr, nprog,
-                                   (unsigned)(sh.plan_batch + 1), i8 ? 1 : 0, i8 ? sh.xs8.get<float>() : nullptr);
+                                   (unsigned)(sh.plan_batch + 1), i8 ? 1 : 0, i8 ? sh.xs8.get<float>() : nullptr,
+                                   cert8 ? sh.xr8.get<float>() : nullptr, cert8 ? sh.qhn.get<float>() : nullptr);
         }
         else if (bigk)
             launch_ivf_scan_bigk(xq, d, metric, sh.codes, sh.list_off.get<int64_t>(), sh.list_len.get<int>(),
@@ -527,7 +650,7 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
     // flagged queries re-run on the device in the direct form, each by the rerank wave that flagged it
     // (ivf_block_fallback inline: no host readback and no launch of its own); HIPANN_IVF_HOST_FALLBACK=1: from the
     // host on the 3-term path (A/B)
-    const bool inline_fb = !host_fallback();
+    const bool inline_fb = !host_fallback() && !sh.count_only;
     int fb_cap = 0, fb_maxch = 1;
     if (inline_fb) {
         if (!sh.fb_total.p) {
@@ -555,19 +678,22 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
         ScopedTiming t(ix.timer_merge, st);
         launch_ivf_rerank(sh.part_d.get<float>(), sh.part_i.get<int>(), sh.slot_off.get<int>(), np, nq, kfilt, kout,
                           metric, xq, sh.codes, d, sh.ids, sh.n, 0, xmax2, D, I, sh.nflag.get<int>(),
-                          sh.flagged.get<int>(), st, kSplit2Eps, i8 ? sh.i8_rxmax : half ? sh.half_rxmax : -1.f,
+                          sh.flagged.get<int>(), st, kSplit2Eps, i8 ? rxmax8 : half ? sh.half_rxmax : -1.f,
                           i8 ? sh.qres8.get<float>() : half ? sh.hres.get<float>() : nullptr, sh.coarse_i.get<int64_t>(),
                           sh.list_off.get<int64_t>(), nlist, qbound, img && metric == kL2 ? qn : nullptr, kslot,
                           sub ? 1 : 0, inline_fb ? sh.list_len.get<int>() : nullptr,
                           inline_fb ? sh.fpd.get<float>() : nullptr, inline_fb ? sh.fpi.get<long long>() : nullptr,
-                          inline_fb ? sh.fb_total.get<unsigned long long>() : nullptr, fb_cap);
+                          inline_fb ? sh.fb_total.get<unsigned long long>() : nullptr, fb_cap, cert8 ? 1 : 0);
         if (fb_cap > 0)
             launch_ivf_fallback_chunks(sh.nflag.get<int>(), sh.flagged.get<int>(), fb_cap, np, fb_maxch, ivf_chunk_rows(),
                                        kout, metric, xq, sh.codes, d, sh.ids, 0, sh.coarse_i.get<int64_t>(),
                                        sh.list_off.get<int64_t>(), sh.list_len.get<int>(), nlist, sh.fbc_d.get<float>(),
                                        sh.fbc_i.get<long long>(), sh.fbc_done.get<unsigned>(), D, I,
-                                       sh.fb_total.get<unsigned long long>(), st);
+                                       sh.fb_total.get<unsigned long long>(), st,
+                                       as_half && !probation ? auto8_host_word(sh) : nullptr, (unsigned)++sh.fb_seq);
     }
+    if (sh.count_only) return;  // probation's pass: the flag count stays in nflag, nothing is re-run
+    if (probation) auto8_probation(ix, sh, nq, xq, k_user, kout, st, probes_in);
     if (inline_fb) return;
     int nf = 0;
     HIPANN_CHECK(hipMemcpyAsync(&nf, sh.nflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -654,10 +780,16 @@ static void ivf_relayout(IvfIndex &ix, IvfShard &sh, const std::vector<int64_t> 
         }
     }
     const bool img_h = sh.half_state > 0 && sh.codes_h.p, img_t = sh.codes_t.p != nullptr;
+    const bool img_8 = sh.i8_state > 0 && sh.codes_i8.p;
     if (img_h) move_array(sh.codes_h, sh.codes_h.p, (size_t)ivf_half_pass_bytes(d), true, (size_t)tp[nlist]);
     if (img_t)
         move_array(sh.codes_t, sh.codes_t.p, sizeof(float) * (size_t)ivf_mfma_pass_floats(d), true, (size_t)tp[nlist]);
-    if (img_h || img_t) {
+    if (img_8) {  // the int8 image's passes and its per-row scales and residuals
+        move_array(sh.codes_i8, sh.codes_i8.p, (size_t)ivf_i8_pass_bytes(d), true, (size_t)tp[nlist]);
+        move_array(sh.xs8, sh.xs8.p, sizeof(float), false, (size_t)N);
+        move_array(sh.xr8, sh.xr8.p, sizeof(float), false, (size_t)N);
+    }
+    if (img_h || img_t || img_8) {
         sh.tpass_off.ensure(sizeof(int64_t) * (nlist + 1), sh.device);
         HIPANN_CHECK(hipMemcpyAsync(sh.tpass_off.p, tp.data(), sizeof(int64_t) * (nlist + 1), hipMemcpyHostToDevice, st));
         HIPANN_CHECK(hipStreamSynchronize(st));  // tp (host) is released on return
@@ -679,12 +811,6 @@ static void ivf_add_rows(IvfIndex &ix, int64_t n, const float *xb, const int64_t
     // every shard's pending searches (possibly on other streams) finish before its buffers change
     std::vector<std::unique_ptr<FenceScope>> fences;
     for (auto &shp : ix.shards) fences.push_back(std::make_unique<FenceScope>(shp->fence, shp->stream, shp->device));
-    // the int8 image (kFormI8Exact, opt-in) is not maintained in place: released, rebuilt at its next search
-    for (auto &shp : ix.shards) {
-        shp->i8_state = 0;
-        shp->codes_i8.release();
-        shp->xs8.release();
-    }
     // FAISS assigns in blocks of 65536 rows (so the Flat nq < 20 direct-form rule applies per block); each block's
     // rows follow the previous block's in their lists (insertion order)
     const int64_t bs = 65536;
@@ -787,6 +913,8 @@ static void ivf_add_block(IvfIndex &ix, int64_t n, const float *xb, const int64_
                 sh.half_rxmax = std::max(sh.half_rxmax, std::sqrt(r2) * 1.0001f);
             }
         }
+        // the int8 image keeps no whole-table statistic for L2 (per-row residuals): only a non-finite new entry ends it
+        if (sh.i8_state > 0 && hs[1] >= 0x7f800000u) release_i8_codes(sh, -1);
         DeviceGuard g(sh.device);
         hipStream_t ss = sh.stream;
         if (&sh != &s0) {  // the block's rows (and their norms) on this shard's device too
@@ -834,6 +962,7 @@ static void ivf_add_block(IvfIndex &ix, int64_t n, const float *xb, const int64_
         const int64_t *ddst = sh.app_up.get<int64_t>(), *dlab = ddst + n, *dpass = dlab + n;
         const int *dlen = reinterpret_cast<const int *>(dpass + np);
         const bool img_h = sh.half_state > 0 && sh.codes_h.p, img_t = sh.codes_t.p != nullptr;
+        const bool img_8 = sh.i8_state > 0 && sh.codes_i8.p;
         const float hscale = std::ldexp(1.f, sh.half_es);
         // one kernel: rows, labels and norms into their CSR rows, the new lengths
         launch_ivf_append_rows(sh.app_rows.get<float>(), sh.app_norm.get<float>(), ddst, dlab, n, d,
@@ -850,6 +979,12 @@ static void ivf_add_block(IvfIndex &ix, int64_t n, const float *xb, const int64_
         if (np > 0 && img_t)
             launch_ivf_tile_codes(sh.codes, sh.list_off.get<int64_t>(), sh.list_len.get<int>(),
                                   sh.tpass_off.get<int64_t>(), nlist, np, d, sh.codes_t.get<float>(), ss, dpass);
+        if (np > 0 && img_8) {  // (scales and residuals of the passes' rows with them; the IP bound's maximum is retaken)
+            launch_ivf_tile_i8(sh.codes, sh.list_off.get<int64_t>(), sh.list_len.get<int>(), sh.tpass_off.get<int64_t>(),
+                               nlist, np, d, sh.codes_i8.p, sh.xs8.get<float>(), sh.xr8.get<float>(), nullptr, ss, dpass);
+            sh.i8_tiled += np;
+            sh.i8_rxmax = -1.f;
+        }
         if (prof) {
             HIPANN_CHECK(hipStreamSynchronize(ss));
             std::fprintf(stderr, "hipann append: n %lld h2d %.0f us, assign %.0f us, shard %d done %.0f us (grow %d, %lld passes)\n",
@@ -861,7 +996,7 @@ static void ivf_add_block(IvfIndex &ix, int64_t n, const float *xb, const int64_
 // What one shard's removal needs on the device, allocated for every shard before any shard's rows move.
 struct IvfRemoval {
     DevBuf labels, mark, plan, pass_ids, out;  // out: [npass u64 | newlen int × nlist]
-    bool img_h = false, img_t = false;
+    bool img_h = false, img_t = false, img_8 = false;
 };
 
 // faiss::IndexIVF::remove_ids (FAISS 1.13.2, DirectMap NoMap: per list j = 0, l = len; while (j < l) { if
@@ -870,7 +1005,7 @@ struct IvfRemoval {
 // norm, zeroes the vacated rows — the slack stays zero for the whole-table maxima — and writes the new length); the
 // host reads back only the new lengths and the count of tiled passes to re-tile.  List starts do not change: the
 // freed rows are append slack a later add reuses.  The fp16 / fp32 tiled images are re-tiled at the passes holding a
-// destination or a vacated row; the int8 image is released, as an add releases it.  xmax2, half_rxmax and the fp16
+// destination or a vacated row; the int8 image's likewise, with its rows' scales and residuals.  xmax2, half_rxmax and the fp16
 // scale stay: maxima over a superset of the rows, still upper bounds.  A borrowed handle moves into owned storage
 // first (ivf_relayout, as at its first add).  Every buffer of every shard is allocated before the first kernel that
 // moves a row; the cost is the label lookup (8 B per live row) plus the rows moved.
@@ -891,11 +1026,12 @@ static int64_t ivf_remove_rows(IvfIndex &ix, const std::vector<int64_t> &lab) {
         IvfRemoval &r = rm[s];
         r.img_h = sh.half_state > 0 && sh.codes_h.p;
         r.img_t = sh.codes_t.p != nullptr;
+        r.img_8 = sh.i8_state > 0 && sh.codes_i8.p;
         r.labels.ensure(sizeof(int64_t) * (size_t)m, sh.device);
         r.mark.ensure((size_t)sh.n, sh.device);
         r.plan.ensure(sizeof(int) * (size_t)sh.n, sh.device);
         r.out.ensure(sizeof(unsigned long long) + sizeof(int) * (size_t)nlist, sh.device);
-        if (r.img_h || r.img_t) {
+        if (r.img_h || r.img_t || r.img_8) {
             HIPANN_REQUIRE(sh.tpass_off.p, "tiled image without pass offsets");
             int64_t tp = 0;
             for (int l = 0; l < nlist; ++l) tp += ceil_div(sh.h_off[l + 1] - sh.h_off[l], 32);
@@ -942,11 +1078,14 @@ static int64_t ivf_remove_rows(IvfIndex &ix, const std::vector<int64_t> &lab) {
             launch_ivf_tile_codes(sh.codes, sh.list_off.get<int64_t>(), sh.list_len.get<int>(),
                                   sh.tpass_off.get<int64_t>(), nlist, (int64_t)np, d, sh.codes_t.get<float>(), st,
                                   r.pass_ids.get<int64_t>());
+        if (np > 0 && r.img_8) {
+            launch_ivf_tile_i8(sh.codes, sh.list_off.get<int64_t>(), sh.list_len.get<int>(), sh.tpass_off.get<int64_t>(),
+                               nlist, (int64_t)np, d, sh.codes_i8.p, sh.xs8.get<float>(), sh.xr8.get<float>(), nullptr, st,
+                               r.pass_ids.get<int64_t>());
+            sh.i8_tiled += (int64_t)np;
+        }
         HIPANN_CHECK(hipStreamSynchronize(st));  // synchronous: the staging buffers are freed on return
-        // the int8 image (kFormI8Exact, opt-in) is not maintained in place: released, rebuilt at its next search
-        sh.i8_state = 0;
-        sh.codes_i8.release();
-        sh.xs8.release();
+        if (sh.i8_state < 0) sh.i8_state = 0;  // the non-finite row may be gone: tried again at the next int8 search
     }
     return before - ix.ntotal();
 }
@@ -1406,6 +1545,41 @@ int64_t hipann_ivf_rerank_fallbacks(void *h) {
         if (hipMemcpy(&v, sh->fb_total.p, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
         t += (int64_t)v;
     }
+    return t;
+}
+
+int hipann_ivf_set_filter_image(void *h, int mode) {
+    if (!h || mode < 0 || mode > 2) return -1;
+    auto *ix = static_cast<IndexBase *>(h);
+    if (ix->kind != Kind::IVF) return -1;
+    auto *vx = static_cast<IvfIndex *>(ix);
+    std::lock_guard<std::mutex> lk(vx->mu);
+    vx->filter_image = mode;
+    return 0;
+}
+
+int hipann_ivf_get_filter_image(void *h) {
+    if (!h) return -1;
+    auto *ix = static_cast<IndexBase *>(h);
+    if (ix->kind != Kind::IVF) return -1;
+    return static_cast<IvfIndex *>(ix)->filter_image;
+}
+
+int hipann_ivf_last_filter_image(void *h) {
+    if (!h) return -1;
+    auto *ix = static_cast<IndexBase *>(h);
+    if (ix->kind != Kind::IVF) return -1;
+    return static_cast<IvfIndex *>(ix)->last_filter_image;
+}
+
+int64_t hipann_ivf_i8_passes_tiled(void *h) {
+    if (!h) return -1;
+    auto *ix = static_cast<IndexBase *>(h);
+    if (ix->kind != Kind::IVF) return -1;
+    auto *vx = static_cast<IvfIndex *>(ix);
+    std::lock_guard<std::mutex> lk(vx->mu);
+    int64_t t = 0;
+    for (auto &sh : vx->shards) t += sh->i8_tiled;
     return t;
 }
 

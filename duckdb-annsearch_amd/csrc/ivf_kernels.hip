@@ -1865,8 +1865,13 @@ ivf_fallback_chunks(const int *__restrict__ nflag, const int *__restrict__ flagg
                     const int64_t *__restrict__ ids, int64_t label_offset, const int64_t *__restrict__ probes,
                     const int64_t *__restrict__ list_off, const int *__restrict__ list_len, int nlist,
                     float *__restrict__ cpd, long long *__restrict__ cpi, unsigned *__restrict__ done,
-                    float *__restrict__ D, int64_t *__restrict__ I, unsigned long long *__restrict__ total) {
+                    float *__restrict__ D, int64_t *__restrict__ I, unsigned long long *__restrict__ total,
+                    unsigned long long *host_word, unsigned host_seq) {
     const int nf0 = *nflag;
+    // the batch's flag count for the host (pinned, host-mapped memory; the next call reads it: ivf.cpp, auto image)
+    if (host_word && blockIdx.x == 0 && threadIdx.x == 0)
+        __hip_atomic_store(host_word, ((unsigned long long)host_seq << 32) | (unsigned)nf0, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
     const int nf = nf0 < fb_cap ? nf0 : fb_cap;
     if (nf <= 0) return;
     const int lane = threadIdx.x & 63;
@@ -1974,18 +1979,19 @@ void launch_ivf_fallback_chunks(const int *nflag, const int *flagged, int fb_cap
                                 int kout, int metric, const float *Q, const float *codes, int d, const int64_t *ids,
                                 int64_t label_offset, const int64_t *probes, const int64_t *list_off,
                                 const int *list_len, int nlist, float *cpd, long long *cpi, unsigned *done, float *D,
-                                int64_t *I, unsigned long long *total, hipStream_t st) {
+                                int64_t *I, unsigned long long *total, hipStream_t st, unsigned long long *host_word,
+                                unsigned host_seq) {
     if (fb_cap <= 0) return;
     HIPANN_REQUIRE(kout >= 1 && kout <= 64 && maxch >= 1 && chunk_rows >= 64, "ivf fallback: arguments out of range");
     dim3 grid(256), block(256);  // 1024 waves: a grid-stride loop over the items; an empty batch returns at once
     if (metric == kIP)
         hipLaunchKernelGGL(ivf_fallback_chunks<true>, grid, block, 0, st, nflag, flagged, fb_cap, nprobe, maxch,
                            chunk_rows, kout, Q, codes, d, ids, label_offset, probes, list_off, list_len, nlist, cpd, cpi,
-                           done, D, I, total);
+                           done, D, I, total, host_word, host_seq);
     else
         hipLaunchKernelGGL(ivf_fallback_chunks<false>, grid, block, 0, st, nflag, flagged, fb_cap, nprobe, maxch,
                            chunk_rows, kout, Q, codes, d, ids, label_offset, probes, list_off, list_len, nlist, cpd, cpi,
-                           done, D, I, total);
+                           done, D, I, total, host_word, host_seq);
     HIPANN_CHECK(hipGetLastError());
 }
 
@@ -2011,6 +2017,12 @@ void launch_ivf_fallback_chunks(const int *nflag, const int *flagged, int fb_cap
 // largest row residual: |q̂·x̂ − q·x| ≤ ‖q‖·‖x̂−x‖ + ‖q̂−q‖·‖x̂‖ ≤ ‖q‖·rxmax + ‖q̂−q‖·(max‖x‖ + rxmax),
 // plus the fp32 accumulation of d exact products (≤ d·2⁻²⁴·‖q̂‖‖x̂‖), doubled for L2, plus the fp32
 // rounding of the key and of the reranked direct distance (≤ (d + 8)·2⁻²⁴·2(‖q‖² + max‖x‖²)), all ×1.01.
+// i8_l2 (the IVF int8 image, L2): the scan key is itself a lower bound of ‖q̂ − x‖², q̂ the dequantised query (each
+// row's own residual is subtracted in the scan, ivf_mfma.hip), so every pruned row has ‖q̂ − x‖² ≥ B − E with B the
+// smaller of the k-th merged key and the smallest full sub-list's key and E only the fp32 rounding term above (the
+// int32 sums are exact).  By the triangle inequality ‖q − x‖ ≥ ‖q̂ − x‖ − ‖q − q̂‖: the query is certified when
+// sqrt(d_kout) + ‖q − q̂‖ < sqrt((B − E)·(1 − 2⁻²⁰)) — the query's residual (qres) enters once, in distance units, and
+// no whole-table residual maximum is involved.
 // ---------------------------------------------------------------------------------------------
 // WV = 1: one wave per query, four queries per block (large batches).  WV > 1 (small batches, the
 // extension's nq = 1 call): one block of WV waves per query — the waves merge disjoint parts of the
@@ -2026,7 +2038,7 @@ ivf_rerank_topk(const float *__restrict__ pd, const int *__restrict__ pi, const 
                 const int64_t *__restrict__ list_off, int nlist, const unsigned *__restrict__ qbound,
                 const float *__restrict__ qnorm, int kslot, int sub, const int *__restrict__ list_len,
                 float *__restrict__ fpd, long long *__restrict__ fpi, unsigned long long *__restrict__ fb_total,
-                int fb_cap) {
+                int fb_cap, int i8_l2) {
     const int64_t q = WV == 1 ? (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6) : (int64_t)blockIdx.x;
     if (q >= nq) return;
     const int lane = threadIdx.x & 63;
@@ -2239,7 +2251,10 @@ ivf_rerank_topk(const float *__restrict__ pd, const int *__restrict__ pi, const 
     // 4. exactness check
     const float dk = readlane_f(R.d[0], kout - 1);
     float E;
-    if (rxmax >= 0.f) {
+    const bool cert8 = !IP && i8_l2 != 0;
+    if (cert8) {
+        E = 1.01f * (float)(d + 8) * 0x1p-24f * 2.f * (qq + xmax2);
+    } else if (rxmax >= 0.f) {
         // qres (IVF fp16 form): the query's own split residual, and 2d products per accumulator chain
         const float qn = sqrtf(qq), rq = qres ? qres_pre : sqrtf(rq2), xh = sqrtf(xmax2) + rxmax;
         const float g = (float)(qres ? 2 * d : d) * 0x1p-24f;
@@ -2252,8 +2267,13 @@ ivf_rerank_topk(const float *__restrict__ pd, const int *__restrict__ pi, const 
     // has no candidate at all: empty probe lists, or the Flat bounded passes' overflowed query, which
     // flat_cand_select already flagged (flagged holds nq entries: no query may be appended twice); sub-lists: the
     // kout-th distance must also clear the smallest full sub-list's k-th key
-    const bool flag = sel_bad || (ncand > 0 && !(E <= 3.4e38f)) || (ncand == k && !(dk < k16 - E)) ||
-                      (sub && tsub < __builtin_inff() && !(dk < tsub - E));
+    // clear(B): the kout-th exact distance lies below every row the scan pruned under the bound B
+    const float lhs8 = cert8 ? (sqrtf(fmaxf(dk, 0.f)) + qres_pre) * (1.f + 0x1p-20f) : 0.f;
+    auto clear = [&](float B) {
+        return cert8 ? lhs8 < sqrtf(fmaxf((B - E) * (1.f - 0x1p-20f), 0.f)) : dk < B - E;
+    };
+    const bool flag = sel_bad || (ncand > 0 && !(E <= 3.4e38f && (!cert8 || qres_pre <= 3.4e38f))) ||
+                      (ncand == k && !clear(k16)) || (sub && tsub < __builtin_inff() && !clear(tsub));
     int fslot = 0;
     if (flag && lane == 0) {
         fslot = atomicAdd(nflag, 1);
@@ -2478,9 +2498,10 @@ void launch_ivf_rerank(const float *pd, const int *pi, const int *slot_off, int 
                        hipStream_t st, float eps, float rxmax, const float *qres, const int64_t *probes,
                        const int64_t *list_off, int nlist, const unsigned *qbound, const float *qnorm, int kslot,
                        int sub, const int *list_len, float *fpd, long long *fpi, unsigned long long *fb_total,
-                       int fb_cap) {
+                       int fb_cap, int i8_l2) {
     if (nq <= 0) return;
     if (kslot <= 0) kslot = k;
+    HIPANN_REQUIRE(!i8_l2 || (metric == kL2 && qres && qnorm), "ivf rerank: the int8 L2 certificate needs ‖q − q̂‖ and ‖q‖²");
     // the filter depth k bounds kout (kout = k leaves no margin: those queries are flagged and re-run exactly)
     HIPANN_REQUIRE(k >= kRerankK && k <= 64 && kout >= 1 && kout <= k && kslot >= 1 && (!sub || qbound),
                    "ivf rerank: k / kout out of range");
@@ -2490,7 +2511,7 @@ void launch_ivf_rerank(const float *pd, const int *pi, const int *slot_off, int 
     dim3 grid((unsigned)(wide ? nq : ceil_div(nq, 4))), block(256);
 #define RR_ARGS pd, pi, slot_off, nprobe, nq, k, kout, Q, codes, d, ids, nrows, label_offset, xmax2, D, I, nflag, flagged, \
                 eps, rxmax, qres, probes, list_off, nlist, qbound, qnorm, kslot, sub, list_len, fpd, fpi, fb_total, \
-                fpd ? fb_cap : 0
+                fpd ? fb_cap : 0, i8_l2
     if (metric == kIP) {
         if (wide) hipLaunchKernelGGL((ivf_rerank_topk<true, 4>), grid, block, 0, st, RR_ARGS);
         else hipLaunchKernelGGL((ivf_rerank_topk<true, 1>), grid, block, 0, st, RR_ARGS);

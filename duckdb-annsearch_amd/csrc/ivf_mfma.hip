@@ -1012,7 +1012,12 @@ __device__ __forceinline__ mf_f32x4 mh_mfma(const uint4 &a, const uint4 &b, cons
 // Same geometry as the fp16 image with 64-dim super-steps: [pass][S][row tile r][lane (g, m)][16 B] = row 16r + m,
 // dims 64S + 16g .. +15 (the queries' units use the same lane order, so the MFMA pairs equal k-slots whatever its
 // internal k mapping).  The filter is coarser (≈ 2⁻⁸ relative): the scan always keeps per-wave sub-lists and the
-// rerank takes 64 candidates, certified with the int8 residuals (max row ‖x − s·x̂‖, the query's own).
+// rerank takes 64 candidates, certified with the int8 residuals.  IP: the largest row residual and the query's own
+// (the Cauchy-Schwarz bound of ivf_rerank_topk).  L2: every row's own residual r_x = ‖x − s_x·x̂‖ (xr8, written with
+// the scales) makes the scan key a lower bound of ‖q̂ − x‖², q̂ = s_q·q̂₈ the dequantised query:
+//   ‖q̂ − x‖² = ‖q̂‖² + ‖x‖² − 2 q̂·x̂ − 2 q̂·(x − x̂) ≥ ‖q̂‖² + ‖x‖² − 2·s_q·s_x·Σq̂₈x̂₈ − 2‖q̂‖·r_x =: key (clamped at 0),
+// and the query's residual enters once, in distance units: ‖q − x‖ ≥ ‖q̂ − x‖ − ‖q − q̂‖ (the rerank's certificate).
+// No whole-table maximum is involved, so an add or a remove re-tiles the touched passes only.
 typedef int mf_i32x4 __attribute__((ext_vector_type(4)));
 __host__ __device__ inline int mi_nsup(int d) { return (int)ceil_div(ceil_div(d, 64), MH_P) * MH_P; }
 __device__ __forceinline__ int mi_quant(float x, float s) {
@@ -1036,12 +1041,15 @@ __device__ __forceinline__ float mi_row_scale(const float *x, int d, int lane) {
     return mx > 0.f && mx < 3.0e38f ? mx / 127.f : (mx == 0.f ? 0.f : -1.f);
 }
 
-// one block per 32-row pass (list by binary search over the pass offsets, as ivf_tile_half): the rows' scales (into
-// xs8 at their CSR rows) and the pass's units; rows past the list's live length: zero units, scale 0
+// one block per 32-row pass (list by binary search over the pass offsets, as ivf_tile_half): the rows' scales and
+// residuals ‖x − s·x̂‖ (×1.0001 for the fp32 sum; into xs8 / xr8 at their CSR rows) and the pass's units; rows past the
+// list's live length: zero units, scale 0, residual 0.  A non-finite row: zero units, residual +inf, and nonfin (when
+// given) is set — the host drops the image
 __global__ void __launch_bounds__(256)
 ivf_tile_i8(const float *__restrict__ codes, const int64_t *__restrict__ list_off, const int *__restrict__ list_len,
             const int64_t *__restrict__ tpass_off, int nlist, int d, int nsup, uint4 *__restrict__ dst,
-            float *__restrict__ xs8, const int64_t *__restrict__ pass_ids) {
+            float *__restrict__ xs8, float *__restrict__ xr8, unsigned *__restrict__ nonfin,
+            const int64_t *__restrict__ pass_ids) {
     const int64_t pass = pass_ids ? pass_ids[blockIdx.x] : (int64_t)blockIdx.x;
     int lo = 0, hi = nlist - 1;
     while (lo < hi) {
@@ -1054,14 +1062,31 @@ ivf_tile_i8(const float *__restrict__ codes, const int64_t *__restrict__ list_of
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int rr = wave; rr < 32; rr += 4) {
         const int64_t row = r0 + rr;
-        float s = 0.f;
+        float s = 0.f, res = 0.f;
         if (row < rend) {
-            s = mi_row_scale(codes + row * (int64_t)d, d, lane);
-            if (s < 0.f) s = 0.f;  // non-finite row: zero units (its residual is +inf: the rerank re-runs every query)
+            const float *x = codes + row * (int64_t)d;
+            s = mi_row_scale(x, d, lane);
+            if (s < 0.f) {  // non-finite row: zero units, residual +inf
+                s = 0.f;
+                res = __builtin_inff();
+            } else {
+                float r2 = 0.f;
+                for (int e = lane; e < d; e += 64) {
+                    const float t = x[e] - s * (float)mi_quant(x[e], s);
+                    r2 = fmaf(t, t, r2);
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) r2 += __shfl_xor(r2, o);
+                res = sqrtf(r2) * 1.0001f;
+            }
         }
         if (lane == 0) {
             sc[rr] = s;
-            if (row < list_off[l + 1]) xs8[row] = s;
+            if (row < list_off[l + 1]) {
+                xs8[row] = s;
+                xr8[row] = res;
+            }
+            if (nonfin && res == __builtin_inff()) atomicOr(nonfin, 1u);
         }
     }
     __syncthreads();
@@ -1074,33 +1099,14 @@ ivf_tile_i8(const float *__restrict__ codes, const int64_t *__restrict__ list_of
     }
 }
 
-// max over rows of ‖x − s·x̂‖² (one wave per row; +inf for a non-finite row) as float bits
-__global__ void __launch_bounds__(256) ivf_i8_residual(const float *__restrict__ codes, int64_t n, int d,
-                                                       unsigned *__restrict__ out) {
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;
-    const int lane = threadIdx.x & 63;
-    const float *x = codes + row * (int64_t)d;
-    const float s = mi_row_scale(x, d, lane);
-    float r2 = 0.f;
-    if (s >= 0.f) {
-        for (int e = lane; e < d; e += 64) {
-            const float rr = x[e] - s * (float)mi_quant(x[e], s);
-            r2 = fmaf(rr, rr, r2);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) r2 += __shfl_xor(r2, o);
-    } else {
-        r2 = __builtin_inff();
-    }
-    if (lane == 0) atomicMax(out, __float_as_uint(r2));
-}
-
 // The batch's int8 queries, one wave per query: scale qs8 = max|q| / 127, residual qres8 = ‖q − qs8·q̂‖ (×1.0001; +inf
-// for a non-finite query: the rerank re-runs it) and the units [q][S][g] (zero past d)
+// for a non-finite query: the rerank re-runs it), the dequantised query's qhn2 = ‖q̂‖² (the L2 scan key's query term)
+// and qhn = ‖q̂‖ (×1.0001: an upper bound, the factor of the rows' residuals in the key), and the units [q][S][g]
+// (zero past d)
 __global__ void __launch_bounds__(256) ivf_split_queries_i8(const float *__restrict__ Q, int64_t nq, int d, int nsup,
                                                             uint4 *__restrict__ out, float *__restrict__ qs8,
-                                                            float *__restrict__ qres8) {
+                                                            float *__restrict__ qres8, float *__restrict__ qhn2,
+                                                            float *__restrict__ qhn) {
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= nq) return;
     const int lane = threadIdx.x & 63;
@@ -1108,16 +1114,22 @@ __global__ void __launch_bounds__(256) ivf_split_queries_i8(const float *__restr
     float s = mi_row_scale(x, d, lane);
     const bool fin = s >= 0.f;
     if (!fin) s = 0.f;
-    float r2 = 0.f;
+    float r2 = 0.f, h2 = 0.f;
     for (int e = lane; e < d; e += 64) {
-        const float rr = x[e] - s * (float)mi_quant(x[e], s);
+        const float qh = s * (float)mi_quant(x[e], s), rr = x[e] - qh;
         r2 = fmaf(rr, rr, r2);
+        h2 = fmaf(qh, qh, h2);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) r2 += __shfl_xor(r2, o);
+    for (int o = 32; o > 0; o >>= 1) {
+        r2 += __shfl_xor(r2, o);
+        h2 += __shfl_xor(h2, o);
+    }
     if (lane == 0) {
         qs8[q] = s;
         qres8[q] = fin ? sqrtf(r2) * 1.0001f : __builtin_inff();
+        qhn2[q] = h2;
+        qhn[q] = sqrtf(h2) * 1.0001f;
     }
     for (int u = lane; u < nsup * 4; u += 64) out[q * nsup * 4 + u] = mi_units(x, 64 * (u >> 2) + 16 * (u & 3), d, s);
 }
@@ -1402,12 +1414,12 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
                                         const float *__restrict__ xn, int64_t r0, int64_t r1, int nqi,
                                         const unsigned *__restrict__ qs, int stride, const float (&qn)[QT][4],
                                         const float (&qits)[QT][4], const unsigned (&qb)[QT][4],
-                                        const float2 *__restrict__ qpar,
+                                        const float *__restrict__ qpar,
                                         const int *__restrict__ bucket, int boff, int nprobe,
                                         const int *__restrict__ slot_off, int chunk, int k, int sub, float *smem,
                                         unsigned *__restrict__ qbound, float *__restrict__ part_d,
                                         int *__restrict__ part_i, unsigned *prog, unsigned epoch, unsigned pword,
-                                        const float *__restrict__ xs8) {
+                                        const float *__restrict__ xs8, const float *__restrict__ xr8) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = lane & 15, g = lane >> 4;
@@ -1467,7 +1479,8 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
     };
 
     uint4 ring[MH_P][MF_RT];
-    float xnr[MF_RT] = {0.f, 0.f}, xsr[MF_RT] = {0.f, 0.f};  // (I8: the rows' scales)
+    float xnr[MF_RT] = {0.f, 0.f}, xsr[MF_RT] = {0.f, 0.f};  // (I8: the rows' scales; L2: their residuals below)
+    float xrr[MF_RT] = {0.f, 0.f};
     if (npass > 0) {
         set_pass(0);
 #pragma unroll
@@ -1479,6 +1492,10 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
         if constexpr (I8) {
 #pragma unroll
             for (int r = 0; r < MF_RT; ++r) xsr[r] = xs8[row_of(0, r)];
+            if (!IP) {
+#pragma unroll
+                for (int r = 0; r < MF_RT; ++r) xrr[r] = xr8[row_of(0, r)];
+            }
         }
     }
     // the item's query image (and the wide items' parameters) were written by every thread before the call: wait for
@@ -1499,7 +1516,7 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
                 if constexpr (I8) acci[qt][r] = mf_i32x4{0, 0, 0, 0};
                 else acc[qt][r] = mf_f32x4{0.f, 0.f, 0.f, 0.f};
             }
-        float xnr_next[MF_RT] = {0.f, 0.f}, xsr_next[MF_RT] = {0.f, 0.f};
+        float xnr_next[MF_RT] = {0.f, 0.f}, xsr_next[MF_RT] = {0.f, 0.f}, xrr_next[MF_RT] = {0.f, 0.f};
         if (!IP) {
 #pragma unroll
             for (int r = 0; r < MF_RT; ++r) xnr_next[r] = xn[row_of(i + 1 <= ilast ? i + 1 : ilast, r)];
@@ -1507,6 +1524,10 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
         if constexpr (I8) {
 #pragma unroll
             for (int r = 0; r < MF_RT; ++r) xsr_next[r] = xs8[row_of(i + 1 <= ilast ? i + 1 : ilast, r)];
+            if (!IP) {
+#pragma unroll
+                for (int r = 0; r < MF_RT; ++r) xrr_next[r] = xr8[row_of(i + 1 <= ilast ? i + 1 : ilast, r)];
+            }
         }
         for (int S0 = 0; S0 < nsup; S0 += MH_P) {
 #pragma unroll
@@ -1547,9 +1568,14 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
             for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
-                    float qnv, qiv;
-                    if constexpr (NT == 1) {  // wide items: (‖q‖², 1/(t·s)) from LDS (registers for 96 queries spill)
-                        const float2 p = qpar[qt * 16 + 4 * g + v];
+                    float qnv, qiv, qrv = 0.f;
+                    if constexpr (I8) {  // (‖q̂‖², s_q, 2‖q̂‖, −) from LDS
+                        const float4 p = reinterpret_cast<const float4 *>(qpar)[qt * 16 + 4 * g + v];
+                        qnv = p.x;
+                        qiv = p.y;
+                        qrv = p.z;
+                    } else if constexpr (NT == 1) {  // wide items: (‖q‖², 1/(t·s)) from LDS (registers for 96 queries spill)
+                        const float2 p = reinterpret_cast<const float2 *>(qpar)[qt * 16 + 4 * g + v];
                         qnv = p.x;
                         qiv = p.y;
                     } else {
@@ -1565,6 +1591,7 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
                         key = -av * sc;
                     } else {
                         key = fmaf(-2.f * sc, av, qnv + xnr[r]);
+                        if constexpr (I8) key = fmaf(-qrv, xrr[r], key);  // a lower bound of ‖q̂ − x‖² (header)
                         key = key < 0.f ? 0.f : key;
                     }
                     const bool ok = rok && qt * 16 + 4 * g + v < nqi;
@@ -1581,6 +1608,7 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
         for (int r = 0; r < MF_RT; ++r) {
             xnr[r] = xnr_next[r];
             xsr[r] = xsr_next[r];
+            xrr[r] = xrr_next[r];
         }
     }
 
@@ -1805,7 +1833,8 @@ __device__ __forceinline__ void mg_item(int d, const uint4 *__restrict__ codes_h
     }
 }
 
-// I8: the int8 image (every item one-term: units in qsplit, s_q in its, s_x in xs8; no residual copy)
+// I8: the int8 image (every item one-term: units in qsplit, s_q in its, s_x in xs8; no residual copy; L2: qnorm is
+// ‖q̂‖² of the dequantised queries, qhn their ‖q̂‖ and xr8 the rows' residuals — the lower-bound key of the header)
 template <bool IP, bool I8>
 __global__ void __launch_bounds__(MF_THREADS, MF_WAVES / 4)
 ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnorm, const float *__restrict__ its, int d,
@@ -1814,7 +1843,8 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
                 const int *__restrict__ item_off, const int *__restrict__ bucket, const int *__restrict__ slot_off,
                 int nlist, int nprobe, int group, int k, int sub, unsigned *__restrict__ qbound, float *__restrict__ part_d,
                 int *__restrict__ part_i, float *__restrict__ qres, int nq, int remap, unsigned *__restrict__ prog,
-                int nprog, unsigned epoch, const float *__restrict__ xs8) {
+                int nprog, unsigned epoch, const float *__restrict__ xs8, const float *__restrict__ xr8,
+                const float *__restrict__ qhn) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int total = item_off[nlist];
     if ((int)blockIdx.x >= total) return;
@@ -1862,12 +1892,16 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
     unsigned *qs = reinterpret_cast<unsigned *>(smem);
     const int nsup = I8 ? mi_nsup(d) : mh_nsup(d);
     const int stride = I8 ? mi_nsup(d) * 16 + 8 : mh_stride(d, wide ? 1 : 2);
-    float2 *qpar = reinterpret_cast<float2 *>(qs + nqi * stride);  // wide items: (‖q‖², 1/(t·s)) after the image
+    // wide items: (‖q‖², 1/(t·s)) after the image (stride: a multiple of 8 dwords, so 16-byte aligned); I8: four floats
+    float *qpar = reinterpret_cast<float *>(qs + nqi * stride);
     if (wide) {
         mh_fill<1, I8 ? 1 : 2>(qs, qsplit, nsup, stride, nqi, bucket, boff, nprobe);
         for (int t = threadIdx.x; t < nqi; t += MF_THREADS) {
             const int qi = bucket[boff + t] / nprobe;
-            qpar[t] = make_float2(IP ? 0.f : qnorm[qi], its[qi]);
+            if constexpr (I8)
+                reinterpret_cast<float4 *>(qpar)[t] =
+                    make_float4(IP ? 0.f : qnorm[qi], its[qi], IP ? 0.f : 2.f * qhn[qi], 0.f);
+            else reinterpret_cast<float2 *>(qpar)[t] = make_float2(IP ? 0.f : qnorm[qi], its[qi]);
             // these queries' scan keys miss the low term: the rerank bounds them with the one-term residual (every
             // item of the query's wide lists writes the same value)
             if (!I8) qres[qi] = qres[nq + qi];
@@ -1879,7 +1913,7 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
 
     const int lane = threadIdx.x & 63, g = lane >> 4;
 #define MH_ARGS d, codes_h, tp0, xn, r0, r1, nqi, qs, stride, qn, qi_s, qb, qpar, bucket, boff, nprobe, slot_off, chunk, k, sub, smem, \
-                qbound, part_d, part_i, pw, epoch, pword, xs8
+                qbound, part_d, part_i, pw, epoch, pword, xs8, xr8
 #define MH_QN(QTV)                                                                                          \
     float qn[QTV][4], qi_s[QTV][4];                                                                         \
     unsigned qb[QTV][4];                                                                                    \
@@ -1915,9 +1949,10 @@ int ivf_scan_sublists() { return MF_WAVES; }
 int64_t ivf_half_pass_bytes(int d) { return (int64_t)mh_nsup(d) * MF_RT * 64 * 16; }
 int64_t ivf_half_qsplit_bytes(int64_t nq, int d) { return nq * 2 * mh_nsup(d) * 64; }
 bool ivf_mfma_h_supported(int d, int k) { return d >= 1 && k >= 1 && k <= MF_KMAX && mh_group(d) >= 16; }
-// int8 image: every item one-term, up to 96 queries (MH_QTW tiles) that fit the LDS with their (‖q‖², s_q)
+// int8 image: every item one-term, up to 96 queries (MH_QTW tiles) that fit the LDS with their four parameters
+// (‖q̂‖², s_q, 2‖q̂‖, −: 16 B per query, 1.5 KiB for 96)
 int ivf_mfma_i8_group(int d) {
-    const int g = (int)(MF_LDS_MAX / ((size_t)(mi_nsup(d) * 16 + 8) * 4 + 8)) / 16 * 16;
+    const int g = (int)(MF_LDS_MAX / ((size_t)(mi_nsup(d) * 16 + 8) * 4 + 16)) / 16 * 16;
     return (g < 16 * MH_QTW ? g : 16 * MH_QTW) << 8;
 }
 int64_t ivf_i8_pass_bytes(int d) { return (int64_t)mi_nsup(d) * MF_RT * 64 * 16; }
@@ -1926,27 +1961,22 @@ bool ivf_mfma_i8_supported(int d, int k) {
     return d >= 1 && k >= 1 && k <= MF_KMAX && ivf_group_wide(ivf_mfma_i8_group(d)) >= 16;
 }
 void launch_ivf_tile_i8(const float *codes, const int64_t *list_off, const int *list_len, const int64_t *tpass_off,
-                        int nlist, int64_t total_pass, int d, void *dst, float *xs8, hipStream_t st,
-                        const int64_t *pass_ids) {
+                        int nlist, int64_t total_pass, int d, void *dst, float *xs8, float *xr8, unsigned *nonfin,
+                        hipStream_t st, const int64_t *pass_ids) {
+    if (nonfin) HIPANN_CHECK(hipMemsetAsync(nonfin, 0, sizeof(unsigned), st));
     if (total_pass <= 0) return;
     HIPANN_REQUIRE(total_pass < (int64_t)0x7fffffff, "too many passes");
+    HIPANN_REQUIRE(xs8 && xr8, "int8 image: missing scale / residual planes");
     hipLaunchKernelGGL(ivf_tile_i8, dim3((unsigned)total_pass), dim3(256), 0, st, codes, list_off, list_len, tpass_off,
-                       nlist, d, mi_nsup(d), static_cast<uint4 *>(dst), xs8, pass_ids);
-    HIPANN_CHECK(hipGetLastError());
-}
-void launch_ivf_i8_residual(const float *codes, int64_t n, int d, unsigned *out, hipStream_t st) {
-    HIPANN_CHECK(hipMemsetAsync(out, 0, sizeof(unsigned), st));
-    if (n <= 0) return;
-    HIPANN_REQUIRE(ceil_div(n, 4) < (int64_t)0x7fffffff, "too many rows");
-    hipLaunchKernelGGL(ivf_i8_residual, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, st, codes, n, d, out);
+                       nlist, d, mi_nsup(d), static_cast<uint4 *>(dst), xs8, xr8, nonfin, pass_ids);
     HIPANN_CHECK(hipGetLastError());
 }
 void launch_ivf_split_queries_i8(const float *Q, int64_t nq, int d, void *qi8, float *qs8, float *qres8,
-                                 hipStream_t st) {
+                                 float *qhn2, float *qhn, hipStream_t st) {
     if (nq <= 0) return;
     HIPANN_REQUIRE(ceil_div(nq, 4) < (int64_t)0x7fffffff, "too many queries");
     hipLaunchKernelGGL(ivf_split_queries_i8, dim3((unsigned)ceil_div(nq, 4)), dim3(256), 0, st, Q, nq, d, mi_nsup(d),
-                       static_cast<uint4 *>(qi8), qs8, qres8);
+                       static_cast<uint4 *>(qi8), qs8, qres8, qhn2, qhn);
     HIPANN_CHECK(hipGetLastError());
 }
 
@@ -2003,13 +2033,15 @@ void launch_ivf_scan_mfma_h(const float *Q, int64_t nq, void *qsplit, float *its
                             const int64_t *list_off, const int *list_len, const int *cnt, const int *bucket_off,
                             const int *item_off, const int *bucket, const int *slot_off, int nlist, int nprobe, int k,
                             int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, bool split_done,
-                            int sub, unsigned *prog, int nprog, unsigned epoch, int i8mode, const float *xs8) {
+                            int sub, unsigned *prog, int nprog, unsigned epoch, int i8mode, const float *xs8,
+                            const float *xr8, const float *qhn) {
     if (max_items <= 0 || nq <= 0) return;
     HIPANN_REQUIRE(max_items < (int64_t)0x7fffffff, "too many IVF work items");
     HIPANN_REQUIRE(qsplit && its && qres && codes_h, "fp16 IVF scan: missing buffers");
     HIPANN_REQUIRE(i8mode ? ivf_mfma_i8_supported(d, k) && xs8 && split_done : ivf_mfma_h_supported(d, k),
                    "fp16 / int8 IVF scan needs k <= 16 (int8: scales and prepared queries)");
     HIPANN_REQUIRE(metric == kIP || (qn && xn), "decomposed L2 scan needs query and row norms");
+    HIPANN_REQUIRE(!i8mode || metric == kIP || (xr8 && qhn), "int8 L2 scan needs the rows' residuals and the queries' norms");
     const int nsup = mh_nsup(d);
     uint4 *qs = static_cast<uint4 *>(qsplit);
     if (!split_done)
@@ -2019,7 +2051,7 @@ void launch_ivf_scan_mfma_h(const float *Q, int64_t nq, void *qsplit, float *its
     const int gw = ivf_group_wide(group);
     const size_t merge = (size_t)(MF_WAVES / 2) * (gw ? MH_QTW : MF_QTMAX) * 4 * 64 * sizeof(float2);
     const size_t wstride = i8mode ? (size_t)(mi_nsup(d) * 16 + 8) * 4 : (size_t)mh_stride(d, 1) * 4;
-    const size_t smem = std::max({(size_t)ivf_group_narrow(group) * mh_stride(d) * 4, (size_t)gw * (wstride + 8), merge,
+    const size_t smem = std::max({(size_t)ivf_group_narrow(group) * mh_stride(d) * 4, (size_t)gw * (wstride + (i8mode ? 16 : 8)), merge,
                                   ivf_group_gemm(group) ? MG_LDS : (size_t)0});
     HIPANN_REQUIRE(smem <= MF_LDS_MAX, "fp16 IVF scan: LDS image too large");
     HIPANN_REQUIRE(nq < (int64_t)0x7fffffff, "fp16 IVF scan: batch too large");
@@ -2029,7 +2061,7 @@ void launch_ivf_scan_mfma_h(const float *Q, int64_t nq, void *qsplit, float *its
     // contiguous runs per XCD
     static const int remap = [] { const char *e = std::getenv("HIPANN_IVF_REMAP"); return !e || std::atoi(e) ? 1 : 0; }();
 #define MH_LAUNCH_ARGS qs, qn, its, d, ch, tpass_off, xn, list_off, list_len, cnt, bucket_off, item_off, bucket, slot_off, nlist, nprobe, \
-                       group, k, sub, qbound, pd, pi, qres, (int)nq, remap, prog, nprog, epoch, xs8
+                       group, k, sub, qbound, pd, pi, qres, (int)nq, remap, prog, nprog, epoch, xs8, xr8, qhn
     if (i8mode) {
         if (metric == kIP) hipLaunchKernelGGL((ivf_scan_mfma_h<true, true>), grid, block, smem, st, MH_LAUNCH_ARGS);
         else hipLaunchKernelGGL((ivf_scan_mfma_h<false, true>), grid, block, smem, st, MH_LAUNCH_ARGS);

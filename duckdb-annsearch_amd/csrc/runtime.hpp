@@ -421,11 +421,26 @@ struct IvfShard {
     int half_state = 0, half_es = 0;
     float half_rxmax = 0.f;
     DevBuf codes_h, hsplit, hits, hres;
-    // kFormI8Exact: tiled int8 image (same passes), per-row scales, its largest row residual ‖x − s·x̂‖, the batch's
-    // int8 queries / scales / residuals; i8_state as half_state (released by appends: rebuilt at the next search)
+    // kFormI8Exact: tiled int8 image (same passes), per-row scales (xs8) and residuals ‖x − s·x̂‖ (xr8), the batch's
+    // int8 queries / scales / residuals / dequantised norms (‖q̂‖², ‖q̂‖); i8_state as half_state.  Adds and removes
+    // re-tile the touched passes (i8_tiled: passes tiled since creation).  i8_rxmax: the largest row residual, the IP
+    // bound's only (−1: to be taken from xr8 at the next IP search; L2 certifies with each row's own residual)
     int i8_state = 0;
-    float i8_rxmax = 0.f;
-    DevBuf codes_i8, xs8, qi8, qs8, qres8;
+    float i8_rxmax = -1.f;
+    int64_t i8_tiled = 0;
+    DevBuf codes_i8, xs8, xr8, qi8, qs8, qres8, qhn2, qhn;
+    // The exact fp16 form's choice of filter image (hipann_ivf_set_filter_image, auto): auto8 0 untested, 1 int8,
+    // −1 fp16; auto8_live: the live rows at the last probation (a quarter more rows: probation again); auto8_over:
+    // consecutive int8 batches whose flag count broke the byte rule.  fb_host (pinned, host-mapped): batch number
+    // << 32 | flag count of the latest int8 batch, written by its fallback launch and read by the next call — no
+    // host synchronisation and no stream marker in the steady state.  count_only: probation's int8 pass (scratch
+    // outputs probe_D / probe_I, no re-run of flagged queries, the flag count left in nflag).
+    int auto8 = 0, auto8_over = 0;
+    int64_t auto8_live = 0;
+    HostBuf fb_host;
+    uint64_t fb_seq = 0, fb_seen = 0;
+    bool count_only = false;
+    DevBuf probe_D, probe_I;
     DevBuf prog;  // fp16 scan: per 64-pass chunk key, the latest item's position (rounds) and the batch it belongs to
     // an append's staging (hipann_ivf_add): the new rows grouped by list, labels, physical destinations, norms,
     // the tiled passes they touch, and the new rows' maxima (‖x‖², |x|, fp16 residual²)
@@ -446,6 +461,7 @@ struct IvfIndex : IndexBase {
     int nlist = 0, nprobe = 1;
     std::vector<int> owner;  // list → shard (size-balanced at create; appended rows follow their list)
     int form = kFormHalfExact;
+    int filter_image = 2, last_filter_image = 0;  // hipann_ivf_set_filter_image (0 fp16, 1 int8, 2 auto); the last search's
     int64_t rerank_fallbacks = 0;  // queries re-run from the host (HIPANN_IVF_HOST_FALLBACK); device re-runs: fb_total
     std::vector<std::unique_ptr<IvfShard>> shards;
     int64_t last_nq = 0;
@@ -463,7 +479,8 @@ struct IvfIndex : IndexBase {
         int64_t b = 0;
         for (auto &s : shards)
             b += s->n * ((int64_t)d * 4 + 8 + (metric == kL2 ? 4 : 0)) + (int64_t)nlist * d * 4 +
-                 (int64_t)s->codes_h.bytes + (int64_t)s->codes_t.bytes + (int64_t)s->codes_i8.bytes + (int64_t)s->xs8.bytes;
+                 (int64_t)s->codes_h.bytes + (int64_t)s->codes_t.bytes + (int64_t)s->codes_i8.bytes + (int64_t)s->xs8.bytes +
+                 (int64_t)s->xr8.bytes;
         return b;
     }
 };
@@ -530,14 +547,16 @@ void launch_ivf_rerank(const float *pd, const int *pi, const int *slot_off, int 
                        const unsigned *qbound = nullptr, const float *qnorm = nullptr, int kslot = 0, int sub = 0,
                        const int *list_len = nullptr, float *fpd = nullptr, long long *fpi = nullptr,
                        unsigned long long *fb_total = nullptr,  // fpd != nullptr: flagged IVF queries re-run inline
-                       int fb_cap = 0);  // ... except the first fb_cap, left to launch_ivf_fallback_chunks
+                       int fb_cap = 0,  // ... except the first fb_cap, left to launch_ivf_fallback_chunks
+                       int i8_l2 = 0);  // the int8 image's L2 certificate (qres = ‖q − q̂‖, lower-bound scan keys)
 // the rerank's first fb_cap flagged queries re-run in parallel (one wave per (query, probe, chunk) item); cpd/cpi:
 // fb_cap·nprobe·maxch·kout entries, done: fb_cap counters (zero on entry; left zero)
 void launch_ivf_fallback_chunks(const int *nflag, const int *flagged, int fb_cap, int nprobe, int maxch, int chunk_rows,
                                 int kout, int metric, const float *Q, const float *codes, int d, const int64_t *ids,
                                 int64_t label_offset, const int64_t *probes, const int64_t *list_off,
                                 const int *list_len, int nlist, float *cpd, long long *cpi, unsigned *done, float *D,
-                                int64_t *I, unsigned long long *total, hipStream_t st);
+                                int64_t *I, unsigned long long *total, hipStream_t st,
+                                unsigned long long *host_word = nullptr, unsigned host_seq = 0);
 // ivf_mfma.hip, fp16-image scan (kFormHalfExact)
 int ivf_mfma_h_group(int d);
 int ivf_scan_sublists();  // sub-lists per slot of the matrix-core scans in sub-list mode (one per wave)
@@ -556,19 +575,19 @@ void launch_ivf_scan_mfma_h(const float *Q, int64_t nq, void *qsplit, float *its
                             const int *bucket, const int *slot_off, int nlist, int nprobe, int k, int64_t max_items,
                             unsigned *qbound, float *pd, int *pi, hipStream_t st, bool split_done = false,
                             int sub = 0, unsigned *prog = nullptr, int nprog = 0, unsigned epoch = 0, int i8mode = 0,
-                            const float *xs8 = nullptr);
-// int8 image (kFormI8Exact): packed group (wide items only), pass / query-image bytes, support, the tiling (one scale per
-// row into xs8), max row residual² (float bits), the batch's int8 queries (units, scales, residuals)
+                            const float *xs8 = nullptr, const float *xr8 = nullptr, const float *qhn = nullptr);
+// int8 image (kFormI8Exact): packed group (wide items only), pass / query-image bytes, support, the tiling (one scale
+// and one residual per row into xs8 / xr8; *nonfin != 0 afterwards: a non-finite row), the batch's int8 queries (units,
+// scales, residuals, ‖q̂‖² and ‖q̂‖ of the dequantised queries)
 int ivf_mfma_i8_group(int d);
 int64_t ivf_i8_pass_bytes(int d);
 int64_t ivf_i8_qimg_bytes(int64_t nq, int d);
 bool ivf_mfma_i8_supported(int d, int k);
 void launch_ivf_tile_i8(const float *codes, const int64_t *list_off, const int *list_len, const int64_t *tpass_off,
-                        int nlist, int64_t total_pass, int d, void *dst, float *xs8, hipStream_t st,
-                        const int64_t *pass_ids = nullptr);
-void launch_ivf_i8_residual(const float *codes, int64_t n, int d, unsigned *out, hipStream_t st);
+                        int nlist, int64_t total_pass, int d, void *dst, float *xs8, float *xr8, unsigned *nonfin,
+                        hipStream_t st, const int64_t *pass_ids = nullptr);
 void launch_ivf_split_queries_i8(const float *Q, int64_t nq, int d, void *qi8, float *qs8, float *qres8,
-                                 hipStream_t st);
+                                 float *qhn2, float *qhn, hipStream_t st);
 // the batch's fp16 query terms (+ 1/(t·s), split residuals) and, when qn != nullptr, ‖q‖² (row_norms_f32's bits)
 void launch_ivf_split_queries_h(const float *Q, int64_t nq, int d, int es, void *qsplit, float *its, float *qres,
                                 float *qn, hipStream_t st);

@@ -122,6 +122,10 @@ def lib() -> C.CDLL:
             "hipann_ivf_set_form": ([vp, i32], i32),
             "hipann_ivf_get_form": ([vp], i32),
             "hipann_ivf_rerank_fallbacks": ([vp], i64),
+            "hipann_ivf_i8_passes_tiled": ([vp], i64),
+            "hipann_ivf_set_filter_image": ([vp, i32], i32),
+            "hipann_ivf_get_filter_image": ([vp], i32),
+            "hipann_ivf_last_filter_image": ([vp], i32),
             "hipann_ntotal": ([vp], i64),
             "hipann_dim": ([vp], i32),
             "hipann_metric": ([vp], i32),
@@ -524,6 +528,27 @@ class HipIndexIVFFlat(_Handle):
     def rerank_fallbacks(self) -> int:
         """Queries the exact form's bound check flagged since creation (re-run on the device in the direct form)."""
         return int(lib().hipann_ivf_rerank_fallbacks(self._h))
+
+    FILTER_FP16, FILTER_INT8, FILTER_AUTO = 0, 1, 2
+
+    @property
+    def filter_image(self) -> int:
+        """The image form 6 requests filter through (hipann_ivf_set_filter_image): 0 fp16, 1 int8, 2 auto (default)."""
+        return int(lib().hipann_ivf_get_filter_image(self._h))
+
+    @filter_image.setter
+    def filter_image(self, v: int) -> None:
+        if lib().hipann_ivf_set_filter_image(self._h, int(v)) != 0:
+            raise HipAnnError("filter image must be 0 (fp16), 1 (int8) or 2 (auto)")
+
+    def last_filter_image(self) -> int:
+        """The image the last search scanned: 0 fp16 (or none), 1 int8."""
+        return int(lib().hipann_ivf_last_filter_image(self._h))
+
+    def i8_passes_tiled(self) -> int:
+        """32-row passes of the int8 image (form 7) tiled since creation: all of them at the first int8 search, then
+        only those an add or a remove touched."""
+        return int(lib().hipann_ivf_i8_passes_tiled(self._h))
 
     def last_probes(self, nq: int) -> np.ndarray:
         P = np.empty((nq, min(self._nprobe, self.nlist)), np.int64)

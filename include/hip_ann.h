@@ -252,8 +252,8 @@ int hipann_ivf_add(void *index, int64_t n, const float *xb, const int64_t *ids, 
  * so the call can be made on the CPU index and the GPU copy alike (at DELETE or VACUUM time) and hipann_ivf_export
  * stays equal to the CPU index's lists.  Returns rows removed, or -1.  Synchronous; n == 0 returns 0.  The work runs
  * on the device, on the lists each shard owns: the cost is the id lookup (8 bytes per live row) plus the rows moved,
- * not the table; the freed rows become append slack that a later hipann_ivf_add reuses.  The fp16 / fp32 tiled images
- * are re-tiled only where rows moved; the int8 image (form 7) is rebuilt at its next search.  A borrowed handle
+ * not the table; the freed rows become append slack that a later hipann_ivf_add reuses.  The fp16 / fp32 / int8
+ * tiled images are re-tiled only where rows moved (the int8 image with its rows' scales and residuals).  A borrowed handle
  * (hipann_ivf_create_device with copy = 0) moves into owned storage first, as at its first add.  Extra HBM during the
  * call: 5 bytes per physical row, 8 per label and 8 per 32-row pass of a built image, all allocated before a row moves.
  * NOTE: hipann_ivf_add with ids == NULL still labels its rows ntotal + i, as FAISS does; after a removal that can
@@ -327,11 +327,32 @@ int hipann_ivf_export(void *index, float *centroids, int64_t *list_offsets, int6
 /* HIPANN_IVF_FORM_I8_EXACT (opt-in): the same filter + exact rerank over a tiled int8 image (one scale per row,
  * max|x|/127: a quarter of the fp32 rows' bytes) against int8 queries on the int8 matrix cores (exact int32 sums);
  * the scan always keeps per-wave sub-lists and the rerank takes 64 candidates, certified with the int8 residuals.
- * The image is rebuilt at the first search after an add.  Codes with a non-finite entry, or k > 64, take
+ * L2: each row's own residual ‖x − s·x̂‖ (one float per row beside its scale) is subtracted in the scan, so the key
+ * is a lower bound of ‖q̂ − x‖² for the dequantised query q̂, and a query is certified when sqrt(d_k) + ‖q − q̂‖ lies
+ * below the square root of the smallest pruned key; IP: the Cauchy-Schwarz bound with the largest row residual.
+ * The image costs n·(d + 8) bytes (+ padding of d to 64 and of the lists to 32 rows) and is kept across adds and
+ * removes, which re-tile only the 32-row passes they touch.  Codes with a non-finite entry, or k > 64, take
  * SPLIT2_EXACT.  Results equal SPLIT2_EXACT's. */
 #define HIPANN_IVF_FORM_I8_EXACT 7
 int hipann_ivf_set_form(void *index, int form);
 int hipann_ivf_get_form(void *index);
+/* The filter image of HIPANN_IVF_FORM_HALF_EXACT requests: 0 = the fp16 image, 1 = the int8 image of form 7 (where it
+ * applies: L2, k <= 12, a shape the int8 scan holds), 2 = auto (default).  The exact rerank certifies either filter,
+ * so the rows and distances returned are the same; hipann_last_search_path keeps reporting form 6 (with the filter
+ * depth and sub-lists that ran) and hipann_ivf_last_filter_image tells which image the last search scanned.
+ * Auto considers the int8 image for L2 batches of 64 queries or more.  Per shard, the first such batch is answered
+ * through the fp16 image and then run once more through the int8 image into scratch, only counting the queries its
+ * certificate flags (one host synchronisation); the int8 image is taken when their direct-form re-runs would cost
+ * less than a quarter of the bytes it saves (flagged < nlist / (16 nprobe)), dropped after two consecutive batches
+ * over that rule, and tried again when the shard has grown by a quarter.  The int8 image costs n (d + 12) more bytes
+ * of HBM (image, scale and residual per row).  HIPANN_IVF_FILTER_IMAGE=0|1|2 in the environment overrides the
+ * setting (A/B).  Return 0 / the mode, or -1 for a bad handle or mode. */
+int hipann_ivf_set_filter_image(void *index, int mode);
+int hipann_ivf_get_filter_image(void *index);
+int hipann_ivf_last_filter_image(void *index);
+/* 32-row passes of the int8 image tiled since the index was created, summed over its shards (the first int8 search
+ * tiles every pass; an add or a remove only the passes it touched).  −1 for a bad handle. */
+int64_t hipann_ivf_i8_passes_tiled(void *index);
 /* Queries the exact forms' bound check flagged since the index was created (each re-run on the device in
  * the direct form; reading the device-side count synchronises the device). */
 int64_t hipann_ivf_rerank_fallbacks(void *index);
