@@ -248,6 +248,10 @@ void compute_row_norms(IvfShard &sh, int d, int metric) {
 namespace hipann {
 
 IvfIndex::~IvfIndex() {
+    if (!shards.empty()) {
+        DeviceGuard g(shards[0]->device);
+        ivf_mh_stats_report();
+    }
     for (auto &s : shards) {
         s->quant.reset();
         DeviceGuard g(s->device);

@@ -34,14 +34,16 @@
 #include "wave_topk.hpp"
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 namespace hipann {
 
 typedef float mf_f32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef HIPANN_MF_EXPERIMENT
-#define HIPANN_MF_EXPERIMENT 0  // tuning builds only (wrong results): 1 no selection, 2 no row loads, 3 no MFMA
+#define HIPANN_MF_EXPERIMENT 0  // tuning builds only (wrong results): 1 no selection (mf_item, mh_item), 2 no row loads, 3 no MFMA
 #endif
 
 #ifndef HIPANN_MF_WAVES
@@ -146,6 +148,21 @@ __device__ __forceinline__ void row_merge16(uint64_t &l, uint64_t c, int m) {
     row_cx<4>(l, m & 4);
     row_cx<2>(l, m & 2);
     row_cx<1>(l, m & 1);
+}
+// Insert at most one pair per DPP row into the row's sorted list: c holds the pair in one lane of the row and MF_EMPTY
+// (all ones) in the others, so the row's AND is the pair (four DPP stages, quads then halves), and lane m keeps its
+// entry when that is ≤ the pair, else takes the larger of the pair and lane m − 1's entry (lane 0: the pair).  A row
+// without a pair (AND = MF_EMPTY) keeps its list.  About a quarter of the sort + merge network's instructions.
+__device__ __forceinline__ void row_insert1(uint64_t &l, uint64_t c) {
+    c &= row_xor<1>(c);
+    c &= row_xor<2>(c);
+    c &= row_xor<7>(c);
+    c &= row_xor<15>(c);
+    // row_shr:1, bound_ctrl: lane 0 of a row reads zero (below every pair)
+    const unsigned plo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)l, 0x111, 0xF, 0xF, true);
+    const unsigned phi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(l >> 32), 0x111, 0xF, 0xF, true);
+    const uint64_t prev = ((uint64_t)phi << 32) | plo;
+    l = l <= c ? l : (prev <= c ? c : prev);
 }
 // Element kth of every row's list, broadcast to the row's lanes (the row's admission threshold).
 __device__ __forceinline__ uint64_t row_kth(uint64_t l, int kth, int g) {
@@ -943,6 +960,26 @@ typedef _Float16 mh_f16x8 __attribute__((ext_vector_type(8)));
 #ifndef HIPANN_MH_NT
 #define HIPANN_MH_NT 1  // non-temporal row loads (the image is read once per batch): 2.67 -> 2.59 ms at 10M x 768
 #endif
+#ifndef HIPANN_MH_INSERT
+// A step of mh_item's epilogue whose four queries each admit at most this many of the tile's 16 rows inserts them one
+// by one (row_insert1) instead of sorting the 16 candidates and merging them; 0: always sort and merge.
+// Measured on the headline batch (10M x 768, nlist 1024, nprobe 32, nq 1024, k 10, int8 image; same box, alternating,
+// profiles/ivf_scan_epilogue/): 43 % of the steps admit a row (79 % in the fifth of the blocks that starts first), 1.6
+// rows per such step (7.1), and 99 % (74 %) of those steps take the insertions at 3.  Scan 1.93 ms (0) -> 1.78 ms (1)
+// -> 1.76 ms (3), with no selection at all (HIPANN_MF_EXPERIMENT=1) 1.47 ms; plain bench 2.11 - 2.13 ms (0), 1.99 -
+// 2.01 (1), 1.91 - 1.97 (3).  The fp16 image's scan does not move (2.50 -> 2.49 ms; without selection 2.45 ms).
+#define HIPANN_MH_INSERT 3
+#endif
+#ifndef HIPANN_MH_STATS
+// 1 (tuning builds): count the epilogue's work per image (fp16 | int8) — passes, (row tile, query tile, register)
+// steps, steps that admitted a row, the rows they admitted and the steps that took the insertions — the first fifth
+// of a launch's blocks (the ones that start with the loosest bounds) apart from the rest; printed once, when an index
+// closes (ivf_mh_stats_report)
+#define HIPANN_MH_STATS 0
+#endif
+#if HIPANN_MH_STATS
+__device__ unsigned long long mh_stats_dev[2][2][5];
+#endif
 constexpr int MH_P = HIPANN_MH_P;  // super-steps in flight per wave: 6 × 2 row tiles × 16 B = 192 B per lane
 __host__ __device__ inline int mh_nsup(int d) { return (int)ceil_div(ceil_div(d, 32), MH_P) * MH_P; }
 // LDS dwords per query: NT terms × super-steps × 4 groups × 4 dwords, + 8 (≡ 8 mod 64: conflict-free)
@@ -1419,7 +1456,7 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
                                         const int *__restrict__ slot_off, int chunk, int k, int sub, float *smem,
                                         unsigned *__restrict__ qbound, float *__restrict__ part_d,
                                         int *__restrict__ part_i, unsigned *prog, unsigned epoch, unsigned pword,
-                                        const float *__restrict__ xs8, const float *__restrict__ xr8) {
+                                        const float *__restrict__ xs8, const float *__restrict__ xr8, int stat_part) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = lane & 15, g = lane >> 4;
@@ -1508,6 +1545,8 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
 
     mf_f32x4 acc[QT][MF_RT];
     mf_i32x4 acci[QT][MF_RT];  // (I8: int32 sums)
+    uint64_t sink = 0;                                                               // (HIPANN_MF_EXPERIMENT)
+    [[maybe_unused]] unsigned st_step = 0, st_hit = 0, st_rows = 0, st_ins = 0;      // (HIPANN_MH_STATS)
     for (int i = 0; i < npass; ++i) {
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt)
@@ -1597,9 +1636,37 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
                     const bool ok = rok && qt * 16 + 4 * g + v < nqi;
                     const unsigned ks = mf_sortable(key);
                     uint64_t cp = ok ? (((uint64_t)ks << 32) | rid) : MF_EMPTY;
-                    if (__ballot(ok && ks <= thr[qt][v])) {
-                        row_sort16(cp, m);
-                        row_merge16(lst[qt][v], cp, m);
+                    if (HIPANN_MH_STATS) ++st_step;
+                    if (HIPANN_MF_EXPERIMENT == 1) {
+                        sink ^= cp;  // keeps the keys live
+                    } else if (const uint64_t hit = __ballot(ok && ks <= thr[qt][v])) {
+                        // the most admitted rows any of the four queries has in its 16 lanes (scalar)
+                        int most = 0;
+#pragma unroll
+                        for (int f = 0; f < 4; ++f) {
+                            const int c = __popc((unsigned)(hit >> (16 * f)) & 0xffffu);
+                            most = c > most ? c : most;
+                        }
+                        if (HIPANN_MH_STATS) { ++st_hit; st_rows += __popcll(hit); st_ins += most <= HIPANN_MH_INSERT; }
+                        if (most <= HIPANN_MH_INSERT) {
+                            // few: one insertion per round, of every query's lowest pending lane.  Either way the list
+                            // becomes the 16 smallest of itself and the admitted rows; the rows the sort would have
+                            // merged besides them lie above the k-th key and never reach the first k entries.
+                            uint64_t pend = hit;
+                            do {
+                                uint64_t first = 0;
+#pragma unroll
+                                for (int f = 0; f < 4; ++f) {
+                                    const unsigned x = (unsigned)(pend >> (16 * f)) & 0xffffu;
+                                    first |= (uint64_t)(x & (0u - x)) << (16 * f);
+                                }
+                                row_insert1(lst[qt][v], (first >> lane) & 1 ? cp : MF_EMPTY);
+                                pend &= ~first;
+                            } while (HIPANN_MH_INSERT > 1 && pend);
+                        } else {
+                            row_sort16(cp, m);
+                            row_merge16(lst[qt][v], cp, m);
+                        }
                         thr[qt][v] = row_kth_key(lst[qt][v], k - 1, g);
                     }
                 }
@@ -1612,6 +1679,17 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
         }
     }
 
+    if (HIPANN_MF_EXPERIMENT == 1 && sink == 1) part_d[0] = 0.f;
+#if HIPANN_MH_STATS
+    if (lane == 0) {
+        unsigned long long *st = mh_stats_dev[I8][stat_part];
+        atomicAdd(st + 0, (unsigned long long)npass);
+        atomicAdd(st + 1, (unsigned long long)st_step);
+        atomicAdd(st + 2, (unsigned long long)st_hit);
+        atomicAdd(st + 3, (unsigned long long)st_rows);
+        atomicAdd(st + 4, (unsigned long long)st_ins);
+    }
+#endif
     mf_finish_item<QT>(lst, smem, nqi, bucket, boff, nprobe, slot_off, chunk, k, sub, qbound, part_d, part_i);
 }
 
@@ -1912,8 +1990,9 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
     if (!HIPANN_MH_EARLY) __syncthreads();  // (early: mh_item waits for the fill after issuing its first row loads)
 
     const int lane = threadIdx.x & 63, g = lane >> 4;
+    const int stat_part = (int64_t)blockIdx.x * 5 < (int64_t)total ? 0 : 1;  // (HIPANN_MH_STATS)
 #define MH_ARGS d, codes_h, tp0, xn, r0, r1, nqi, qs, stride, qn, qi_s, qb, qpar, bucket, boff, nprobe, slot_off, chunk, k, sub, smem, \
-                qbound, part_d, part_i, pw, epoch, pword, xs8, xr8
+                qbound, part_d, part_i, pw, epoch, pword, xs8, xr8, stat_part
 #define MH_QN(QTV)                                                                                          \
     float qn[QTV][4], qi_s[QTV][4];                                                                         \
     unsigned qb[QTV][4];                                                                                    \
@@ -1942,6 +2021,21 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
 #undef MH_CASE
 #undef MH_QN
 #undef MH_ARGS
+}
+
+// HIPANN_MH_STATS builds: print the epilogue's counters (and clear them); every other build: nothing
+void ivf_mh_stats_report() {
+#if HIPANN_MH_STATS
+    unsigned long long h[2][2][5];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(mh_stats_dev), sizeof(h)) != hipSuccess) return;
+    for (int i8 = 0; i8 < 2; ++i8)
+        for (int part = 0; part < 2; ++part)
+            std::fprintf(stderr, "HIPANN_MH_STATS image=%s blocks=%s passes=%llu steps=%llu hit_steps=%llu admitted_rows=%llu "
+                                 "insert_steps=%llu\n", i8 ? "int8" : "fp16", part ? "rest" : "first_fifth", h[i8][part][0],
+                         h[i8][part][1], h[i8][part][2], h[i8][part][3], h[i8][part][4]);
+    std::memset(h, 0, sizeof(h));
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(mh_stats_dev), h, sizeof(h));
+#endif
 }
 
 int ivf_mfma_h_group(int d) { return mh_group_packed(d); }

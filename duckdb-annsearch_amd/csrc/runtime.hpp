@@ -559,6 +559,7 @@ void launch_ivf_fallback_chunks(const int *nflag, const int *flagged, int fb_cap
                                 unsigned long long *host_word = nullptr, unsigned host_seq = 0);
 // ivf_mfma.hip, fp16-image scan (kFormHalfExact)
 int ivf_mfma_h_group(int d);
+void ivf_mh_stats_report();  // HIPANN_MH_STATS tuning builds: the fp16 / int8 scan epilogue's counters, to stderr
 int ivf_scan_sublists();  // sub-lists per slot of the matrix-core scans in sub-list mode (one per wave)
 int64_t ivf_half_pass_bytes(int d);
 int64_t ivf_half_qsplit_bytes(int64_t nq, int d);
