@@ -99,25 +99,16 @@ constexpr float kSplit2Eps = 0x1p-12f;
 __host__ __device__ inline bool ivf_form_split(int f) { return f == kFormSplit3 || f == kFormSplit2; }
 __host__ __device__ inline int ivf_form_terms(int f) { return f == kFormSplit3 ? 3 : 2; }
 
-// Query groups of an IVF list probed by c queries.  `group` packs the scan's group sizes: narrow (bits 0-7), wide
-// (bits 8-15, 0 = none) and GEMM (bits 16-27, 0 = none).  A list probed by more queries than the narrow size is
-// scanned in groups of up to the wide size (the fp16 scan's one-term items, ivf_mfma.hip), and one probed by more
-// than the wide size in groups of up to the GEMM size (the GEMM-shaped items), so its rows are streamed ceil(c / size)
-// times.  A narrow size of 0 makes every probed list at least wide (the default of the fp16 form).
+// Query groups of an IVF list probed by c queries.  `group` packs the scan's group sizes: narrow (bits 0-7) and wide
+// (bits 8-15, 0 = none).  A list probed by more queries than the narrow size is scanned in groups of up to the wide
+// size, so its rows are streamed ceil(c / size) times.  Forms 0-5 have a narrow size only; the fp16 and int8 image
+// scans (ivf_mfma.hip) a wide size only: a narrow size of 0 makes every probed list wide.
 __host__ __device__ inline int ivf_group_narrow(int group) { return group & 0xff; }
 __host__ __device__ inline int ivf_group_wide(int group) { return (group >> 8) & 0xff; }
-__host__ __device__ inline int ivf_group_gemm(int group) { return group >> 16; }
-// 0 narrow, 1 wide, 2 GEMM
-__host__ __device__ inline int ivf_list_class(int c, int group) {
-    const int n = ivf_group_narrow(group), w = ivf_group_wide(group), m = ivf_group_gemm(group);
-    if (m > 0 && c > (w > 0 ? w : n)) return 2;
-    return w > 0 && c > n ? 1 : 0;
-}
-__host__ __device__ inline bool ivf_list_wide(int c, int group) { return ivf_list_class(c, group) == 1; }
 __host__ __device__ inline int ivf_ngroups(int c, int group) {
     if (c <= 0) return 0;  // (an unprobed list: no division by a zero narrow size)
-    const int cls = ivf_list_class(c, group);
-    const int g = cls == 2 ? ivf_group_gemm(group) : cls == 1 ? ivf_group_wide(group) : ivf_group_narrow(group);
+    const int n = ivf_group_narrow(group), w = ivf_group_wide(group);
+    const int g = w > 0 && c > n ? w : n;
     return (c + g - 1) / g;
 }
 // the smallest group size (the work-item bound)

@@ -445,7 +445,7 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
         i8 = sub_req && ivf_mfma_i8_supported(d, kRerankK) && ensure_i8_codes(sh, d, nlist, st);
         req = kFormSplit2Exact;
     }
-    const bool img = half || i8;  // a tiled fp16 / int8 image and the one-term (or two-term) item scan
+    const bool img = half || i8;  // a tiled fp16 / int8 image and the one-term item scan
     // kFormSplit2Exact: the 2-term scan keeps kRerankK per list (per wave with sub-lists), the rerank makes the
     // results exact
     const bool want_exact = req == kFormSplit2Exact;
@@ -595,29 +595,15 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
         RoctxRange rr("hipann.ivf.scan");
         ScopedTiming t(ix.timer_main, st);
         if (img) {
-            // per 64-pass chunk key the latest item's round (HIPANN_IVF_FOLLOW=1 with a HIPANN_MH_FOLLOW=1 build, A/B
-            // only: measured no better, ivf_mfma.hip); the
-            // words carry the batch number, so a stale word is ignored and the buffer is zeroed only when allocated
-            static const bool follow = [] { const char *e = std::getenv("HIPANN_IVF_FOLLOW"); return e && std::atoi(e); }();
-            int nprog = 0;
-            if (follow) {
-                nprog = (int)std::min<int64_t>(1 << 20, (sh.h_off[nlist] / 32 + nlist) / 64 + 2);
-                if (!sh.prog.p || sh.prog.bytes < sizeof(unsigned) * (size_t)nprog) {
-                    sh.prog.ensure(sizeof(unsigned) * (size_t)nprog, sh.device);
-                    HIPANN_CHECK(hipMemsetAsync(sh.prog.p, 0, sh.prog.bytes, st));
-                }
-            }
             // (int8: its query units, scales and residuals in the fp16 form's slots; L2: ‖q̂‖² of the dequantised
             // queries as the key's query term)
-            launch_ivf_scan_mfma_h(xq, nq, i8 ? sh.qi8.p : sh.hsplit.p, i8 ? sh.qs8.get<float>() : sh.hits.get<float>(),
-                                   i8 ? sh.qres8.get<float>() : sh.hres.get<float>(), sh.half_es,
-                                   cert8 ? sh.qhn2.get<float>() : qn, d,
+            launch_ivf_scan_mfma_h(nq, i8 ? sh.qi8.p : sh.hsplit.p, i8 ? sh.qs8.get<float>() : sh.hits.get<float>(),
+                                   i8 ? sh.qres8.get<float>() : sh.hres.get<float>(), cert8 ? sh.qhn2.get<float>() : qn, d,
                                    metric, i8 ? sh.codes_i8.p : sh.codes_h.p, sh.tpass_off.get<int64_t>(), sh.xnorm.get<float>(),
                                    sh.list_off.get<int64_t>(), sh.list_len.get<int>(), sh.cnt.get<int>(), sh.bucket_off.get<int>(),
                                    sh.item_off.get<int>(), sh.bucket.get<int>(), sh.slot_off.get<int>(), nlist, np, k,
-                                   max_items, qbound, sh.part_d.get<float>(), sh.part_i.get<int>(), st, true,
-                                   sub ? 1 : 0, follow ? sh.prog.get<unsigned>() : nullptr, nprog,
-                                   (unsigned)(sh.plan_batch + 1), i8 ? 1 : 0, i8 ? sh.xs8.get<float>() : nullptr,
+                                   max_items, qbound, sh.part_d.get<float>(), sh.part_i.get<int>(), st, sub ? 1 : 0,
+                                   i8 ? 1 : 0, i8 ? sh.xs8.get<float>() : nullptr,
                                    cert8 ? sh.xr8.get<float>() : nullptr, cert8 ? sh.qhn.get<float>() : nullptr);
         }
         else if (bigk)

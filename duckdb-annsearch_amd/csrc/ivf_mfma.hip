@@ -933,9 +933,9 @@ void launch_ivf_scan_mfma_bf(int np, const float *Q, int64_t nq, void *qsplit, c
 // The rows are stored once as a tiled fp16 image of x·s (s = 2^(14 − e), max|x| = f·2^e, f ∈ [½, 1):
 // every scaled element ≤ 2^14, far inside fp16's range), round to nearest even, subnormal results
 // flushed to zero; each query is scaled the same way (t = 2^(14 − e_q)) and split into two fp16 terms
-// q·t = h + l (+ ≤ 2⁻²² relative), so q·x ≈ (h + l)·x̂ / (t·s) on v_mfma_f32_16x16x32_f16 (fp16 × fp16
-// products are exact in fp32, fp32 accumulation) — or, in the one-term items that are the default since r06
-// (mh_wide_mode), h·x̂ / (t·s) with the query's own one-term residual ‖q − h/t‖ in the bound.  The other error is
+// q·t = h + l (+ ≤ 2⁻²² relative); the scan multiplies the high term only, q·x ≈ h·x̂ / (t·s) on
+// v_mfma_f32_16x16x32_f16 (fp16 × fp16 products are exact in fp32, fp32 accumulation), with the query's own
+// one-term residual ‖q − h/t‖ in the bound (the prepared image still carries both terms).  The other error is
 // the rows' own fp16 rounding, |q·(x − x̂/s)| ≤ ‖q‖·‖x − x̂/s‖, and the scan is a FILTER: it keeps the 16 best per
 // (query, list, chunk) like form 5, ivf_rerank_topk recomputes them in FAISS's direct fp32 form and
 // proves with the measured residuals (largest row residual, this query's split residual) that no
@@ -946,19 +946,6 @@ void launch_ivf_scan_mfma_bf(int np, const float *Q, int64_t nq, void *qsplit, c
 typedef _Float16 mh_f16x8 __attribute__((ext_vector_type(8)));
 #ifndef HIPANN_MH_P
 #define HIPANN_MH_P 6
-#endif
-#ifndef HIPANN_MH_FOLLOW
-// 1 (tuning builds, with HIPANN_IVF_FOLLOW=1): items start at the round another query group of their chunk last
-// published.  Measured and left out: same box, alternating (tools/gpu_r06_follow.sh, profiles/r06/
-// ivf_follow_ab_r06.txt) the SURVEY mixture's scan 5.14 / 5.25 ms against 5.23 / 5.24 (runtime off) and 5.18 / 5.20
-// (compiled out) — within the noise; the rotation's scalar registers spill to VGPR lanes for nothing
-#define HIPANN_MH_FOLLOW 0
-#endif
-#ifndef HIPANN_MH_EARLY
-#define HIPANN_MH_EARLY 1  // issue the item's first row loads before waiting for its query fill (0: fill, barrier, loads)
-#endif
-#ifndef HIPANN_MH_NT
-#define HIPANN_MH_NT 1  // non-temporal row loads (the image is read once per batch): 2.67 -> 2.59 ms at 10M x 768
 #endif
 #ifndef HIPANN_MH_INSERT
 // A step of mh_item's epilogue whose four queries each admit at most this many of the tile's 16 rows inserts them one
@@ -982,49 +969,24 @@ __device__ unsigned long long mh_stats_dev[2][2][5];
 #endif
 constexpr int MH_P = HIPANN_MH_P;  // super-steps in flight per wave: 6 × 2 row tiles × 16 B = 192 B per lane
 __host__ __device__ inline int mh_nsup(int d) { return (int)ceil_div(ceil_div(d, 32), MH_P) * MH_P; }
-// LDS dwords per query: NT terms × super-steps × 4 groups × 4 dwords, + 8 (≡ 8 mod 64: conflict-free)
-__host__ __device__ inline int mh_stride(int d, int nt = 2) { return nt * mh_nsup(d) * 16 + 8; }
-inline int mh_group(int d) {
-    const int g = (int)(MF_LDS_MAX / ((size_t)mh_stride(d) * 4)) / 16 * 16;
-    return g < 16 * MF_QTMAX ? g : 16 * MF_QTMAX;
-}
-// Wide items (lists probed by more queries than one two-term group holds): the queries' high fp16 term only, so
-// twice the queries fit the LDS (96 at d = 768) and the list's rows are streamed half as often; MFMAs per row and
-// query halve too.  The price is the query's own split residual: ‖q − h/t‖ (≈ 2⁻¹² relative) instead of
-// ‖q − (h + l)/t‖ (≈ 2⁻²³), which the scan hands to the rerank's bound for every query of a wide item.
-// On SURVEY §8(d)'s mixture (σ 0.8, nprobe 16) popular lists are probed by up to ~400 queries: 9 two-term
-// groups re-read each 2048-row chunk, 36 % of it from L2 (profiles/r06/mixture_scan_pmc_r06.txt).
-constexpr int MH_QTW = 6;  // query tiles of a wide item
+// LDS dwords per query of an item (its high fp16 term): super-steps × 4 groups × 4 dwords, + 8 (≡ 8 mod 64:
+// conflict-free)
+__host__ __device__ inline int mh_stride(int d) { return mh_nsup(d) * 16 + 8; }
+// The form's support limit dates from the items that held both query terms in LDS and is kept as it was: 16 queries
+// of a two-term image (twice the super-steps per query) fit the LDS.  That ends the form at d = 2496; one-term items
+// alone would fit up to d = 4992, and widening the predicate would move those d from form 5 to this one.
+inline bool mh_two_term_fits(int d) { return MF_LDS_MAX / ((size_t)(2 * mh_nsup(d) * 16 + 8) * 4) >= 16; }
+// Items are wide: the queries' high fp16 term only, so 96 of them fit the LDS at d = 768 and a list probed by c queries
+// streams its rows ceil(c / 96) times.  The price is the query's own split residual: ‖q − h/t‖ (≈ 2⁻¹² relative)
+// instead of ‖q − (h + l)/t‖ (≈ 2⁻²³), which the scan hands to the rerank's bound for every query it scans.
+// (Two-term items for the less probed lists were measured against this and lost, DESIGN.md.)
+constexpr int MH_QTW = 6;  // query tiles of an item
 inline int mh_group_wide(int d) {  // the image + (‖q‖², 1/(t·s)) per query
-    const int g = (int)(MF_LDS_MAX / ((size_t)mh_stride(d, 1) * 4 + 8)) / 16 * 16;
+    const int g = (int)(MF_LDS_MAX / ((size_t)mh_stride(d) * 4 + 8)) / 16 * 16;
     return g < 16 * MH_QTW ? g : 16 * MH_QTW;
 }
-// HIPANN_IVF_WIDE: 2 (default) every item one-term (narrow size 0: groups of up to 96 queries); 1 (A/B) two-term items
-// for lists probed by ≤ 48 queries, one-term above; 0 (A/B) every item two-term.  Same box, alternating
-// (tools/gpu_r06_wide.sh MODES="1 2"): the headline 382.2K / 382.0K → 395.9K / 395.9K QPS (scan 2.553 → 2.491 ms: half
-// the MFMAs and LDS reads per row and query), the mixture unchanged, 0 flagged queries in both
-inline int mh_wide_mode() {
-    static const int mode = [] { const char *e = std::getenv("HIPANN_IVF_WIDE"); return e ? std::atoi(e) : 2; }();
-    return mode;
-}
-// GEMM items (lists probed by more queries than a wide item holds): up to MG_Q queries, database rows and queries both
-// staged through LDS by LDS-DMA (mg_item below).  HIPANN_IVF_GEMM=1 (A/B) enables them; off by default: measured
-// slower, same box, alternating (tools/gpu_r06_gemm.sh, profiles/r06/ivf_gemm_items_ab_r06.txt) — the SURVEY mixture's
-// scan 5.17 → 8.32 ms at nprobe 16, intrinsic dimension 32 at nprobe 128 185K → 112K QPS.  The item streams its rows
-// with too little in flight: vector-memory loads retire in issue order, so the rows (HBM) and the query slices (L2)
-// share one lead, and four 24 KiB stages keep only 24 KiB of rows in flight per CU against the wide items' 96 KiB.
-constexpr int MG_Q = 256;
-inline bool mg_enabled() {
-    static const bool on = [] { const char *e = std::getenv("HIPANN_IVF_GEMM"); return e && std::atoi(e); }();
-    return on;
-}
-// the packed group of the plan and the scan (narrow | wide << 8 | GEMM << 16: ivf_ngroups, common.hpp)
-inline int mh_group_packed(int d) {
-    const int g = mh_group(d), w = mh_group_wide(d);
-    if (!mh_wide_mode() || w <= g || g < 16) return g;
-    const int gm = mg_enabled() && w >= 16 ? MG_Q << 16 : 0;
-    return (mh_wide_mode() == 2 ? 0 : g) | (w << 8) | gm;
-}
+// the packed group of the plan and the scan (narrow 0 | wide << 8: ivf_ngroups, common.hpp); 0 where unsupported
+inline int mh_group_packed(int d) { return mh_two_term_fits(d) ? mh_group_wide(d) << 8 : 0; }
 
 // fp32 → fp16 round to nearest even; subnormal results flushed to zero (the MFMA sees only normal
 // values or zero whatever its denormal mode, and the residuals are measured against exactly this)
@@ -1442,38 +1404,26 @@ __global__ void __launch_bounds__(256) ivf_split_queries_h(const float *__restri
     if (lane == 0) {
         its[q] = ldexpf(1.f, ok ? eits : 0);
         qres[q] = ok ? sqrtf(r2) * 1.0001f : __builtin_inff();
-        qres[nq + q] = ok ? sqrtf(r1) * 1.0001f : __builtin_inff();  // a wide item's scan copies it over qres[q]
+        qres[nq + q] = ok ? sqrtf(r1) * 1.0001f : __builtin_inff();  // the scan copies it over qres[q]
     }
 }
 
-template <int QT, bool IP, int NT, bool I8 = false>
+template <int QT, bool IP, bool I8>
 __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h, int64_t tp0,
                                         const float *__restrict__ xn, int64_t r0, int64_t r1, int nqi,
-                                        const unsigned *__restrict__ qs, int stride, const float (&qn)[QT][4],
-                                        const float (&qits)[QT][4], const unsigned (&qb)[QT][4],
+                                        const unsigned *__restrict__ qs, int stride, const unsigned (&qb)[QT][4],
                                         const float *__restrict__ qpar,
                                         const int *__restrict__ bucket, int boff, int nprobe,
                                         const int *__restrict__ slot_off, int chunk, int k, int sub, float *smem,
                                         unsigned *__restrict__ qbound, float *__restrict__ part_d,
-                                        int *__restrict__ part_i, unsigned *prog, unsigned epoch, unsigned pword,
-                                        const float *__restrict__ xs8, const float *__restrict__ xr8, int stat_part) {
+                                        int *__restrict__ part_i, const float *__restrict__ xs8,
+                                        const float *__restrict__ xr8, int stat_part) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = lane & 15, g = lane >> 4;
     const int nsup = I8 ? mi_nsup(d) : mh_nsup(d);  // (I8: 64-dim super-steps of the int8 image)
     const int npass_all = (int)ceil_div(r1 - r0, MF_PASS);
     const int npass = npass_all > wave ? (npass_all - wave + MF_WAVES - 1) / MF_WAVES : 0;
-    // Round rotation (prog): the query groups of one chunk run as consecutive items on one XCD, each streaming the
-    // whole chunk; an item that starts while another group of the chunk is under way begins at the round (8 passes)
-    // that item last published and wraps around, so both read the same rows at about the same time and the later
-    // one's reads hit the XCD's L2.  The slot's k-list does not depend on the order its rows are seen.
-    int rr0 = 0;  // (pword: the chunk's progress word, loaded by the kernel ahead of the query fill)
-    if (HIPANN_MH_FOLLOW && prog && npass > 0 && (pword >> 8) == (epoch & 0xffffffu)) rr0 = (int)(pword & 0xffu) % npass;
-    auto rot = [&](int i) {  // i < npass
-        if constexpr (!HIPANN_MH_FOLLOW) return i;
-        const int r = i + rr0;
-        return r < npass ? r : r - npass;
-    };
 
     // per query: the sorted list (key, row) and the admission gate = the key of its k-th entry (a 16-row batch
     // merges when some lane's key is ≤ the gate: a superset of the lexicographic test, the merge itself is exact)
@@ -1489,24 +1439,22 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
         }
 
     auto row_of = [&](int i, int r) -> int64_t {
-        const int64_t row = r0 + (int64_t)(wave + MF_WAVES * rot(i)) * MF_PASS + 16 * r + m;
+        const int64_t row = r0 + (int64_t)(wave + MF_WAVES * i) * MF_PASS + 16 * r + m;
         return row < r1 ? row : r1 - 1;
     };
     const int ilast = npass > 0 ? npass - 1 : 0;
     const uint4 *rp;
     int ld_i = 0, ld_s = 0;  // stream position (super-steps), wave-uniform
-    auto set_pass = [&](int i) { rp = codes_h + ((tp0 + wave + MF_WAVES * rot(i)) * nsup) * (MF_RT * 64) + lane; };
+    auto set_pass = [&](int i) { rp = codes_h + ((tp0 + wave + MF_WAVES * i) * nsup) * (MF_RT * 64) + lane; };
     // unconditional loads (past the wave's last step they re-read it): see mf_item
     auto next_load = [&](uint4 (&dst)[MF_RT]) {
         const int s = ld_i <= ilast ? ld_s : nsup - 1;
 #pragma unroll
         for (int r = 0; r < MF_RT; ++r) {
-            if (HIPANN_MH_NT) {
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(rp + (int64_t)s * (MF_RT * 64) + r * 64));
-                dst[r] = make_uint4(v[0], v[1], v[2], v[3]);
-            }
-            else dst[r] = rp[(int64_t)s * (MF_RT * 64) + r * 64];
+            // non-temporal: the image is read once per batch (2.67 -> 2.59 ms at 10M x 768)
+            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+            const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(rp + (int64_t)s * (MF_RT * 64) + r * 64));
+            dst[r] = make_uint4(v[0], v[1], v[2], v[3]);
         }
         if (++ld_s == nsup) {
             ld_s = 0;
@@ -1535,10 +1483,10 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
             }
         }
     }
-    // the item's query image (and the wide items' parameters) were written by every thread before the call: wait for
-    // them only now, with this wave's first MH_P super-steps of rows already in flight
+    // the item's query image and parameters were written by every thread before the call: wait for them only now,
+    // with this wave's first MH_P super-steps of rows already in flight
     // (an LDS-only wait and the barrier: __syncthreads()'s fence would also drain the row loads, vmcnt(0))
-    if (HIPANN_MH_EARLY) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     const unsigned *qrow[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) qrow[qt] = qs + (qt * 16 + m) * stride + 4 * g;
@@ -1572,32 +1520,23 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
 #pragma unroll
             for (int p = 0; p < MH_P; ++p) {
                 const int S = S0 + p;
-                uint4 qa[QT][NT];
+                uint4 qa[QT];
+#pragma unroll
+                for (int qt = 0; qt < QT; ++qt) qa[qt] = *reinterpret_cast<const uint4 *>(qrow[qt] + S * 16);
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
-                    for (int j = 0; j < NT; ++j) qa[qt][j] = *reinterpret_cast<const uint4 *>(qrow[qt] + (j * nsup + S) * 16);
-                // the small query term first in every accumulator chain
-#pragma unroll
-                for (int j = NT - 1; j >= 0; --j)
-#pragma unroll
-                    for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-                        for (int r = 0; r < MF_RT; ++r) {
-                            if constexpr (I8)
-                                acci[qt][r] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(mf_i32x4, qa[qt][j]),
-                                                                                   __builtin_bit_cast(mf_i32x4, ring[p][r]),
-                                                                                   acci[qt][r], 0, 0, 0);
-                            else acc[qt][r] = mh_mfma(qa[qt][j], ring[p][r], acc[qt][r]);
-                        }
+                    for (int r = 0; r < MF_RT; ++r) {
+                        if constexpr (I8)
+                            acci[qt][r] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(mf_i32x4, qa[qt]),
+                                                                               __builtin_bit_cast(mf_i32x4, ring[p][r]),
+                                                                               acci[qt][r], 0, 0, 0);
+                        else acc[qt][r] = mh_mfma(qa[qt], ring[p][r], acc[qt][r]);
+                    }
                 next_load(ring[p]);
             }
         }
-        const int64_t prow0 = r0 + (int64_t)(wave + MF_WAVES * rot(i)) * MF_PASS;
-        // publish the round this item reaches next (wave 0; a later group of the chunk starts there)
-        if (HIPANN_MH_FOLLOW && prog && wave == 0 && lane == 0)
-            __hip_atomic_store(prog, (epoch << 8) | (unsigned)((rot(i) + 1) % npass), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+        const int64_t prow0 = r0 + (int64_t)(wave + MF_WAVES * i) * MF_PASS;
 #pragma unroll
         for (int r = 0; r < MF_RT; ++r) {
             const int64_t row = prow0 + 16 * r + m;
@@ -1613,13 +1552,10 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
                         qnv = p.x;
                         qiv = p.y;
                         qrv = p.z;
-                    } else if constexpr (NT == 1) {  // wide items: (‖q‖², 1/(t·s)) from LDS (registers for 96 queries spill)
+                    } else {  // (‖q‖², 1/(t·s)) from LDS (registers for 96 queries spill)
                         const float2 p = reinterpret_cast<const float2 *>(qpar)[qt * 16 + 4 * g + v];
                         qnv = p.x;
                         qiv = p.y;
-                    } else {
-                        qnv = qn[qt][v];
-                        qiv = qits[qt][v];
                     }
                     float key;
                     // I8: the sum as a whole-vector convert (per-element extracts of a bit-cast i32 MFMA result were
@@ -1693,226 +1629,22 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
     mf_finish_item<QT>(lst, smem, nqi, bucket, boff, nprobe, slot_off, chunk, k, sub, qbound, part_d, part_i);
 }
 
-// Copy the item's queries' first NT fp16 terms (of the TS in qsplit [query][term][S][g][4 dwords]: 2, or 1 for the
-// int8 units) into LDS [query][term][S][g][4].
-template <int NT, int TS = 2>
+// Copy the item's queries' first term (of the TS in qsplit [query][term][S][g][4 dwords]: the two fp16 terms, or the
+// int8 units alone) into LDS [query][S][g][4].
+template <int TS>
 __device__ __forceinline__ void mh_fill(unsigned *qs, const uint4 *__restrict__ qsplit, int nsup, int stride, int nqi,
                                         const int *__restrict__ bucket, int boff, int nprobe) {
-    const int per_q = NT * nsup * 4;
+    const int per_q = nsup * 4;
     for (int t = threadIdx.x; t < nqi * per_q; t += MF_THREADS) {
-        const int q = t / per_q, rr = t - q * per_q;
-        const int j = rr / (nsup * 4), r2 = rr - j * (nsup * 4);
+        const int q = t / per_q, r2 = t - q * per_q;
         const int gq = bucket[boff + q] / nprobe;
-        *reinterpret_cast<uint4 *>(qs + q * stride + r2 * 4 + j * nsup * 16) = qsplit[((int64_t)gq * TS + j) * nsup * 4 + r2];
+        *reinterpret_cast<uint4 *>(qs + q * stride + r2 * 4) = qsplit[(int64_t)gq * TS * nsup * 4 + r2];
     }
 }
 
-// ---- GEMM items --------------------------------------------------------------------------------------------------
-// A list probed by more queries than a wide item holds (96 one-term queries fill the LDS) is scanned in items of up to
-// MG_Q = 256 of them, shaped as a small GEMM: per 32-dim K-step the block stages, by LDS-DMA, the step's slice of 128
-// database rows (4 passes × 2 row tiles × 1 KiB, straight from the tiled fp16 image) and of its 256 queries' high terms
-// (16 pieces of 16 queries × 64 B, gathered per lane from the batch's query image), four stages deep (three K-steps in
-// flight); wave (wr, wq) multiplies its 64 rows by its 64 queries (4 × 4 tiles of v_mfma_f32_16x16x32_f16) and keeps
-// the same 16-lane DPP-row lists as the wide items for its queries.  A 2048-row chunk is 16 block steps; the list is
-// streamed ceil(c / 256) times instead of ceil(c / 96).  LDS per K-step and wave: 4 + 4 ds_read_b128 for 16 MFMAs.
-// The stored query slice is swizzled (group g of query q at unit 4q + (g ^ F(q)), F(q) = −((q >> 2) & 3) & 3) so that
-// a wave's 16-query fragment read is conflict-free; the DMA lane that fills unit u loads the group that belongs there.
-typedef __attribute__((address_space(3))) void mg_lds_void;
-constexpr int MG_PASSES = 4;                        // 32-row passes per block step (128 rows)
-constexpr int MG_NST = 4;                           // LDS stages
-constexpr int MG_ROWU = MG_PASSES * MF_RT * 64;     // 16-B units of a stage's rows (8 KiB)
-constexpr int MG_STU = MG_ROWU + MG_Q * 4;          // + the queries' slice (16 KiB)
-constexpr size_t MG_XN = (size_t)MG_NST * MG_STU * 16;               // ‖x‖² of a block step's rows, by block parity
-constexpr size_t MG_QPAR = MG_XN + 2 * MG_PASSES * MF_PASS * sizeof(float);  // (‖q‖², 1/(t·s)) per query
-constexpr size_t MG_SCR = MG_QPAR + (size_t)MG_Q * sizeof(float2);  // the row halves' list merge
-constexpr size_t MG_LDS = MG_SCR + (size_t)4 * 4 * 4 * 64 * sizeof(uint64_t);
-static_assert(MG_LDS <= MF_LDS_MAX, "GEMM item LDS");
-static_assert(MF_WAVES == 8, "GEMM items: 2 row halves x 4 query quarters");
-
-template <bool IP>
-__device__ __forceinline__ void mg_item(int d, const uint4 *__restrict__ codes_h, int64_t tp0, const float *xn, int64_t r0,
-                                        int64_t r1, int nqi, const uint4 *__restrict__ qsplit, const float2 *qpar,
-                                        const int *__restrict__ bucket, int boff, int nprobe,
-                                        const int *__restrict__ slot_off, int chunk, int k, int sub, uint4 *stg,
-                                        uint64_t *scr, unsigned *__restrict__ qbound, float *__restrict__ part_d,
-                                        int *__restrict__ part_i) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int m = lane & 15, g = lane >> 4;
-    const int wr = wave & 1, wq = wave >> 1;  // row half (64 rows of a block step), query quarter (64 queries)
-    const int nsup = mh_nsup(d);
-    const int npass = (int)ceil_div(r1 - r0, MF_PASS);
-    const int G = (int)ceil_div(npass, MG_PASSES) * nsup;  // K-steps of the item
-    const int q0w = wq * 64;
-    const int nqt_w = nqi > q0w ? min(4, (nqi - q0w + 15) >> 4) : 0;  // the wave's tiles holding a real query
-
-    uint64_t lst[4][4];
-    unsigned thr[4][4];
-#pragma unroll
-    for (int qt = 0; qt < 4; ++qt)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int q = q0w + qt * 16 + 4 * g + v;
-            const unsigned qb = q < nqi ? __atomic_load_n(qbound + bucket[boff + q] / nprobe, __ATOMIC_RELAXED)
-                                        : 0xffffffffu;
-            lst[qt][v] = m < k ? (((uint64_t)qb << 32) | MF_PAD_ID) : MF_EMPTY;
-            thr[qt][v] = qb;
-        }
-
-    // the wave's DMA pieces per K-step: row piece (pass wave >> 1, tile wave & 1) and query pieces 2·wave, 2·wave + 1
-    const int rp_p = wave >> 1, rp_r = wave & 1;
-    const uint4 *qsrc[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int ql = 16 * (2 * wave + i) + (lane >> 2);
-        const int gq = bucket[boff + (ql < nqi ? ql : 0)] / nprobe;
-        const int gs = (lane & 3) ^ ((-(lane >> 4)) & 3);  // the source group stored at this lane's unit
-        qsrc[i] = qsplit + (int64_t)gq * 2 * nsup * 4 + gs;
-    }
-    // a block step's first K-step also brings its rows' ‖x‖² (L2): one dword DMA per wave, rows 64·(wave & 1) + lane of
-    // the step into the parity-(blk & 1) buffer (the other waves repeat the two halves: every wave issues the same ops)
-    float *xnb = reinterpret_cast<float *>(reinterpret_cast<char *>(stg) + MG_XN);
-    auto issue = [&](int gk) {  // K-step min(gk, G − 1) into stage gk % MG_NST (past the end: a stage never read)
-        const int gs = gk < G ? gk : G - 1;
-        const int blk = gs / nsup, S = gs - blk * nsup;
-        int pass = blk * MG_PASSES + rp_p;
-        pass = pass < npass ? pass : npass - 1;
-        uint4 *dst = stg + (gk % MG_NST) * MG_STU;
-        if (!IP && S == 0) {
-            const int64_t row = r0 + (int64_t)blk * (MG_PASSES * MF_PASS) + 64 * (wave & 1) + lane;
-            __builtin_amdgcn_global_load_lds((const void *)(xn + (row < r1 ? row : r1 - 1)),
-                                             (mg_lds_void *)(xnb + (blk & 1) * (MG_PASSES * MF_PASS) + 64 * (wave & 1)),
-                                             4, 0, 0);
-        }
-        __builtin_amdgcn_global_load_lds(
-            (const void *)(codes_h + ((tp0 + pass) * nsup + S) * (MF_RT * 64) + rp_r * 64 + lane),
-            (mg_lds_void *)(dst + (rp_p * MF_RT + rp_r) * 64), 16, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_global_load_lds((const void *)(qsrc[i] + S * 4),
-                                             (mg_lds_void *)(dst + MG_ROWU + (2 * wave + i) * 64), 16, 0, 0);
-    };
-    // waits (vmcnt: loads retire in issue order): at K-step gk the stage of gk must have landed; younger are the two
-    // next K-steps' DMA ops — 3 each, 4 for a block step's first K-step (L2: its ‖x‖²)
-    auto first_of_blk = [&](int x) { const int gs = x < G ? x : G - 1; return !IP && gs % nsup == 0; };
-
-    if (G > 0) {
-        issue(0);
-        issue(1);
-        issue(2);
-    }
-    mf_f32x4 acc[4][4];
-    float xr[4] = {0.f, 0.f, 0.f, 0.f};
-    int blk = 0, S = 0;
-    const int fq = (-(m >> 2)) & 3;  // the swizzle of this lane's query rows
-    for (int gk = 0; gk < G; ++gk) {
-        if (S == 0)
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt)
-#pragma unroll
-                for (int rt = 0; rt < 4; ++rt) acc[qt][rt] = mf_f32x4{0.f, 0.f, 0.f, 0.f};
-        const int younger = (int)first_of_blk(gk + 1) + (int)first_of_blk(gk + 2);  // wave-uniform
-        if (younger == 0) __builtin_amdgcn_s_waitcnt(0xF70u | 6u);
-        else if (younger == 1) __builtin_amdgcn_s_waitcnt(0xF70u | 7u);
-        else __builtin_amdgcn_s_waitcnt(0xF70u | 8u);
-        __builtin_amdgcn_s_barrier();  // every wave's stage gk landed; every wave done reading stage gk − 1
-        asm volatile("" ::: "memory");
-        issue(gk + 3);
-        const uint4 *sb = stg + (gk % MG_NST) * MG_STU;
-        uint4 rb[4], qa[4];
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt) rb[rt] = sb[((2 * wr + (rt >> 1)) * MF_RT + (rt & 1)) * 64 + lane];
-#pragma unroll
-        for (int qt = 0; qt < 4; ++qt)
-            if (qt < nqt_w) qa[qt] = sb[MG_ROWU + (q0w + qt * 16 + m) * 4 + (g ^ fq)];
-#pragma unroll
-        for (int qt = 0; qt < 4; ++qt)
-            if (qt < nqt_w)
-#pragma unroll
-                for (int rt = 0; rt < 4; ++rt) acc[qt][rt] = mh_mfma(qa[qt], rb[rt], acc[qt][rt]);
-        if (++S == nsup) {
-            // epilogue of block step blk: the wave's 64 rows × its queries into the lists
-            if (!IP)
-#pragma unroll
-                for (int rt = 0; rt < 4; ++rt) xr[rt] = xnb[(blk & 1) * (MG_PASSES * MF_PASS) + wr * 64 + rt * 16 + m];
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt) {
-                const int64_t row = r0 + (int64_t)blk * (MG_PASSES * MF_PASS) + wr * 64 + rt * 16 + m;
-                const bool rok = row < r1;
-                const unsigned rid = rok ? (unsigned)row : MF_PAD_ID;
-#pragma unroll
-                for (int qt = 0; qt < 4; ++qt) {
-                    if (qt >= nqt_w) continue;  // wave-uniform
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int q = q0w + qt * 16 + 4 * g + v;
-                        const float2 p = qpar[q];
-                        float key;
-                        if (IP) {
-                            key = -acc[qt][rt][v] * p.y;
-                        } else {
-                            key = fmaf(-2.f * p.y, acc[qt][rt][v], p.x + xr[rt]);
-                            key = key < 0.f ? 0.f : key;
-                        }
-                        const bool ok = rok && q < nqi;
-                        const unsigned ks = mf_sortable(key);
-                        uint64_t cp = ok ? (((uint64_t)ks << 32) | rid) : MF_EMPTY;
-                        if (__ballot(ok && ks <= thr[qt][v])) {
-                            row_sort16(cp, m);
-                            row_merge16(lst[qt][v], cp, m);
-                            thr[qt][v] = row_kth_key(lst[qt][v], k - 1, g);
-                        }
-                    }
-                }
-            }
-            S = 0;
-            ++blk;
-        }
-    }
-    // drain the DMA issued past the end before the LDS is reused or released
-    __builtin_amdgcn_s_waitcnt(0xF70u);
-    __syncthreads();
-    if (!sub) {  // the two row halves' lists of each query quarter: wr = 1 hands its lists to wr = 0
-        uint64_t *sw = scr + (size_t)wq * 4 * 4 * 64;
-        if (wr == 1)
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) sw[(qt * 4 + v) * 64 + lane] = lst[qt][v];
-        __syncthreads();
-        if (wr == 0)
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) row_merge16(lst[qt][v], sw[(qt * 4 + v) * 64 + lane], m);
-    }
-    if ((sub || wr == 0) && m < k) {
-#pragma unroll
-        for (int qt = 0; qt < 4; ++qt)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int q = q0w + qt * 16 + 4 * g + v;
-                if (q >= nqi) continue;
-                const int pr = bucket[boff + q];
-                const int64_t slot = (int64_t)slot_off[pr] + chunk;
-                const uint64_t e = lst[qt][v];
-                const unsigned id = (unsigned)e;
-                const bool real = e != MF_EMPTY && id != MF_PAD_ID;
-                const int64_t off = (sub ? slot * MF_WAVES + wr : slot) * k + m;
-                part_d[off] = real ? mf_unsortable((unsigned)(e >> 32)) : __builtin_inff();
-                part_i[off] = real ? (int)id : (int)MF_PAD_ID;
-                if (m == k - 1 && real) atomicMin(qbound + pr / nprobe, (unsigned)(e >> 32));
-                if (sub && wr == 0)  // the slot's other sub-lists (MF_WAVES per slot; two row halves here) stay empty
-                    for (int s2 = 2; s2 < MF_WAVES; ++s2) {
-                        part_d[(slot * MF_WAVES + s2) * k + m] = __builtin_inff();
-                        part_i[(slot * MF_WAVES + s2) * k + m] = (int)MF_PAD_ID;
-                    }
-            }
-    }
-}
-
-// I8: the int8 image (every item one-term: units in qsplit, s_q in its, s_x in xs8; no residual copy; L2: qnorm is
-// ‖q̂‖² of the dequantised queries, qhn their ‖q̂‖ and xr8 the rows' residuals — the lower-bound key of the header)
+// Every item scans one query term.  I8: the int8 image (units in qsplit, s_q in its, s_x in xs8; no residual copy; L2:
+// qnorm is ‖q̂‖² of the dequantised queries, qhn their ‖q̂‖ and xr8 the rows' residuals — the lower-bound key of the
+// header)
 template <bool IP, bool I8>
 __global__ void __launch_bounds__(MF_THREADS, MF_WAVES / 4)
 ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnorm, const float *__restrict__ its, int d,
@@ -1920,9 +1652,8 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
                 const int64_t *__restrict__ list_off, const int *__restrict__ list_len, const int *__restrict__ cnt, const int *__restrict__ bucket_off,
                 const int *__restrict__ item_off, const int *__restrict__ bucket, const int *__restrict__ slot_off,
                 int nlist, int nprobe, int group, int k, int sub, unsigned *__restrict__ qbound, float *__restrict__ part_d,
-                int *__restrict__ part_i, float *__restrict__ qres, int nq, int remap, unsigned *__restrict__ prog,
-                int nprog, unsigned epoch, const float *__restrict__ xs8, const float *__restrict__ xr8,
-                const float *__restrict__ qhn) {
+                int *__restrict__ part_i, float *__restrict__ qres, int nq, int remap, const float *__restrict__ xs8,
+                const float *__restrict__ xr8, const float *__restrict__ qhn) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int total = item_off[nlist];
     if ((int)blockIdx.x >= total) return;
@@ -1935,8 +1666,6 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
     const int l = lo;
     const int64_t lr0 = list_off[l], lr1 = lr0 + list_len[l];
     const int c = cnt[l];
-    const int cls = ivf_list_class(c, group);  // block-uniform
-    const bool wide = I8 || cls == 1;
     const int ng = ivf_ngroups(c, group);
     const int rem = item - item_off[l];
     const int chunk = rem / ng, grp = rem - chunk * ng;
@@ -1947,80 +1676,49 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
     const int boff = bucket_off[l] + q_begin;
     const int nqt = (nqi + 15) >> 4;
 
-    if (!I8 && cls == 2) {
-        uint4 *stg = reinterpret_cast<uint4 *>(smem);
-        float2 *gpar = reinterpret_cast<float2 *>(reinterpret_cast<char *>(smem) + MG_QPAR);
-        for (int t = threadIdx.x; t < nqi; t += MF_THREADS) {
-            const int qi = bucket[boff + t] / nprobe;
-            gpar[t] = make_float2(IP ? 0.f : qnorm[qi], its[qi]);
-            qres[qi] = qres[nq + qi];  // one-term scan keys: the rerank's bound takes the one-term residual
-        }
-        __syncthreads();
-        const int64_t tpg = tpass_off[l] + (int64_t)chunk * (MF_CH / MF_PASS);
-        mg_item<IP>(d, codes_h, tpg, xn, r0, r1, nqi, qsplit, gpar, bucket, boff, nprobe, slot_off, chunk, k, sub, stg,
-                    reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(smem) + MG_SCR), qbound, part_d, part_i);
-        return;
-    }
-    // the chunk's progress word, loaded before the query fill so that its latency hides behind it
     const int64_t tp0 = tpass_off[l] + (int64_t)chunk * (MF_CH / MF_PASS);
-    unsigned *pw = HIPANN_MH_FOLLOW && prog && nprog > 0 ? prog + (int)((tp0 >> 6) % nprog) : nullptr;
-    const unsigned pword = pw ? (unsigned)__builtin_amdgcn_readfirstlane(
-                                    (int)__hip_atomic_load(pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                              : 0u;
     unsigned *qs = reinterpret_cast<unsigned *>(smem);
     const int nsup = I8 ? mi_nsup(d) : mh_nsup(d);
-    const int stride = I8 ? mi_nsup(d) * 16 + 8 : mh_stride(d, wide ? 1 : 2);
-    // wide items: (‖q‖², 1/(t·s)) after the image (stride: a multiple of 8 dwords, so 16-byte aligned); I8: four floats
+    const int stride = I8 ? mi_nsup(d) * 16 + 8 : mh_stride(d);
+    // (‖q‖², 1/(t·s)) after the image (stride: a multiple of 8 dwords, so 16-byte aligned); I8: four floats
     float *qpar = reinterpret_cast<float *>(qs + nqi * stride);
-    if (wide) {
-        mh_fill<1, I8 ? 1 : 2>(qs, qsplit, nsup, stride, nqi, bucket, boff, nprobe);
-        for (int t = threadIdx.x; t < nqi; t += MF_THREADS) {
-            const int qi = bucket[boff + t] / nprobe;
-            if constexpr (I8)
-                reinterpret_cast<float4 *>(qpar)[t] =
-                    make_float4(IP ? 0.f : qnorm[qi], its[qi], IP ? 0.f : 2.f * qhn[qi], 0.f);
-            else reinterpret_cast<float2 *>(qpar)[t] = make_float2(IP ? 0.f : qnorm[qi], its[qi]);
-            // these queries' scan keys miss the low term: the rerank bounds them with the one-term residual (every
-            // item of the query's wide lists writes the same value)
-            if (!I8) qres[qi] = qres[nq + qi];
-        }
-    } else if constexpr (!I8) {
-        mh_fill<2>(qs, qsplit, nsup, stride, nqi, bucket, boff, nprobe);
+    mh_fill<I8 ? 1 : 2>(qs, qsplit, nsup, stride, nqi, bucket, boff, nprobe);
+    for (int t = threadIdx.x; t < nqi; t += MF_THREADS) {
+        const int qi = bucket[boff + t] / nprobe;
+        if constexpr (I8)
+            reinterpret_cast<float4 *>(qpar)[t] =
+                make_float4(IP ? 0.f : qnorm[qi], its[qi], IP ? 0.f : 2.f * qhn[qi], 0.f);
+        else reinterpret_cast<float2 *>(qpar)[t] = make_float2(IP ? 0.f : qnorm[qi], its[qi]);
+        // the fp16 scan keys miss the low term: the rerank bounds them with the one-term residual (every item of
+        // the query writes the same value)
+        if (!I8) qres[qi] = qres[nq + qi];
     }
-    if (!HIPANN_MH_EARLY) __syncthreads();  // (early: mh_item waits for the fill after issuing its first row loads)
+    // (no barrier here: mh_item waits for the fill after issuing its first row loads)
 
     const int lane = threadIdx.x & 63, g = lane >> 4;
     const int stat_part = (int64_t)blockIdx.x * 5 < (int64_t)total ? 0 : 1;  // (HIPANN_MH_STATS)
-#define MH_ARGS d, codes_h, tp0, xn, r0, r1, nqi, qs, stride, qn, qi_s, qb, qpar, bucket, boff, nprobe, slot_off, chunk, k, sub, smem, \
-                qbound, part_d, part_i, pw, epoch, pword, xs8, xr8, stat_part
-#define MH_QN(QTV)                                                                                          \
-    float qn[QTV][4], qi_s[QTV][4];                                                                         \
-    unsigned qb[QTV][4];                                                                                    \
-    _Pragma("unroll") for (int qt = 0; qt < QTV; ++qt) _Pragma("unroll") for (int v = 0; v < 4; ++v) {      \
-        const int q = qt * 16 + 4 * g + v;                                                                  \
-        const int qi = q < nqi ? bucket[boff + q] / nprobe : 0;                                             \
-        qn[qt][v] = (!IP && !wide && q < nqi) ? qnorm[qi] : 0.f;                                            \
-        qi_s[qt][v] = !wide && q < nqi ? its[qi] : 0.f;                                                     \
-        qb[qt][v] = q < nqi ? __atomic_load_n(qbound + qi, __ATOMIC_RELAXED) : 0xffffffffu;                 \
+#define MH_CASE(QTV)                                                                                        \
+    {                                                                                                       \
+        unsigned qb[QTV][4];                                                                                \
+        _Pragma("unroll") for (int qt = 0; qt < QTV; ++qt) _Pragma("unroll") for (int v = 0; v < 4; ++v) {  \
+            const int q = qt * 16 + 4 * g + v;                                                              \
+            const int qi = q < nqi ? bucket[boff + q] / nprobe : 0;                                         \
+            qb[qt][v] = q < nqi ? __atomic_load_n(qbound + qi, __ATOMIC_RELAXED) : 0xffffffffu;             \
+        }                                                                                                   \
+        mh_item<QTV, IP, I8>(d, codes_h, tp0, xn, r0, r1, nqi, qs, stride, qb, qpar, bucket, boff, nprobe, slot_off, \
+                             chunk, k, sub, smem, qbound, part_d, part_i, xs8, xr8, stat_part);             \
     }
-#define MH_CASE(QTV, NTV) { MH_QN(QTV) mh_item<QTV, IP, NTV, I8>(MH_ARGS); }
-    if (wide) {
-        // nqi > narrow / 2 (a wide list has more than one narrow group of queries, split evenly) unless every list
-        // is wide (narrow 0, A/B)
-        if (nqt <= 1) MH_CASE(1, 1)
-        else if (nqt == 2) MH_CASE(2, 1)
-        else if (nqt == 3) MH_CASE(3, 1)
-        else if (nqt == 4) MH_CASE(4, 1)
-        else if (nqt == 5) MH_CASE(5, 1)
-        else MH_CASE(6, 1)
-    } else if constexpr (!I8) {
-        if (nqt <= 1) MH_CASE(1, 2)
-        else if (nqt == 2) MH_CASE(2, 2)
-        else MH_CASE(3, 2)
+    // (a switch: compiled as an if-else chain over nqt the kernel spills about 150 more scalar registers to
+    // vector-register lanes and takes one more VGPR, profiles/ivf_scan_prune/resource_usage.txt)
+    switch (nqt) {
+    case 0: case 1: MH_CASE(1) break;
+    case 2: MH_CASE(2) break;
+    case 3: MH_CASE(3) break;
+    case 4: MH_CASE(4) break;
+    case 5: MH_CASE(5) break;
+    default: MH_CASE(6) break;
     }
 #undef MH_CASE
-#undef MH_QN
-#undef MH_ARGS
 }
 
 // HIPANN_MH_STATS builds: print the epilogue's counters (and clear them); every other build: nothing
@@ -2042,8 +1740,8 @@ int ivf_mfma_h_group(int d) { return mh_group_packed(d); }
 int ivf_scan_sublists() { return MF_WAVES; }
 int64_t ivf_half_pass_bytes(int d) { return (int64_t)mh_nsup(d) * MF_RT * 64 * 16; }
 int64_t ivf_half_qsplit_bytes(int64_t nq, int d) { return nq * 2 * mh_nsup(d) * 64; }
-bool ivf_mfma_h_supported(int d, int k) { return d >= 1 && k >= 1 && k <= MF_KMAX && mh_group(d) >= 16; }
-// int8 image: every item one-term, up to 96 queries (MH_QTW tiles) that fit the LDS with their four parameters
+bool ivf_mfma_h_supported(int d, int k) { return d >= 1 && k >= 1 && k <= MF_KMAX && mh_two_term_fits(d); }
+// int8 image: up to 96 queries (MH_QTW tiles) that fit the LDS with their four parameters
 // (‖q̂‖², s_q, 2‖q̂‖, −: 16 B per query, 1.5 KiB for 96)
 int ivf_mfma_i8_group(int d) {
     const int g = (int)(MF_LDS_MAX / ((size_t)(mi_nsup(d) * 16 + 8) * 4 + 16)) / 16 * 16;
@@ -2122,31 +1820,26 @@ void launch_ivf_split_queries_h(const float *Q, int64_t nq, int d, int es, void 
     HIPANN_CHECK(hipGetLastError());
 }
 
-void launch_ivf_scan_mfma_h(const float *Q, int64_t nq, void *qsplit, float *its, float *qres, int es, const float *qn,
-                            int d, int metric, const void *codes_h, const int64_t *tpass_off, const float *xn,
+// The batch's queries are already prepared (launch_ivf_split_queries_h / launch_ivf_split_queries_i8).
+void launch_ivf_scan_mfma_h(int64_t nq, const void *qsplit, const float *its, float *qres, const float *qn, int d,
+                            int metric, const void *codes_h, const int64_t *tpass_off, const float *xn,
                             const int64_t *list_off, const int *list_len, const int *cnt, const int *bucket_off,
                             const int *item_off, const int *bucket, const int *slot_off, int nlist, int nprobe, int k,
-                            int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, bool split_done,
-                            int sub, unsigned *prog, int nprog, unsigned epoch, int i8mode, const float *xs8,
-                            const float *xr8, const float *qhn) {
+                            int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub, int i8mode,
+                            const float *xs8, const float *xr8, const float *qhn) {
     if (max_items <= 0 || nq <= 0) return;
     HIPANN_REQUIRE(max_items < (int64_t)0x7fffffff, "too many IVF work items");
     HIPANN_REQUIRE(qsplit && its && qres && codes_h, "fp16 IVF scan: missing buffers");
-    HIPANN_REQUIRE(i8mode ? ivf_mfma_i8_supported(d, k) && xs8 && split_done : ivf_mfma_h_supported(d, k),
+    HIPANN_REQUIRE(i8mode ? ivf_mfma_i8_supported(d, k) && xs8 : ivf_mfma_h_supported(d, k),
                    "fp16 / int8 IVF scan needs k <= 16 (int8: scales and prepared queries)");
     HIPANN_REQUIRE(metric == kIP || (qn && xn), "decomposed L2 scan needs query and row norms");
     HIPANN_REQUIRE(!i8mode || metric == kIP || (xr8 && qhn), "int8 L2 scan needs the rows' residuals and the queries' norms");
-    const int nsup = mh_nsup(d);
-    uint4 *qs = static_cast<uint4 *>(qsplit);
-    if (!split_done)
-        hipLaunchKernelGGL(ivf_split_queries_h, dim3((unsigned)ceil_div(nq, 4)), dim3(256), 0, st, Q, nq, d, nsup, es, qs,
-                           its, qres, nullptr, (d % 4 == 0) && ((uintptr_t)Q % 16 == 0));
+    const uint4 *qs = static_cast<const uint4 *>(qsplit);
     const int group = i8mode ? ivf_mfma_i8_group(d) : mh_group_packed(d);
-    const int gw = ivf_group_wide(group);
-    const size_t merge = (size_t)(MF_WAVES / 2) * (gw ? MH_QTW : MF_QTMAX) * 4 * 64 * sizeof(float2);
-    const size_t wstride = i8mode ? (size_t)(mi_nsup(d) * 16 + 8) * 4 : (size_t)mh_stride(d, 1) * 4;
-    const size_t smem = std::max({(size_t)ivf_group_narrow(group) * mh_stride(d) * 4, (size_t)gw * (wstride + (i8mode ? 16 : 8)), merge,
-                                  ivf_group_gemm(group) ? MG_LDS : (size_t)0});
+    // LDS: the group's query image and parameters, or the end-of-item merge scratch
+    const size_t merge = (size_t)(MF_WAVES / 2) * MH_QTW * 4 * 64 * sizeof(float2);
+    const size_t per_q = i8mode ? (size_t)(mi_nsup(d) * 16 + 8) * 4 + 16 : (size_t)mh_stride(d) * 4 + 8;
+    const size_t smem = std::max((size_t)ivf_group_wide(group) * per_q, merge);
     HIPANN_REQUIRE(smem <= MF_LDS_MAX, "fp16 IVF scan: LDS image too large");
     HIPANN_REQUIRE(nq < (int64_t)0x7fffffff, "fp16 IVF scan: batch too large");
     dim3 grid((unsigned)max_items), block(MF_THREADS);
@@ -2155,7 +1848,7 @@ void launch_ivf_scan_mfma_h(const float *Q, int64_t nq, void *qsplit, float *its
     // contiguous runs per XCD
     static const int remap = [] { const char *e = std::getenv("HIPANN_IVF_REMAP"); return !e || std::atoi(e) ? 1 : 0; }();
 #define MH_LAUNCH_ARGS qs, qn, its, d, ch, tpass_off, xn, list_off, list_len, cnt, bucket_off, item_off, bucket, slot_off, nlist, nprobe, \
-                       group, k, sub, qbound, pd, pi, qres, (int)nq, remap, prog, nprog, epoch, xs8, xr8, qhn
+                       group, k, sub, qbound, pd, pi, qres, (int)nq, remap, xs8, xr8, qhn
     if (i8mode) {
         if (metric == kIP) hipLaunchKernelGGL((ivf_scan_mfma_h<true, true>), grid, block, smem, st, MH_LAUNCH_ARGS);
         else hipLaunchKernelGGL((ivf_scan_mfma_h<false, true>), grid, block, smem, st, MH_LAUNCH_ARGS);

@@ -441,7 +441,6 @@ struct IvfShard {
     uint64_t fb_seq = 0, fb_seen = 0;
     bool count_only = false;
     DevBuf probe_D, probe_I;
-    DevBuf prog;  // fp16 scan: per 64-pass chunk key, the latest item's position (rounds) and the batch it belongs to
     // an append's staging (hipann_ivf_add): the new rows grouped by list, labels, physical destinations, norms,
     // the tiled passes they touch, and the new rows' maxima (‖x‖², |x|, fp16 residual²)
     DevBuf app_rows, app_norm, app_assign, app_up, app_stat;
@@ -570,13 +569,14 @@ void launch_ivf_tile_half(const float *codes, const int64_t *list_off, const int
                           int nlist, int64_t total_pass, int d, float scale, void *dst, hipStream_t st,
                           const int64_t *pass_ids = nullptr);
 void launch_ivf_half_residual(const float *codes, int64_t n, int d, float scale, unsigned *out, hipStream_t st);
-void launch_ivf_scan_mfma_h(const float *Q, int64_t nq, void *qsplit, float *its, float *qres, int es, const float *qn,
-                            int d, int metric, const void *codes_h, const int64_t *tpass_off, const float *xn,
-                            const int64_t *list_off, const int *list_len, const int *cnt, const int *bucket_off, const int *item_off,
-                            const int *bucket, const int *slot_off, int nlist, int nprobe, int k, int64_t max_items,
-                            unsigned *qbound, float *pd, int *pi, hipStream_t st, bool split_done = false,
-                            int sub = 0, unsigned *prog = nullptr, int nprog = 0, unsigned epoch = 0, int i8mode = 0,
-                            const float *xs8 = nullptr, const float *xr8 = nullptr, const float *qhn = nullptr);
+// (the batch's queries already prepared: launch_ivf_split_queries_h, or launch_ivf_split_queries_i8 with i8mode)
+void launch_ivf_scan_mfma_h(int64_t nq, const void *qsplit, const float *its, float *qres, const float *qn, int d,
+                            int metric, const void *codes_h, const int64_t *tpass_off, const float *xn,
+                            const int64_t *list_off, const int *list_len, const int *cnt, const int *bucket_off,
+                            const int *item_off, const int *bucket, const int *slot_off, int nlist, int nprobe, int k,
+                            int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub = 0,
+                            int i8mode = 0, const float *xs8 = nullptr, const float *xr8 = nullptr,
+                            const float *qhn = nullptr);
 // int8 image (kFormI8Exact): packed group (wide items only), pass / query-image bytes, support, the tiling (one scale
 // and one residual per row into xs8 / xr8; *nonfin != 0 afterwards: a non-finite row), the batch's int8 queries (units,
 // scales, residuals, ‖q̂‖² and ‖q̂‖ of the dequantised queries)

@@ -221,10 +221,12 @@ def scan_pairs(index, probes: np.ndarray) -> int:
 
 
 def half_scan_groups(d: int, mode: int = 2, gemm: bool = False) -> tuple:
-    """(narrow, wide, gemm) query-group sizes of the fp16 form's scan (ivf_mfma.hip mh_group / mh_group_wide /
-    mh_group_packed: the queries' LDS image, two fp16 terms or the high term only, in 160 KiB; GEMM items of 256) for
-    HIPANN_IVF_WIDE = mode (2 default: every list at least wide, narrow 0; 1: wide above the narrow size; 0: no wide
-    items) and HIPANN_IVF_GEMM (gemm)."""
+    """(narrow, wide, gemm) query-group sizes of the fp16 form's scan.  The library only ever runs mode 2 without GEMM
+    items: (0, wide, 0), the queries' high fp16 term in 160 KiB of LDS (ivf_mfma.hip mh_group_wide / mh_group_packed;
+    `g`, the two-term image's group, survives there only as the form's support limit, mh_two_term_fits).  The other
+    modes (1: two-term items up to the narrow size, wide above; 0: two-term items only) and the GEMM items of 256
+    queries model scan variants that were measured and removed; they are kept for callers that still
+    pass them."""
     nsup = -(-(-(-d // 32)) // 6) * 6
     g = min(48, (163840 // ((2 * nsup * 16 + 8) * 4)) // 16 * 16)
     w = min(96, (163840 // ((nsup * 16 + 8) * 4 + 8)) // 16 * 16)

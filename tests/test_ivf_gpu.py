@@ -115,11 +115,9 @@ def test_ivf_mfma_query_tiles(gpu, oracle, nq, d, metric, form):
 def test_ivf_half_wide_items(gpu, oracle, nq, d, metric, k, form):
     """The fp16 form's one-term items (ivf_mfma.hip): every list's queries enter on their high fp16 term, in wide
     items of up to 96 queries (48 at d = 1536): one item of 17-96 queries (2-6 query tiles), two of 48/49 or 128/129,
-    three or more, ragged last query tiles; k = 20 takes the sub-list slots.  Run with HIPANN_IVF_GEMM=1 (A/B,
-    tools/gpu_r06_gemm.sh) a list probed by more than 96 queries takes GEMM items of up to 256 instead (one of 97-256
-    queries, two of 128/129, three of 171 at 513).  The rerank bounds those queries with their one-term residual, so
-    the ids still equal the oracle's.  Form 7 (the int8 image) runs the same items over 64-dim super-steps (96 queries
-    at d = 1536 too) with the sub-lists and 64 reranked candidates at every k."""
+    three or more, ragged last query tiles; k = 20 takes the sub-list slots.  The rerank bounds those queries with
+    their one-term residual, so the ids still equal the oracle's.  Form 7 (the int8 image) runs the same items over
+    64-dim super-steps (96 queries at d = 1536 too) with the sub-lists and 64 reranked candidates at every k."""
     xb, xq = faiss_metal_case(4500 if d < 1000 else 2500, nq, d)
     cen = np.ascontiguousarray(xb[:2])
     off = np.array([0, 2100, len(xb)], np.int64)  # two lists, both probed by every query: 2 row chunks, ragged
@@ -131,6 +129,31 @@ def test_ivf_half_wide_items(gpu, oracle, nq, d, metric, k, form):
     Do, Io, Po = oracle.ivf_search(cen, off, ids, xb, xq, k, 2, metric)
     assert np.array_equal(ix.last_probes(nq), Po)
     check_topk_parity(xb, xq, D, I, Do, Io, metric, tau=TAU)
+
+
+@pytest.mark.parametrize("d", [2496, 2500])
+@pytest.mark.parametrize("form", [6, 7])
+def test_ivf_half_largest_dim(gpu, oracle, d, form):
+    """The fp16 form's last supported dimension, where its group arithmetic and LDS size sit at their limit: at
+    d = 2496 (78 super-steps) 32 one-term queries and their parameters fill 157.25 of the 160 KiB, so the 40 queries
+    of the one list run as two items of 20 (two query tiles each).  d = 2500 rounds up to 84 super-steps, past the
+    form's support limit (16 queries of a two-term image in LDS), so a request for form 6 must be answered by
+    another form.  Form 7 (the int8 image, 64-dim super-steps) holds all 40 queries in one item at both."""
+    nq, k = 40, 10
+    xb, xq = faiss_metal_case(600, nq, d)
+    cen = np.ascontiguousarray(xb[:1])
+    off = np.array([0, len(xb)], np.int64)
+    ids = np.arange(len(xb), dtype=np.int64)
+    ix = gpu.HipIndexIVFFlat(cen, off, ids, xb, 1, 0)
+    ix.form = form
+    D, I = ix.search(xq, k)
+    if d == 2496:
+        assert ix.last_search_path()["form"] == form
+    elif form == 6:
+        assert ix.last_search_path()["form"] != 6
+    Do, Io, Po = oracle.ivf_search(cen, off, ids, xb, xq, k, 1, 0)
+    assert np.array_equal(ix.last_probes(nq), Po)
+    check_topk_parity(xb, xq, D, I, Do, Io, 0, tau=TAU)
 
 
 def test_ivf_full_probe_equals_flat(gpu, oracle):
