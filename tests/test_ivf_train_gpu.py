@@ -5,7 +5,11 @@ train_sample rows, then faiss_idx->train).  hipann_ivf_train runs that k-means o
 from splitmix64(seed), so its result is pinned to the oracle's restatement (oracle_kmeans_train), whose outputs
 on the committed fixtures (tests/golden/ivf_train.npz, make_golden.py) the GPU must reproduce: the same
 centroids — every cluster sum is fp64 in row order on both sides — and the same cluster sizes, unless an
-assignment tie between two centroids resolved differently (none on these fixtures)."""
+assignment tie between two centroids resolved differently (none on these fixtures).
+
+The fixtures are all 6000 × 48 rows.  Other shapes — d from 1 to 768, nlist 1 to 1024, more than 65536 training
+rows, real ties, empty-cluster splits at odd d, the device entry on a caller's stream, the argument errors — are in
+tests/test_ivf_train_shapes_gpu.py, computed live against tests/_kmeans_ref.py and the oracle."""
 from __future__ import annotations
 
 import sys
