@@ -92,6 +92,32 @@ extern "C" {
         err_buf: *mut core::ffi::c_char,
         err_len: i32,
     ) -> i32;
+    fn diskann_hip_build_graph(
+        db: *mut core::ffi::c_void,
+        r: i32,
+        l_build: i32,
+        alpha: f32,
+        metric: i32,
+        entry_point: u32,
+        batch_max: i32,
+        adjacency_out: *mut u32,
+        stats: *mut i64,
+        err_buf: *mut core::ffi::c_char,
+        err_len: i32,
+    ) -> i32;
+    fn diskann_hip_robust_prune(
+        db: *mut core::ffi::c_void,
+        targets: *const u32,
+        m: i32,
+        pools: *const u32,
+        pool_cap: i32,
+        r: i32,
+        alpha: f32,
+        metric: i32,
+        out: *mut u32,
+        err_buf: *mut core::ffi::c_char,
+        err_len: i32,
+    ) -> i32;
 }
 
 /// Cached availability: -1 = unchecked, 0 = unavailable, 1 = available (metal_ffi.rs:33-34).
@@ -380,6 +406,79 @@ impl HipDiskDb {
             return None;
         }
         Some(collect_results(&ids, &dists, nq, k))
+    }
+
+    /// Build the DiskANN graph of this fp32 DB on the GPU (prefix-doubling batches searched against the
+    /// frozen graph, RobustPrune, back-edge update) — the device counterpart of the per-row insert loop of
+    /// index_manager.rs:262-313.  L2 only.  Returns the n × max_degree adjacency (u32::MAX padding), ready for
+    /// file_format.rs, and the eight build counters of hip_diskann_bridge.h; the graph stays registered for
+    /// search_batch_resident.  None ⇒ the shape is refused or the device failed; the caller builds on the CPU.
+    pub fn build_graph(
+        &self,
+        max_degree: usize,
+        l_build: usize,
+        alpha: f32,
+        entry_point: u32,
+        batch_max: usize,
+    ) -> Option<(Vec<u32>, [i64; 8])> {
+        if max_degree == 0 || max_degree > 64 || l_build == 0 || l_build > 256 || batch_max == 0 {
+            return None;
+        }
+        let words = self.n.checked_mul(max_degree)?;
+        let mut adjacency = vec![u32::MAX; words];
+        let mut stats = [0i64; 8];
+        let mut err = [0 as core::ffi::c_char; 256];
+        let ret = unsafe {
+            diskann_hip_build_graph(
+                self.h,
+                max_degree as i32,
+                l_build as i32,
+                alpha,
+                0,
+                entry_point,
+                batch_max.min(i32::MAX as usize) as i32,
+                adjacency.as_mut_ptr(),
+                stats.as_mut_ptr(),
+                err.as_mut_ptr(),
+                err.len() as i32,
+            )
+        };
+        if ret != 0 {
+            return None;
+        }
+        Some((adjacency, stats))
+    }
+
+    /// prune() of DESIGN §6 for `targets.len()` nodes over `pools` (targets.len() × pool_cap ids, u32::MAX padding).
+    /// Returns targets.len() × max_degree ids, u32::MAX-padded.
+    pub fn robust_prune(&self, targets: &[u32], pools: &[u32], pool_cap: usize, max_degree: usize, alpha: f32) -> Option<Vec<u32>> {
+        if max_degree == 0 || max_degree > 64 || pool_cap == 0 || pool_cap > i32::MAX as usize || targets.len() > i32::MAX as usize {
+            return None;
+        }
+        if targets.len().checked_mul(pool_cap) != Some(pools.len()) {
+            return None;
+        }
+        let mut out = vec![u32::MAX; targets.len() * max_degree];
+        let mut err = [0 as core::ffi::c_char; 256];
+        let ret = unsafe {
+            diskann_hip_robust_prune(
+                self.h,
+                targets.as_ptr(),
+                targets.len() as i32,
+                pools.as_ptr(),
+                pool_cap as i32,
+                max_degree as i32,
+                alpha,
+                0,
+                out.as_mut_ptr(),
+                err.as_mut_ptr(),
+                err.len() as i32,
+            )
+        };
+        if ret != 0 {
+            return None;
+        }
+        Some(out)
     }
 }
 

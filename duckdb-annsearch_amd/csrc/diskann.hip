@@ -41,6 +41,17 @@ void launch_diskann_bfs(const float *Q, int nq, int d, int fmt, const void *data
                         const uint32_t *adj, const uint32_t *dupw, int R, uint32_t N, const uint32_t *eps, int n_ep, int k, int L,
                         int metric, uint32_t *visited, int64_t vwords, int64_t *out_ids, float *out_d, int *flags,
                         unsigned long long *stats, hipStream_t st);
+// diskann_build.hip
+int vamana_prune_blocks(int64_t m);
+size_t vamana_gram_bytes(int blocks);
+void launch_vamana_prune(const float *x, int d, uint32_t n, const uint32_t *targets, int m, const int *m_ptr,
+                         const uint32_t *pool32, const int64_t *pool64, const float *pool_d, const int *pool_beg,
+                         const int *pool_len, int pool_cap, int R, float alpha, uint32_t *out, bool out_by_target,
+                         float *gram, int blocks, unsigned long long *counters, hipStream_t st);
+void launch_vamana_fill_targets(uint32_t *tg, int b, uint32_t o0, uint32_t ep, hipStream_t st);
+void launch_vamana_backedges(uint32_t *adj, int R, const uint32_t *tg, int b, int *cnt, int *slot, uint32_t *touched,
+                             int *off, int *fill, uint32_t *src, int *ctr, uint32_t *pool, uint32_t *ptgt, int *pbeg,
+                             int *plen, hipStream_t st);
 
 __device__ __forceinline__ float wave_sum(float s) {
 #pragma unroll
@@ -337,6 +348,10 @@ struct DiskDB {
     HostBuf bfs_tok;  // host BFS: per group, the token word the launch posts when it is done (polled)
     unsigned bfs_seq = 0;
     std::vector<uint32_t> adj_host;
+    // diskann_hip_build_graph: adj_dev is ahead of adj_host (the resident search refreshes the host copy before it
+    // re-runs a flagged query on it); the last build's seconds in search / out-edge prunes / back-edges
+    bool adj_host_stale = false;
+    double build_s[3] = {0.0, 0.0, 0.0};
     ~DiskDB() {
         if (stream) { DeviceGuard g(device); (void)hipStreamDestroy(stream); }
     }
@@ -1102,6 +1117,7 @@ int diskann_hip_register_graph(void *h, const uint32_t *adj, int R) {
         DeviceGuard g(db->device);
         const size_t cnt = (size_t)db->n * R;
         db->adj_host.assign(adj, adj + cnt);
+        db->adj_host_stale = false;
         db->adj_dev.ensure(cnt * 4 + 16, db->device);
         if (cnt) HIPANN_CHECK(hipMemcpyAsync(db->adj_dev.p, adj, cnt * 4, hipMemcpyHostToDevice, db->stream));
         // rows with a repeated id (the traversal's first-occurrence dedupe runs only on those)
@@ -1121,22 +1137,13 @@ int diskann_hip_register_graph(void *h, const uint32_t *adj, int R) {
 
 // Resident search: queries / outputs in HBM, asynchronous launch on `stream`, then a wait for the
 // per-query flags (the rare flagged queries and unsupported shapes go through host_bfs).
-int diskann_hip_search_batch_resident_device(void *h, const uint32_t *eps, int n_ep, const float *queries_dev, int nq,
-                                             int k, int l_search, int metric, int64_t *out_ids_dev,
-                                             float *out_d_dev, int64_t *stats, void *stream, char *eb, int el) {
-    RoctxRange r_all("hipann.diskann.resident");
-    try {
-        HIPANN_REQUIRE(h && (n_ep == 0 || eps) && (nq == 0 || (queries_dev && out_ids_dev && out_d_dev)),
-                       "null argument");
-        HIPANN_REQUIRE(nq >= 0 && k > 0 && n_ep >= 0, "bad arguments");
-        HIPANN_REQUIRE(metric == kL2 || metric == kIP, "metric must be 0 or 1");
-        auto *db = static_cast<DiskDB *>(h);
-        std::lock_guard<std::mutex> lk(db->mu);
-        HIPANN_REQUIRE(db->R > 0, "no graph registered (diskann_hip_register_graph)");
-        DeviceGuard g(db->device);
-        const hipStream_t st = stream ? static_cast<hipStream_t>(stream) : db->stream;
+// (the caller holds db->mu and the device; the graph build searches its own frozen graph through this)
+static void resident_search_locked(DiskDB *db, const uint32_t *eps, int n_ep, const float *queries_dev, int nq, int k,
+                                   int l_search, int metric, int64_t *out_ids_dev, float *out_d_dev, int64_t *stats,
+                                   hipStream_t st) {
+    {
         if (stats) { stats[0] = stats[1] = stats[2] = stats[3] = 0; }
-        if (nq == 0) return 0;
+        if (nq == 0) return;
         const uint32_t N = (uint32_t)db->n;
         const int L = std::max(l_search, std::min<int>(k, (int)std::min<int64_t>(db->n, INT32_MAX)));
         const int kk = k;
@@ -1187,6 +1194,13 @@ int diskann_hip_search_batch_resident_device(void *h, const uint32_t *eps, int n
         int64_t hsteps = 0, hevals = 0;
         if (!redo.empty()) {
             const int nr = (int)redo.size(), dim = db->dim;
+            if (db->adj_host_stale) {  // a graph build in progress: the host copy as of this batch's frozen graph
+                db->adj_host.resize((size_t)db->n * db->R);
+                HIPANN_CHECK(hipMemcpyAsync(db->adj_host.data(), db->adj_dev.p, db->adj_host.size() * 4,
+                                            hipMemcpyDeviceToHost, st));
+                HIPANN_CHECK(hipStreamSynchronize(st));
+                db->adj_host_stale = false;
+            }
             std::vector<float> qh((size_t)nr * dim);
             for (int j = 0; j < nr; ++j)
                 HIPANN_CHECK(hipMemcpyAsync(qh.data() + (size_t)j * dim, queries_dev + (size_t)redo[j] * dim,
@@ -1213,6 +1227,24 @@ int diskann_hip_search_batch_resident_device(void *h, const uint32_t *eps, int n
             stats[2] = gpops;
             stats[3] = (int64_t)redo.size();
         }
+    }
+}
+
+int diskann_hip_search_batch_resident_device(void *h, const uint32_t *eps, int n_ep, const float *queries_dev, int nq,
+                                             int k, int l_search, int metric, int64_t *out_ids_dev,
+                                             float *out_d_dev, int64_t *stats, void *stream, char *eb, int el) {
+    RoctxRange r_all("hipann.diskann.resident");
+    try {
+        HIPANN_REQUIRE(h && (n_ep == 0 || eps) && (nq == 0 || (queries_dev && out_ids_dev && out_d_dev)),
+                       "null argument");
+        HIPANN_REQUIRE(nq >= 0 && k > 0 && n_ep >= 0, "bad arguments");
+        HIPANN_REQUIRE(metric == kL2 || metric == kIP, "metric must be 0 or 1");
+        auto *db = static_cast<DiskDB *>(h);
+        std::lock_guard<std::mutex> lk(db->mu);
+        HIPANN_REQUIRE(db->R > 0, "no graph registered (diskann_hip_register_graph)");
+        DeviceGuard g(db->device);
+        const hipStream_t st = stream ? static_cast<hipStream_t>(stream) : db->stream;
+        resident_search_locked(db, eps, n_ep, queries_dev, nq, k, l_search, metric, out_ids_dev, out_d_dev, stats, st);
         return 0;
     } catch (const std::exception &e) {
         set_err(eb, el, e.what());
@@ -1251,6 +1283,231 @@ int diskann_hip_search_batch_resident(void *h, const uint32_t *eps, int n_ep, co
             HIPANN_CHECK(hipMemcpyAsync(out_ids, oi.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
             HIPANN_CHECK(hipMemcpyAsync(out_d, od.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
         }
+        HIPANN_CHECK(hipStreamSynchronize(st));
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(eb, el, e.what());
+    } catch (...) {
+        set_err(eb, el, "hipann: unknown error");
+    }
+    return -1;
+}
+
+// ---- graph build on the device (kernels in diskann_build.hip) ----
+static void swap_buf(DevBuf &a, DevBuf &b) {
+    std::swap(a.p, b.p);
+    std::swap(a.bytes, b.bytes);
+    std::swap(a.device, b.device);
+}
+
+// the shapes both build entry points refuse (a message, never a slow path)
+static void build_shape_check(const DiskDB *db, int R, float alpha, int metric) {
+    HIPANN_REQUIRE(metric != kIP, "graph build: IP is not supported (the crate prunes IP by a different rule)");
+    HIPANN_REQUIRE(metric == kL2, "graph build: metric must be 0 (L2)");
+    HIPANN_REQUIRE(db->fmt == DISKANN_HIP_FMT_F32, "graph build: an fp32 DB is required (SQ8 is not supported)");
+    HIPANN_REQUIRE(R >= 1 && R <= 64, "graph build: R must be in [1, 64]");
+    HIPANN_REQUIRE(db->dim % 4 == 0 && db->dim <= 2048, "graph build: d must be a multiple of 4 and at most 2048");
+    HIPANN_REQUIRE(db->n < ((int64_t)1 << 31), "graph build: n must be below 2^31");
+    HIPANN_REQUIRE(alpha >= 1.0f, "graph build: alpha must be >= 1");  // (a NaN fails the comparison)
+}
+
+int diskann_hip_build_graph(void *h, int R, int l_build, float alpha, int metric, uint32_t entry_point, int batch_max,
+                            uint32_t *adjacency_out, int64_t *stats, char *eb, int el) {
+    try {
+        HIPANN_REQUIRE(h, "graph build: null db");
+        auto *db = static_cast<DiskDB *>(h);
+        std::lock_guard<std::mutex> lk(db->mu);
+        build_shape_check(db, R, alpha, metric);
+        HIPANN_REQUIRE(l_build >= 1 && l_build <= 256, "graph build: L must be in [1, 256]");
+        HIPANN_REQUIRE(batch_max >= 1, "graph build: batch_max must be >= 1");
+        HIPANN_REQUIRE((int64_t)entry_point < db->n, "graph build: entry_point must be below n");
+        DeviceGuard g(db->device);
+        RoctxRange rr("hipann.diskann.build_graph");
+        const hipStream_t st = db->stream;
+        const int64_t n = db->n;
+        const int d = db->dim, dev = db->device;
+        int64_t s8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        // The graph under construction sits in the DB's own graph slots (the traversal reads them); the slots' former
+        // contents come back if the build fails.  No built row repeats an id, so dupw stays zero.
+        DevBuf nadj, ndupw;
+        std::vector<uint32_t> nhost;
+        int nR = R;
+        nadj.ensure((size_t)n * R * 4 + 16, dev);
+        ndupw.ensure((size_t)((n + 31) / 32) * 4 + 16, dev);
+        HIPANN_CHECK(hipMemsetAsync(nadj.p, 0xff, (size_t)n * R * 4, st));
+        HIPANN_CHECK(hipMemsetAsync(ndupw.p, 0, (size_t)((n + 31) / 32) * 4, st));
+        struct Slots {
+            DiskDB *db;
+            DevBuf &a, &w;
+            std::vector<uint32_t> &hst;
+            int &R;
+            bool keep = false;
+            void exchange() {
+                swap_buf(db->adj_dev, a);
+                swap_buf(db->dupw, w);
+                db->adj_host.swap(hst);
+                std::swap(db->R, R);
+            }
+            ~Slots() {
+                if (!keep) exchange();
+                db->adj_host_stale = false;
+            }
+        } slots{db, nadj, ndupw, nhost, nR};
+        slots.exchange();
+        double secs[3] = {0.0, 0.0, 0.0};
+        using clk = std::chrono::steady_clock;
+        auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
+        if (n > 1) {
+            const uint32_t ep = entry_point;
+            const int K = (int)std::min<int64_t>(l_build, n);
+            const int bmax = (int)std::min<int64_t>(batch_max, n - 1);
+            const int64_t pairs = (int64_t)bmax * R;
+            const int64_t rows_max = std::min<int64_t>(pairs, n);  // rows one batch's back-edges can touch
+            const int64_t pool_words = rows_max * R + pairs;
+            HIPANN_REQUIRE(pairs < INT32_MAX && pool_words < INT32_MAX, "graph build: batch_max too large");
+            // scratch, once per build
+            DevBuf sid, sd, tg, cnt, slot, touched, off, fill, src, pool, ptgt, pbeg, plen, ctr, pctr, gram;
+            sid.ensure((size_t)bmax * K * 8, dev);
+            sd.ensure((size_t)bmax * K * 4, dev);
+            tg.ensure((size_t)bmax * 4, dev);
+            cnt.ensure((size_t)n * 4, dev);
+            slot.ensure((size_t)n * 4, dev);
+            touched.ensure((size_t)pairs * 4, dev);
+            off.ensure((size_t)pairs * 4, dev);
+            fill.ensure((size_t)pairs * 4, dev);
+            src.ensure((size_t)pairs * 4, dev);
+            pool.ensure((size_t)pool_words * 4, dev);
+            ptgt.ensure((size_t)rows_max * 4, dev);
+            pbeg.ensure((size_t)rows_max * 4, dev);
+            plen.ensure((size_t)rows_max * 4, dev);
+            ctr.ensure(16, dev);
+            pctr.ensure(32, dev);
+            const int blocks = vamana_prune_blocks(std::max<int64_t>(bmax, rows_max));
+            gram.ensure(vamana_gram_bytes(blocks), dev);
+            HIPANN_CHECK(hipMemsetAsync(pctr.p, 0, 32, st));
+            const float *x = db->data.get<float>();
+            uint32_t *adj = db->adj_dev.get<uint32_t>();
+            const uint32_t eps1[1] = {ep};
+            int64_t o0 = 0;  // rows inserted so far in insertion order (row order, the entry point left out)
+            while (o0 < n - 1) {
+                const int b = (int)std::min<int64_t>(std::min<int64_t>(bmax, std::max<int64_t>(1, o0 + 1)), n - 1 - o0);
+                const int64_t o1 = o0 + b;
+                // 1. search the frozen graph: the batch's rows are contiguous but for the entry point's gap
+                auto t0 = clk::now();
+                const int64_t seg[2][2] = {{o0, std::min<int64_t>(o1, ep)}, {std::max<int64_t>(o0, ep), o1}};
+                for (int sgi = 0; sgi < 2; ++sgi) {
+                    const int64_t oa = seg[sgi][0], ob = seg[sgi][1];
+                    if (ob <= oa) continue;
+                    const int64_t row0 = sgi == 0 ? oa : oa + 1;
+                    int64_t sst[4] = {0, 0, 0, 0};
+                    resident_search_locked(db, eps1, 1, x + row0 * d, (int)(ob - oa), K, l_build, kL2,
+                                           sid.get<int64_t>() + (oa - o0) * K, sd.get<float>() + (oa - o0) * K, sst, st);
+                    s8[0] += sst[0];
+                    s8[4] += sst[3];
+                }
+                secs[0] += since(t0);
+                // 2. out-edges: N(p) = prune(p, the traversal's list)
+                auto t1 = clk::now();
+                launch_vamana_fill_targets(tg.get<uint32_t>(), b, (uint32_t)o0, ep, st);
+                launch_vamana_prune(x, d, (uint32_t)n, tg.get<uint32_t>(), b, nullptr, nullptr, sid.get<int64_t>(),
+                                    sd.get<float>(), nullptr, nullptr, K, R, alpha, adj, true, gram.get<float>(), blocks,
+                                    pctr.get<unsigned long long>() + 2, st);
+                HIPANN_CHECK(hipStreamSynchronize(st));
+                secs[1] += since(t1);
+                // 3. back-edges, grouped per target row on the device; rows that overflow are pruned
+                auto t2 = clk::now();
+                HIPANN_CHECK(hipMemsetAsync(cnt.p, 0, (size_t)n * 4, st));
+                HIPANN_CHECK(hipMemsetAsync(ctr.p, 0, 16, st));
+                launch_vamana_backedges(adj, R, tg.get<uint32_t>(), b, cnt.get<int>(), slot.get<int>(),
+                                        touched.get<uint32_t>(), off.get<int>(), fill.get<int>(), src.get<uint32_t>(),
+                                        ctr.get<int>(), pool.get<uint32_t>(), ptgt.get<uint32_t>(), pbeg.get<int>(),
+                                        plen.get<int>(), st);
+                launch_vamana_prune(x, d, (uint32_t)n, ptgt.get<uint32_t>(), (int)std::min<int64_t>((int64_t)b * R, n),
+                                    ctr.get<int>() + 3, pool.get<uint32_t>(), nullptr, nullptr, pbeg.get<int>(),
+                                    plen.get<int>(), 0, R, alpha, adj, true, gram.get<float>(), blocks,
+                                    pctr.get<unsigned long long>(), st);
+                HIPANN_CHECK(hipStreamSynchronize(st));
+                secs[2] += since(t2);
+                db->adj_host_stale = true;
+                s8[1] += 1;
+                s8[2] += b;
+                o0 = o1;
+            }
+            unsigned long long pc[4] = {0, 0, 0, 0};
+            HIPANN_CHECK(hipMemcpyAsync(pc, pctr.p, 32, hipMemcpyDeviceToHost, st));
+            HIPANN_CHECK(hipStreamSynchronize(st));
+            s8[3] = (int64_t)pc[0];
+            s8[5] = (int64_t)(pc[1] + pc[3]);
+        }
+        // registered as after diskann_hip_register_graph: the host copy and the repeated-id row bits
+        launch_diskann_dup_rows(db->adj_dev.get<uint32_t>(), R, n, db->dupw.get<uint32_t>(), st);
+        db->adj_host.resize((size_t)n * R);
+        HIPANN_CHECK(hipMemcpyAsync(db->adj_host.data(), db->adj_dev.p, (size_t)n * R * 4, hipMemcpyDeviceToHost, st));
+        HIPANN_CHECK(hipStreamSynchronize(st));
+        {  // rows the entry point does not reach
+            const std::vector<uint32_t> &a = db->adj_host;
+            std::vector<uint8_t> seen((size_t)n, 0);
+            std::vector<uint32_t> stack{entry_point};
+            seen[entry_point] = 1;
+            int64_t reached = 1;
+            while (!stack.empty()) {
+                const uint32_t v = stack.back();
+                stack.pop_back();
+                for (int r = 0; r < R; ++r) {
+                    const uint32_t w = a[(size_t)v * R + r];
+                    if (w == 0xffffffffu) break;
+                    if (w < (uint64_t)n && !seen[w]) { seen[w] = 1; ++reached; stack.push_back(w); }
+                }
+            }
+            s8[6] = n - reached;
+        }
+        if (adjacency_out) std::memcpy(adjacency_out, db->adj_host.data(), (size_t)n * R * 4);
+        if (stats) std::memcpy(stats, s8, sizeof(s8));
+        for (int i = 0; i < 3; ++i) db->build_s[i] = secs[i];
+        slots.keep = true;
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(eb, el, e.what());
+    } catch (...) {
+        set_err(eb, el, "hipann: unknown error");
+    }
+    return -1;
+}
+
+int diskann_hip_build_phase_seconds(void *h, double *seconds) {
+    if (!h || !seconds) return -1;
+    auto *db = static_cast<DiskDB *>(h);
+    std::lock_guard<std::mutex> lk(db->mu);
+    for (int i = 0; i < 3; ++i) seconds[i] = db->build_s[i];
+    return 0;
+}
+
+int diskann_hip_robust_prune(void *h, const uint32_t *targets, int m, const uint32_t *pools, int pool_cap, int R,
+                             float alpha, int metric, uint32_t *out, char *eb, int el) {
+    try {
+        HIPANN_REQUIRE(h, "robust prune: null db");
+        auto *db = static_cast<DiskDB *>(h);
+        std::lock_guard<std::mutex> lk(db->mu);
+        build_shape_check(db, R, alpha, metric);
+        HIPANN_REQUIRE(m >= 0 && pool_cap >= 1 && (m == 0 || (targets && pools && out)), "robust prune: bad arguments");
+        for (int i = 0; i < m; ++i) HIPANN_REQUIRE((int64_t)targets[i] < db->n, "robust prune: target id out of range");
+        if (m == 0) return 0;
+        DeviceGuard g(db->device);
+        const hipStream_t st = db->stream;
+        const int dev = db->device;
+        DevBuf tg, pl, od, gram;
+        const size_t pw = (size_t)m * pool_cap;
+        tg.ensure((size_t)m * 4, dev);
+        pl.ensure(pw * 4, dev);
+        od.ensure((size_t)m * R * 4, dev);
+        const int blocks = vamana_prune_blocks(m);
+        gram.ensure(vamana_gram_bytes(blocks), dev);
+        HIPANN_CHECK(hipMemcpyAsync(tg.p, targets, (size_t)m * 4, hipMemcpyHostToDevice, st));
+        HIPANN_CHECK(hipMemcpyAsync(pl.p, pools, pw * 4, hipMemcpyHostToDevice, st));
+        launch_vamana_prune(db->data.get<float>(), db->dim, (uint32_t)db->n, tg.get<uint32_t>(), m, nullptr,
+                            pl.get<uint32_t>(), nullptr, nullptr, nullptr, nullptr, pool_cap, R, alpha,
+                            od.get<uint32_t>(), false, gram.get<float>(), blocks, nullptr, st);
+        HIPANN_CHECK(hipMemcpyAsync(out, od.p, (size_t)m * R * 4, hipMemcpyDeviceToHost, st));
         HIPANN_CHECK(hipStreamSynchronize(st));
         return 0;
     } catch (const std::exception &e) {

@@ -153,6 +153,11 @@ def lib() -> C.CDLL:
             "diskann_hip_kernel_stats": ([vp, C.POINTER(C.c_double), i64p], i32),
             "diskann_hip_search_batch": ([vp, C.POINTER(C.c_uint32), i32, C.POINTER(C.c_uint32), i32, f, i32, i32,
                                           i32, i32, i64p, f, i64p, cp, i32], i32),
+            "diskann_hip_build_graph": ([vp, i32, i32, C.c_float, i32, C.c_uint32, i32, C.POINTER(C.c_uint32), i64p, cp,
+                                         i32], i32),
+            "diskann_hip_robust_prune": ([vp, C.POINTER(C.c_uint32), i32, C.POINTER(C.c_uint32), i32, i32, C.c_float,
+                                          i32, C.POINTER(C.c_uint32), cp, i32], i32),
+            "diskann_hip_build_phase_seconds": ([vp, C.POINTER(C.c_double)], i32),
         }
         missing = [name for name in sig if not hasattr(L, name)]
         if missing:
@@ -710,6 +715,19 @@ def hip_multi_batch_distances(queries, candidates, query_map, total_n: int, nq: 
     return diskann_hip_multi_batch_distances(queries, candidates, query_map, total_n, nq, dim, metric, out) == 0
 
 
+def medoid(x) -> int:
+    """The row nearest the mean of `x` (L2; the smallest index on a tie): DiskANN's usual entry point."""
+    x = np.ascontiguousarray(x, np.float32)
+    c = x.mean(axis=0, dtype=np.float64)
+    best, best_d = 0, np.inf
+    for s in range(0, x.shape[0], 65536):  # (blocks: no n x d float64 temporary)
+        dd = ((x[s:s + 65536].astype(np.float64) - c) ** 2).sum(axis=1)
+        j = int(np.argmin(dd))
+        if dd[j] < best_d:
+            best, best_d = s + j, float(dd[j])
+    return best
+
+
 class DiskannDeviceDB:
     """HBM-resident DiskANN vectors (fp32 or SQ8) + the id-gather distance call."""
 
@@ -772,6 +790,39 @@ class DiskannDeviceDB:
             raise HipAnnError("adjacency must be (n, R)")
         if lib().diskann_hip_register_graph(self._h, _ptr(adj, C.c_uint32), adj.shape[1]) != 0:
             raise HipAnnError("diskann_hip_register_graph failed")
+
+    def build_graph(self, R: int = 64, L: int = 128, alpha: float = 1.2, entry_point: int = 0,
+                    batch_max: int = 4096, metric: int = METRIC_L2):
+        """Build the DiskANN graph of this fp32 DB on the GPU (batched insert, RobustPrune, back-edges)
+        and leave it registered for search_batch_resident.  Returns (adjacency (n, R) uint32, stats)."""
+        if not 0 <= int(entry_point) < 2 ** 32:
+            raise HipAnnError("graph build: entry_point must be below n")
+        adj = np.empty((self.n, max(int(R), 0)), np.uint32)
+        stats = np.zeros(8, np.int64)
+        eb = _err()
+        rc = lib().diskann_hip_build_graph(self._h, R, L, alpha, metric, int(entry_point), batch_max,
+                                           _ptr(adj, C.c_uint32), _ptr(stats, C.c_int64), eb, 1024)
+        _check(rc, eb)
+        sec = (C.c_double * 3)()
+        if lib().diskann_hip_build_phase_seconds(self._h, sec) != 0:
+            raise HipAnnError("diskann_hip_build_phase_seconds failed")
+        return adj, {"search_evals": int(stats[0]), "batches": int(stats[1]), "out_prunes": int(stats[2]),
+                     "back_prunes": int(stats[3]), "host_requeries": int(stats[4]), "pools_truncated": int(stats[5]),
+                     "unreachable": int(stats[6]), "search_s": sec[0], "out_prune_s": sec[1], "back_edge_s": sec[2]}
+
+    def robust_prune(self, targets, pools, R: int, alpha: float = 1.2, metric: int = METRIC_L2) -> np.ndarray:
+        """prune() of DESIGN §6 for each target over its row of `pools` (m, pool_cap) uint32 ids (UINT32_MAX padding;
+        the target itself, repeats and ids >= n are dropped).  Returns (m, R) uint32 ids, UINT32_MAX-padded."""
+        tg = np.ascontiguousarray(targets, np.uint32).reshape(-1)
+        pl = np.ascontiguousarray(pools, np.uint32)
+        if pl.ndim != 2 or pl.shape[0] != tg.size:
+            raise HipAnnError("pools must be (len(targets), pool_cap)")
+        out = np.empty((tg.size, max(int(R), 0)), np.uint32)
+        eb = _err()
+        rc = lib().diskann_hip_robust_prune(self._h, _ptr(tg, C.c_uint32), tg.size, _ptr(pl, C.c_uint32), pl.shape[1],
+                                            R, alpha, metric, _ptr(out, C.c_uint32), eb, 1024)
+        _check(rc, eb)
+        return out
 
     def search_batch_resident(self, entry_points, queries, k: int, l_search: int, metric: int = METRIC_L2):
         """DiskProvider::search_batch with the traversal itself on the GPU (one 2-wavefront workgroup per query).

@@ -113,6 +113,27 @@ int diskann_hip_search_batch_resident_device(void *db, const uint32_t *entry_poi
                                              int64_t *out_ids_dev, float *out_dists_dev, int64_t *stats, void *stream,
                                              char *err_buf, int err_len);
 
+/* ---- extension: graph build on the device -------------------------------------------
+ * Batched insert + RobustPrune + back-edge update against the registered fp32 DB, L2 only.  Refused with a
+ * message (never a slow path): IP, an SQ8 DB, R > 64, L > 256, L < 1, d % 4 != 0, d > 2048, n >= 2^31,
+ * alpha < 1 or NaN, entry_point >= n, batch_max < 1.  A refused call leaves a registered graph as it was. */
+
+/* Build the graph of the registered fp32 DB on the device (spec: DESIGN §6).  adjacency_out: n*R uint32 (host, may be NULL).
+ * On success the graph is also registered on `db`, as after diskann_hip_register_graph.  stats (may be NULL, 8 int64):
+ * [0] search distance evaluations, [1] batches, [2] out-edge prunes, [3] back-edge prunes, [4] searches re-run on the
+ * host, [5] pools truncated to 256, [6] rows unreachable from entry_point, [7] reserved.  0 / -1 (message in err_buf). */
+int diskann_hip_build_graph(void *db, int R, int l_build, float alpha, int metric, uint32_t entry_point,
+                            int batch_max, uint32_t *adjacency_out, int64_t *stats, char *err_buf, int err_len);
+
+/* prune() of the spec for m targets: pools is m*pool_cap ids (UINT32_MAX-padded; self, repeats and ids >= n are
+ * dropped), distances to the target computed on the device.  out: m*R ids, UINT32_MAX-padded.  Host pointers; synchronous. */
+int diskann_hip_robust_prune(void *db, const uint32_t *targets, int m, const uint32_t *pools, int pool_cap, int R,
+                             float alpha, int metric, uint32_t *out, char *err_buf, int err_len);
+
+/* Measurement: host seconds of the last diskann_hip_build_graph on `db`, per phase: [0] searches, [1] out-edge
+ * prunes, [2] back-edges (grouping, appends, prunes).  seconds: 3 doubles. */
+int diskann_hip_build_phase_seconds(void *db, double *seconds);
+
 int64_t diskann_hip_db_size(void *db);
 
 /* Measurement: record HIP events around every id-gather kernel launch of `db` (on its stream) from now
