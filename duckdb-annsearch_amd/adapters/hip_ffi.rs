@@ -18,7 +18,7 @@
 //! Source only in this repository (no cargo/rustc in the build image); INTEGRATION.md shows the
 //! Cargo / CMake wiring.
 
-use std::sync::atomic::{AtomicI32, Ordering};
+use std::sync::atomic::{AtomicI32, AtomicUsize, Ordering};
 
 extern "C" {
     fn diskann_hip_available() -> i32;
@@ -118,6 +118,19 @@ extern "C" {
         err_buf: *mut core::ffi::c_char,
         err_len: i32,
     ) -> i32;
+    fn diskann_hip_remove_ids(
+        db: *mut core::ffi::c_void,
+        labels: *const i64,
+        n_labels: i64,
+        alpha: f32,
+        metric: i32,
+        entry_point: *mut u32,
+        scratch_words: i64,
+        adjacency_out: *mut u32,
+        stats: *mut i64,
+        err_buf: *mut core::ffi::c_char,
+        err_len: i32,
+    ) -> i64;
 }
 
 /// Cached availability: -1 = unchecked, 0 = unavailable, 1 = available (metal_ffi.rs:33-34).
@@ -207,6 +220,9 @@ pub struct HipDiskDb {
     h: *mut core::ffi::c_void,
     n: usize,
     dim: usize,
+    /// degree of the graph registered on the handle (register_graph / build_graph), 0 = none: what the C side
+    /// uses for every adjacency it writes back
+    degree: AtomicUsize,
 }
 
 unsafe impl Send for HipDiskDb {}
@@ -222,7 +238,7 @@ impl HipDiskDb {
         let h = unsafe {
             diskann_hip_register_db(vectors.as_ptr() as *const _, n as i64, dim as i32, 0, std::ptr::null(), std::ptr::null())
         };
-        if h.is_null() { None } else { Some(HipDiskDb { h, n, dim }) }
+        if h.is_null() { None } else { Some(HipDiskDb { h, n, dim, degree: AtomicUsize::new(0) }) }
     }
 
     /// SQ8 codes with the provider's per-dimension min / scale (provider.rs:25-38).
@@ -239,7 +255,7 @@ impl HipDiskDb {
         let h = unsafe {
             diskann_hip_register_db(codes.as_ptr() as *const _, n as i64, dim as i32, 1, min.as_ptr(), scale.as_ptr())
         };
-        if h.is_null() { None } else { Some(HipDiskDb { h, n, dim }) }
+        if h.is_null() { None } else { Some(HipDiskDb { h, n, dim, degree: AtomicUsize::new(0) }) }
     }
 
     /// Slice shapes of a query batch: nq × dim queries, every count within the C ABI's i32.
@@ -305,7 +321,11 @@ impl HipDiskDb {
         if max_degree == 0 || max_degree > i32::MAX as usize || self.n.checked_mul(max_degree) != Some(adjacency.len()) {
             return false;
         }
-        unsafe { diskann_hip_register_graph(self.h, adjacency.as_ptr(), max_degree as i32) == 0 }
+        let ok = unsafe { diskann_hip_register_graph(self.h, adjacency.as_ptr(), max_degree as i32) == 0 };
+        if ok {
+            self.degree.store(max_degree, Ordering::Release);
+        }
+        ok
     }
 
     /// DiskProvider::search_batch with the traversal on the GPU (one workgroup per query runs the reference's
@@ -446,7 +466,51 @@ impl HipDiskDb {
         if ret != 0 {
             return None;
         }
+        self.degree.store(max_degree, Ordering::Release);
         Some((adjacency, stats))
+    }
+
+    /// Remove rows from the DB and its registered graph in place — the device counterpart of
+    /// InMemoryIndex::compact's rebuild of the survivors (index_manager.rs:687-716).  `labels` are row ids (the
+    /// tombstoned labels; duplicates and ids outside the DB are ignored).  Survivors keep their order and new id =
+    /// old id − removed rows below it: the label_map `compact` returns.  Returns the n' × degree adjacency (degree:
+    /// the one this handle recorded at register_graph / build_graph, which is the one the C side writes with), the
+    /// new entry point and the eight counters of hip_diskann_bridge.h; the handle then holds n' rows.  None ⇒ no
+    /// graph was registered through this handle, the call was refused or the device failed, and the handle answers
+    /// as before; the caller rebuilds on the CPU.
+    pub fn remove_ids(&mut self, labels: &[i64], alpha: f32, entry_point: u32) -> Option<(Vec<u32>, u32, [i64; 8])> {
+        let degree = self.degree.load(Ordering::Acquire);
+        // the C side refuses degrees above 64 before it writes anything
+        if degree == 0 || degree > 64 || labels.len() > i64::MAX as usize {
+            return None;
+        }
+        // room for the no-label case, which writes all n × degree words back
+        let words = self.n.checked_mul(degree)?;
+        let mut adjacency = vec![u32::MAX; words];
+        let mut stats = [0i64; 8];
+        let mut ep = entry_point;
+        let mut err = [0 as core::ffi::c_char; 256];
+        let removed = unsafe {
+            diskann_hip_remove_ids(
+                self.h,
+                labels.as_ptr(),
+                labels.len() as i64,
+                alpha,
+                0,
+                &mut ep,
+                0,
+                adjacency.as_mut_ptr(),
+                stats.as_mut_ptr(),
+                err.as_mut_ptr(),
+                err.len() as i32,
+            )
+        };
+        if removed < 0 || removed as usize > self.n {
+            return None;
+        }
+        self.n -= removed as usize;
+        adjacency.truncate(self.n * degree);
+        Some((adjacency, ep, stats))
     }
 
     /// prune() of DESIGN §6 for `targets.len()` nodes over `pools` (targets.len() × pool_cap ids, u32::MAX padding).

@@ -52,6 +52,20 @@ void launch_vamana_fill_targets(uint32_t *tg, int b, uint32_t o0, uint32_t ep, h
 void launch_vamana_backedges(uint32_t *adj, int R, const uint32_t *tg, int b, int *cnt, int *slot, uint32_t *touched,
                              int *off, int *fill, uint32_t *src, int *ctr, uint32_t *pool, uint32_t *ptgt, int *pbeg,
                              int *plen, hipStream_t st);
+// diskann_remove.hip
+int64_t diskann_remove_scan_blocks(int64_t n);
+void launch_diskann_remove_mark(const int64_t *labels, int64_t m, int64_t n, uint32_t *bits, uint32_t *wpre,
+                                uint32_t *sums, hipStream_t st);
+void launch_diskann_remove_sources(const uint32_t *bits, const uint32_t *wpre, int64_t n, int64_t *src, hipStream_t st);
+void launch_diskann_remove_pool_len(const uint32_t *adj, int R, int64_t n, const uint32_t *bits, uint8_t *nrem,
+                                    hipStream_t st);
+void launch_diskann_remove_pool_fill(const uint32_t *adj, int R, int64_t n, const uint32_t *bits,
+                                     const uint32_t *targets, const int *pbeg, const int *plen, int cnt, uint32_t *pool,
+                                     unsigned long long *gathered, hipStream_t st);
+void launch_diskann_remove_nearest(const float *x, int d, int64_t n, const uint32_t *bits, uint32_t ep,
+                                   unsigned long long *best, hipStream_t st);
+void launch_diskann_remove_compact_adj(const uint32_t *adj, int R, int64_t n, const uint32_t *bits,
+                                       const uint32_t *wpre, uint32_t *out, hipStream_t st);
 
 __device__ __forceinline__ float wave_sum(float s) {
 #pragma unroll
@@ -352,6 +366,7 @@ struct DiskDB {
     // re-runs a flagged query on it); the last build's seconds in search / out-edge prunes / back-edges
     bool adj_host_stale = false;
     double build_s[3] = {0.0, 0.0, 0.0};
+    double remove_s[3] = {0.0, 0.0, 0.0};  // the last diskann_hip_remove_ids: pool build, prune, compact
     ~DiskDB() {
         if (stream) { DeviceGuard g(device); (void)hipStreamDestroy(stream); }
     }
@@ -1300,15 +1315,34 @@ static void swap_buf(DevBuf &a, DevBuf &b) {
     std::swap(a.device, b.device);
 }
 
-// the shapes both build entry points refuse (a message, never a slow path)
-static void build_shape_check(const DiskDB *db, int R, float alpha, int metric) {
-    HIPANN_REQUIRE(metric != kIP, "graph build: IP is not supported (the crate prunes IP by a different rule)");
-    HIPANN_REQUIRE(metric == kL2, "graph build: metric must be 0 (L2)");
-    HIPANN_REQUIRE(db->fmt == DISKANN_HIP_FMT_F32, "graph build: an fp32 DB is required (SQ8 is not supported)");
-    HIPANN_REQUIRE(R >= 1 && R <= 64, "graph build: R must be in [1, 64]");
-    HIPANN_REQUIRE(db->dim % 4 == 0 && db->dim <= 2048, "graph build: d must be a multiple of 4 and at most 2048");
-    HIPANN_REQUIRE(db->n < ((int64_t)1 << 31), "graph build: n must be below 2^31");
-    HIPANN_REQUIRE(alpha >= 1.0f, "graph build: alpha must be >= 1");  // (a NaN fails the comparison)
+// the shapes the build entry points and remove_ids refuse (a message, never a slow path); `who` names the call
+static void build_shape_check(const DiskDB *db, int R, float alpha, int metric, const char *who = "graph build") {
+    const std::string w = std::string(who) + ": ";
+    HIPANN_REQUIRE(metric != kIP, w + "IP is not supported (the crate prunes IP by a different rule)");
+    HIPANN_REQUIRE(metric == kL2, w + "metric must be 0 (L2)");
+    HIPANN_REQUIRE(db->fmt == DISKANN_HIP_FMT_F32, w + "an fp32 DB is required (SQ8 is not supported)");
+    HIPANN_REQUIRE(R >= 1 && R <= 64, w + "R must be in [1, 64]");
+    HIPANN_REQUIRE(db->dim % 4 == 0 && db->dim <= 2048, w + "d must be a multiple of 4 and at most 2048");
+    HIPANN_REQUIRE(db->n < ((int64_t)1 << 31), w + "n must be below 2^31");
+    HIPANN_REQUIRE(alpha >= 1.0f, w + "alpha must be >= 1");  // (a NaN fails the comparison)
+}
+
+// rows a walk from entry_point over the host adjacency does not reach (rows end at the first UINT32_MAX)
+static int64_t unreached_rows(const std::vector<uint32_t> &a, int64_t n, int R, uint32_t entry_point) {
+    std::vector<uint8_t> seen((size_t)n, 0);
+    std::vector<uint32_t> stack{entry_point};
+    seen[entry_point] = 1;
+    int64_t reached = 1;
+    while (!stack.empty()) {
+        const uint32_t v = stack.back();
+        stack.pop_back();
+        for (int r = 0; r < R; ++r) {
+            const uint32_t w = a[(size_t)v * R + r];
+            if (w == 0xffffffffu) break;
+            if (w < (uint64_t)n && !seen[w]) { seen[w] = 1; ++reached; stack.push_back(w); }
+        }
+    }
+    return n - reached;
 }
 
 int diskann_hip_build_graph(void *h, int R, int l_build, float alpha, int metric, uint32_t entry_point, int batch_max,
@@ -1444,23 +1478,7 @@ int diskann_hip_build_graph(void *h, int R, int l_build, float alpha, int metric
         db->adj_host.resize((size_t)n * R);
         HIPANN_CHECK(hipMemcpyAsync(db->adj_host.data(), db->adj_dev.p, (size_t)n * R * 4, hipMemcpyDeviceToHost, st));
         HIPANN_CHECK(hipStreamSynchronize(st));
-        {  // rows the entry point does not reach
-            const std::vector<uint32_t> &a = db->adj_host;
-            std::vector<uint8_t> seen((size_t)n, 0);
-            std::vector<uint32_t> stack{entry_point};
-            seen[entry_point] = 1;
-            int64_t reached = 1;
-            while (!stack.empty()) {
-                const uint32_t v = stack.back();
-                stack.pop_back();
-                for (int r = 0; r < R; ++r) {
-                    const uint32_t w = a[(size_t)v * R + r];
-                    if (w == 0xffffffffu) break;
-                    if (w < (uint64_t)n && !seen[w]) { seen[w] = 1; ++reached; stack.push_back(w); }
-                }
-            }
-            s8[6] = n - reached;
-        }
+        s8[6] = unreached_rows(db->adj_host, n, R, entry_point);
         if (adjacency_out) std::memcpy(adjacency_out, db->adj_host.data(), (size_t)n * R * 4);
         if (stats) std::memcpy(stats, s8, sizeof(s8));
         for (int i = 0; i < 3; ++i) db->build_s[i] = secs[i];
@@ -1479,6 +1497,191 @@ int diskann_hip_build_phase_seconds(void *h, double *seconds) {
     auto *db = static_cast<DiskDB *>(h);
     std::lock_guard<std::mutex> lk(db->mu);
     for (int i = 0; i < 3; ++i) seconds[i] = db->build_s[i];
+    return 0;
+}
+
+// ---- row removal from the device graph (kernels in diskann_remove.hip) ----
+int64_t diskann_hip_remove_ids(void *h, const int64_t *labels, int64_t n_labels, float alpha, int metric,
+                               uint32_t *entry_point, int64_t scratch_words, uint32_t *adjacency_out, int64_t *stats,
+                               char *eb, int el) {
+    try {
+        HIPANN_REQUIRE(h, "remove_ids: null db");
+        auto *db = static_cast<DiskDB *>(h);
+        std::lock_guard<std::mutex> lk(db->mu);
+        HIPANN_REQUIRE(db->R > 0, "remove_ids: no graph registered (diskann_hip_register_graph / _build_graph)");
+        build_shape_check(db, db->R, alpha, metric, "remove_ids");
+        HIPANN_REQUIRE(entry_point, "remove_ids: null entry_point");
+        HIPANN_REQUIRE(n_labels >= 0 && (n_labels == 0 || labels) && scratch_words >= 0, "remove_ids: bad arguments");
+        HIPANN_REQUIRE((int64_t)*entry_point < db->n, "remove_ids: entry_point must be below n");
+        const int64_t n = db->n;
+        const int R = db->R, d = db->dim, dev = db->device;
+        const uint32_t ep = *entry_point;
+        int64_t s8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        // D: the distinct labels in range
+        std::vector<uint32_t> dead;
+        for (int64_t i = 0; i < n_labels; ++i)
+            if (labels[i] >= 0 && labels[i] < n) dead.push_back((uint32_t)labels[i]);
+        std::sort(dead.begin(), dead.end());
+        dead.erase(std::unique(dead.begin(), dead.end()), dead.end());
+        const int64_t nd = (int64_t)dead.size(), n2 = n - nd;
+        if (nd == 0) {  // nothing moves
+            s8[6] = unreached_rows(db->adj_host, n, R, ep);
+            if (adjacency_out) std::memcpy(adjacency_out, db->adj_host.data(), (size_t)n * R * 4);
+            if (stats) std::memcpy(stats, s8, sizeof(s8));
+            return 0;
+        }
+        HIPANN_REQUIRE(n2 > 0, "remove_ids: every row would be removed");
+        DeviceGuard g(db->device);
+        RoctxRange rr("hipann.diskann.remove_ids");
+        const hipStream_t st = db->stream;
+        using clk = std::chrono::steady_clock;
+        auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
+        double secs[3] = {0.0, 0.0, 0.0};
+        KernelTimer fill_ev, prune_ev;  // device time of the slabs' pool fills and prunes (read after the last sync)
+        fill_ev.reset(true, db->device);
+        prune_ev.reset(true, db->device);
+        const auto t_call = clk::now();
+        const float *x = db->data.get<float>();
+        const uint32_t *adj = db->adj_dev.get<uint32_t>();
+
+        // 1. mark, rank, and every live row's count of removed neighbours
+        auto t0 = clk::now();
+        const int64_t words = (n + 31) / 32;
+        DevBuf lab, bits, wpre, sums, nrem, radj, ctr;
+        lab.ensure((size_t)n_labels * 8, dev);
+        bits.ensure((size_t)words * 4, dev);
+        wpre.ensure((size_t)words * 4, dev);
+        sums.ensure((size_t)diskann_remove_scan_blocks(n) * 4, dev);
+        nrem.ensure((size_t)n, dev);
+        radj.ensure((size_t)n * R * 4 + 16, dev);
+        ctr.ensure(32, dev);
+        HIPANN_CHECK(hipMemcpyAsync(lab.p, labels, (size_t)n_labels * 8, hipMemcpyHostToDevice, st));
+        launch_diskann_remove_mark(lab.get<int64_t>(), n_labels, n, bits.get<uint32_t>(), wpre.get<uint32_t>(),
+                                   sums.get<uint32_t>(), st);
+        launch_diskann_remove_pool_len(adj, R, n, bits.get<uint32_t>(), nrem.get<uint8_t>(), st);
+        // the repaired graph in the old id space: the stored rows, the pruned ones written over them
+        HIPANN_CHECK(hipMemcpyAsync(radj.p, adj, (size_t)n * R * 4, hipMemcpyDeviceToDevice, st));
+        HIPANN_CHECK(hipMemsetAsync(ctr.p, 0, 32, st));
+        std::vector<uint8_t> hrem((size_t)n);
+        HIPANN_CHECK(hipMemcpyAsync(hrem.data(), nrem.p, (size_t)n, hipMemcpyDeviceToHost, st));
+        HIPANN_CHECK(hipStreamSynchronize(st));
+        // slabs of affected rows whose pool slots fit the budget (a row over the budget takes a slab alone)
+        const int64_t budget = std::min<int64_t>(scratch_words > 0 ? scratch_words : (int64_t)1 << 28, 0x7fff0000);
+        std::vector<uint32_t> tg;
+        std::vector<int> pbeg, plen;
+        std::vector<int64_t> slab_at{0};
+        int64_t used = 0, pool_words = 0, slab_rows = 0;
+        for (int64_t p = 0; p < n; ++p) {
+            if (!hrem[p]) continue;
+            const int len = R * (1 + (int)hrem[p]);
+            if (used > 0 && used + len > budget) {
+                slab_at.push_back((int64_t)tg.size());
+                used = 0;
+            }
+            tg.push_back((uint32_t)p);
+            pbeg.push_back((int)used);
+            plen.push_back(len);
+            used += len;
+            pool_words = std::max(pool_words, used);
+        }
+        slab_at.push_back((int64_t)tg.size());
+        const int64_t na = (int64_t)tg.size();
+        for (size_t s = 0; s + 1 < slab_at.size(); ++s) slab_rows = std::max(slab_rows, slab_at[s + 1] - slab_at[s]);
+        secs[0] += since(t0);
+        if (na > 0) {
+            DevBuf dtg, dbeg, dlen, pool, gram;
+            dtg.ensure((size_t)na * 4, dev);
+            dbeg.ensure((size_t)na * 4, dev);
+            dlen.ensure((size_t)na * 4, dev);
+            pool.ensure((size_t)pool_words * 4, dev);
+            const int blocks = vamana_prune_blocks(slab_rows);
+            gram.ensure(vamana_gram_bytes(blocks), dev);
+            HIPANN_CHECK(hipMemcpyAsync(dtg.p, tg.data(), (size_t)na * 4, hipMemcpyHostToDevice, st));
+            HIPANN_CHECK(hipMemcpyAsync(dbeg.p, pbeg.data(), (size_t)na * 4, hipMemcpyHostToDevice, st));
+            HIPANN_CHECK(hipMemcpyAsync(dlen.p, plen.data(), (size_t)na * 4, hipMemcpyHostToDevice, st));
+            unsigned long long *c64 = ctr.get<unsigned long long>();
+            // the stream orders fill, prune and the next slab's reuse of `pool`; events split the device time
+            for (size_t s = 0; s + 1 < slab_at.size(); ++s) {
+                const int64_t a0 = slab_at[s];
+                const int cnt = (int)(slab_at[s + 1] - a0);
+                if (cnt <= 0) continue;
+                {
+                    ScopedTiming tm(fill_ev, st);
+                    launch_diskann_remove_pool_fill(adj, R, n, bits.get<uint32_t>(), dtg.get<uint32_t>() + a0,
+                                                    dbeg.get<int>() + a0, dlen.get<int>() + a0, cnt,
+                                                    pool.get<uint32_t>(), c64 + 2, st);
+                }
+                {
+                    ScopedTiming tm(prune_ev, st);
+                    launch_vamana_prune(x, d, (uint32_t)n, dtg.get<uint32_t>() + a0, cnt, nullptr, pool.get<uint32_t>(),
+                                        nullptr, nullptr, dbeg.get<int>() + a0, dlen.get<int>() + a0, 0, R, alpha,
+                                        radj.get<uint32_t>(), true, gram.get<float>(), blocks, c64, st);
+                }
+                s8[4] += 1;
+            }
+        }
+        // 2. the entry point: relabelled, or replaced by the nearest live row before the rows move
+        uint32_t nep = ep;
+        unsigned long long hc[4] = {0, 0, 0, ~0ull};
+        if (std::binary_search(dead.begin(), dead.end(), ep)) {
+            HIPANN_CHECK(hipMemsetAsync(ctr.get<unsigned long long>() + 3, 0xff, 8, st));
+            launch_diskann_remove_nearest(x, d, n, bits.get<uint32_t>(), ep, ctr.get<unsigned long long>() + 3, st);
+            s8[5] = 1;
+        }
+        // 3. compact into fresh buffers: rows, adjacency (ids replaced by their ranks), repeated-id row bits
+        DevBuf src, nx, nadj, ndupw;
+        std::vector<uint32_t> nhost((size_t)n2 * R);
+        src.ensure((size_t)n2 * 8, dev);
+        nx.ensure((size_t)n2 * d * 4 + 16, dev);
+        nadj.ensure((size_t)n2 * R * 4 + 16, dev);
+        ndupw.ensure((size_t)((n2 + 31) / 32) * 4 + 16, dev);
+        launch_diskann_remove_sources(bits.get<uint32_t>(), wpre.get<uint32_t>(), n, src.get<int64_t>(), st);
+        launch_flat_gather_rows(x, src.get<int64_t>(), n2, d, nx.get<float>(), st);
+        launch_diskann_remove_compact_adj(radj.get<uint32_t>(), R, n, bits.get<uint32_t>(), wpre.get<uint32_t>(),
+                                          nadj.get<uint32_t>(), st);
+        launch_diskann_dup_rows(nadj.get<uint32_t>(), R, n2, ndupw.get<uint32_t>(), st);
+        HIPANN_CHECK(hipMemcpyAsync(nhost.data(), nadj.p, (size_t)n2 * R * 4, hipMemcpyDeviceToHost, st));
+        HIPANN_CHECK(hipMemcpyAsync(hc, ctr.p, 32, hipMemcpyDeviceToHost, st));
+        HIPANN_CHECK(hipStreamSynchronize(st));
+        if (s8[5]) {
+            HIPANN_REQUIRE(hc[3] != ~0ull, "remove_ids: no live row found for the entry point");
+            nep = (uint32_t)(hc[3] & 0xffffffffull);
+        }
+        nep -= (uint32_t)(std::lower_bound(dead.begin(), dead.end(), nep) - dead.begin());
+        s8[0] = nd;
+        s8[1] = (int64_t)hc[0];
+        s8[2] = (int64_t)hc[1];
+        s8[3] = (int64_t)hc[2];
+        s8[6] = unreached_rows(nhost, n2, R, nep);
+        // phases: host time up to the slab plan plus the fills' device time; the prunes' device time; the rest
+        secs[0] += fill_ev.average_ms() * (double)fill_ev.used * 1e-3;
+        secs[1] = prune_ev.average_ms() * (double)prune_ev.used * 1e-3;
+        secs[2] = std::max(0.0, since(t_call) - secs[0] - secs[1]);
+        // everything is built: swap it in
+        swap_buf(db->data, nx);
+        swap_buf(db->adj_dev, nadj);
+        swap_buf(db->dupw, ndupw);
+        db->adj_host.swap(nhost);
+        db->adj_host_stale = false;
+        db->n = n2;
+        *entry_point = nep;
+        if (adjacency_out) std::memcpy(adjacency_out, db->adj_host.data(), (size_t)n2 * R * 4);
+        if (stats) std::memcpy(stats, s8, sizeof(s8));
+        for (int i = 0; i < 3; ++i) db->remove_s[i] = secs[i];
+        return nd;
+    } catch (const std::exception &e) {
+        set_err(eb, el, e.what());
+    } catch (...) {
+        set_err(eb, el, "hipann: unknown error");
+    }
+    return -1;
+}
+
+int diskann_hip_remove_phase_seconds(void *h, double *seconds) {
+    if (!h || !seconds) return -1;
+    auto *db = static_cast<DiskDB *>(h);
+    std::lock_guard<std::mutex> lk(db->mu);
+    for (int i = 0; i < 3; ++i) seconds[i] = db->remove_s[i];
     return 0;
 }
 

@@ -158,6 +158,9 @@ def lib() -> C.CDLL:
             "diskann_hip_robust_prune": ([vp, C.POINTER(C.c_uint32), i32, C.POINTER(C.c_uint32), i32, i32, C.c_float,
                                           i32, C.POINTER(C.c_uint32), cp, i32], i32),
             "diskann_hip_build_phase_seconds": ([vp, C.POINTER(C.c_double)], i32),
+            "diskann_hip_remove_ids": ([vp, i64p, i64, C.c_float, i32, C.POINTER(C.c_uint32), i64,
+                                        C.POINTER(C.c_uint32), i64p, cp, i32], i64),
+            "diskann_hip_remove_phase_seconds": ([vp, C.POINTER(C.c_double)], i32),
         }
         missing = [name for name in sig if not hasattr(L, name)]
         if missing:
@@ -747,6 +750,7 @@ class DiskannDeviceDB:
             raise HipAnnError("diskann_hip_register_db failed")
         self._h = C.c_void_p(h)
         self.n, self.dim, self.fmt = n, dim, fmt
+        self.R = 0  # degree of the registered graph (0: none)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -790,6 +794,7 @@ class DiskannDeviceDB:
             raise HipAnnError("adjacency must be (n, R)")
         if lib().diskann_hip_register_graph(self._h, _ptr(adj, C.c_uint32), adj.shape[1]) != 0:
             raise HipAnnError("diskann_hip_register_graph failed")
+        self.R = adj.shape[1]
 
     def build_graph(self, R: int = 64, L: int = 128, alpha: float = 1.2, entry_point: int = 0,
                     batch_max: int = 4096, metric: int = METRIC_L2):
@@ -803,12 +808,43 @@ class DiskannDeviceDB:
         rc = lib().diskann_hip_build_graph(self._h, R, L, alpha, metric, int(entry_point), batch_max,
                                            _ptr(adj, C.c_uint32), _ptr(stats, C.c_int64), eb, 1024)
         _check(rc, eb)
+        self.R = int(R)
         sec = (C.c_double * 3)()
         if lib().diskann_hip_build_phase_seconds(self._h, sec) != 0:
             raise HipAnnError("diskann_hip_build_phase_seconds failed")
         return adj, {"search_evals": int(stats[0]), "batches": int(stats[1]), "out_prunes": int(stats[2]),
                      "back_prunes": int(stats[3]), "host_requeries": int(stats[4]), "pools_truncated": int(stats[5]),
                      "unreachable": int(stats[6]), "search_s": sec[0], "out_prune_s": sec[1], "back_edge_s": sec[2]}
+
+    def remove_ids(self, labels, entry_point: int, alpha: float = 1.2, metric: int = METRIC_L2,
+                   scratch_words: int = 0):
+        """Remove rows from this DB and its registered graph in place (the rows that point at a removed
+        row are repaired with RobustPrune, then rows and adjacency are compacted and relabelled; new id = old id −
+        removed rows below it).  Duplicate labels and labels outside [0, n) are ignored.  Returns (adjacency (n', R)
+        uint32, new entry point, stats) and updates self.n."""
+        lab = np.ascontiguousarray(labels, np.int64).reshape(-1)
+        if not 0 <= int(entry_point) < 2 ** 32:
+            raise HipAnnError("remove_ids: entry_point must be below n")
+        R = self.R
+        adj = np.empty((self.n, R), np.uint32)
+        stats = np.zeros(8, np.int64)
+        ep = C.c_uint32(int(entry_point))
+        eb = _err()
+        rc = lib().diskann_hip_remove_ids(self._h, _ptr(lab, C.c_int64), lab.size, alpha, metric, C.byref(ep),
+                                          int(scratch_words), _ptr(adj, C.c_uint32) if R else None,
+                                          _ptr(stats, C.c_int64), eb, 1024)
+        if rc < 0:
+            raise HipAnnError(eb.value.decode(errors="replace") or "hipann error")
+        self.n = int(lib().diskann_hip_db_size(self._h))
+        sec = (C.c_double * 3)()
+        if lib().diskann_hip_remove_phase_seconds(self._h, sec) != 0:
+            raise HipAnnError("diskann_hip_remove_phase_seconds failed")
+        adj = np.ascontiguousarray(adj.reshape(-1)[:self.n * R].reshape(self.n, R))
+        return adj, int(ep.value), {"removed": int(stats[0]), "repaired": int(stats[1]),
+                                    "pools_truncated": int(stats[2]), "pool_ids": int(stats[3]),
+                                    "slabs": int(stats[4]), "entry_replaced": int(stats[5]),
+                                    "unreachable": int(stats[6]), "pool_s": sec[0], "prune_s": sec[1],
+                                    "compact_s": sec[2]}
 
     def robust_prune(self, targets, pools, R: int, alpha: float = 1.2, metric: int = METRIC_L2) -> np.ndarray:
         """prune() of DESIGN §6 for each target over its row of `pools` (m, pool_cap) uint32 ids (UINT32_MAX padding;

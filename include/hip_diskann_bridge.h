@@ -134,6 +134,37 @@ int diskann_hip_robust_prune(void *db, const uint32_t *targets, int m, const uin
  * prunes, [2] back-edges (grouping, appends, prunes).  seconds: 3 doubles. */
 int diskann_hip_build_phase_seconds(void *db, double *seconds);
 
+/* ---- extension: row removal from the device graph ---------------------------------
+ * FreshDiskANN's delete consolidation on the registered fp32 DB and graph, in place of a rebuild of the survivors
+ * (InMemoryIndex::compact, rust_lib/src/index_manager.rs:687-716).  labels: host int64, any order; duplicates and
+ * labels outside [0, n) are ignored.  Only the live rows that point at a removed row are repaired: their pool is
+ * their live neighbours plus the live neighbours of their removed neighbours (one hop), pruned as in the build.
+ * Then the rows and the adjacency are compacted: survivors keep their order, new id = old id − removed rows below
+ * it (the label_map `compact` returns), every stored id is relabelled.  A removed entry point is replaced by the
+ * nearest live row, (Σ(a−b)², id) ascending.
+ * Refused with a message (never a slow path): whatever the build refuses (IP, an SQ8 DB, R > 64, d % 4 != 0,
+ * d > 2048, n >= 2^31, alpha < 1 or NaN), no graph registered, *entry_point >= n, removing every row.  A refused or
+ * failed call leaves the handle answering as before.  No label in range: returns 0 and nothing moves.
+ * scratch_words: pool slots (uint32) the repair may hold at once, 0 = 2^28; the result does not depend on it.
+ * adjacency_out: room for n*R (the old n); the first n'*R words are written.  stats (may be NULL, 8 int64): [0] rows
+ * removed, [1] rows repaired (pruned), [2] pools truncated to 256, [3] live ids gathered into pools, [4] slabs,
+ * [5] 1 when the entry point was replaced, [6] rows the new entry point does not reach, [7] reserved.
+ * Synchronous, on the DB's stream under the DB's mutex.  Returns the rows removed, or -1 (message in err_buf).
+ * Against registering the survivors and a full diskann_hip_build_graph the call was the faster one at every removed
+ * fraction measured (1, 10 and 30 % of 100K x 128 at R 64, L 128 on one MI355X, equal recall@10:
+ * profiles/diskann_remove/README.md), so no fraction is known above which a rebuild is the better call.  Beyond 30 %
+ * removed, and at other shapes, nothing is measured. */
+int64_t diskann_hip_remove_ids(void *db, const int64_t *labels, int64_t n_labels, float alpha, int metric,
+                               uint32_t *entry_point /* in: old id, out: new id */,
+                               int64_t scratch_words /* 0 = default */,
+                               uint32_t *adjacency_out /* n' * R, host, may be NULL */,
+                               int64_t *stats /* 8, may be NULL */, char *err_buf, int err_len);
+
+/* Measurement: seconds of the last diskann_hip_remove_ids on `db`: [0] pool build (host time of mark, rank, pool
+ * lengths and the slab plan, plus the pool fills' device time), [1] the prunes' device time, [2] the rest of the
+ * call (entry point, compaction, copies to the host).  seconds: 3 doubles. */
+int diskann_hip_remove_phase_seconds(void *db, double *seconds);
+
 int64_t diskann_hip_db_size(void *db);
 
 /* Measurement: record HIP events around every id-gather kernel launch of `db` (on its stream) from now
