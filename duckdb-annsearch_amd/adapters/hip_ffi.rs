@@ -131,6 +131,30 @@ extern "C" {
         err_buf: *mut core::ffi::c_char,
         err_len: i32,
     ) -> i64;
+    fn diskann_hip_add_rows(
+        db: *mut core::ffi::c_void,
+        rows: *const f32,
+        m: i64,
+        l_build: i32,
+        alpha: f32,
+        metric: i32,
+        entry_point: u32,
+        batch_max: i32,
+        batch_mates: i32,
+        adjacency_out: *mut u32,
+        stats: *mut i64,
+        err_buf: *mut core::ffi::c_char,
+        err_len: i32,
+    ) -> i64;
+    fn diskann_hip_batch_mates(
+        db: *mut core::ffi::c_void,
+        row0: i64,
+        b: i32,
+        t: i32,
+        out: *mut u32,
+        err_buf: *mut core::ffi::c_char,
+        err_len: i32,
+    ) -> i32;
 }
 
 /// Cached availability: -1 = unchecked, 0 = unavailable, 1 = available (metal_ffi.rs:33-34).
@@ -511,6 +535,77 @@ impl HipDiskDb {
         self.n -= removed as usize;
         adjacency.truncate(self.n * degree);
         Some((adjacency, ep, stats))
+    }
+
+    /// Append `rows_flat` (m × dim) to the DB and insert the rows into its registered graph in place —
+    /// the device counterpart of InMemoryIndex::add's per-row loop (index_manager.rs:262-313) for a chunk of rows.
+    /// The rows get ids n .. n+m−1 in order: the labels `next_label` assigns.  `batch_mates` (0..=64; 16 is the
+    /// measured default) lets the rows of one batch link to each other.  `want_adjacency`: read the whole
+    /// (n+m) × degree adjacency back (u32::MAX padding, for file_format.rs); without it nothing of the graph is
+    /// copied to the host and the vector is empty.  Returns the adjacency and the eight counters of
+    /// hip_diskann_bridge.h; the handle then holds n+m rows.  None ⇒ refused (the handle answers as before) or the
+    /// device failed (the handle has dropped its graph: re-register or rebuild); the caller inserts on the CPU.
+    pub fn add_rows(
+        &mut self,
+        rows_flat: &[f32],
+        l_build: usize,
+        alpha: f32,
+        entry_point: u32,
+        batch_max: usize,
+        batch_mates: usize,
+        want_adjacency: bool,
+    ) -> Option<(Vec<u32>, [i64; 8])> {
+        let degree = self.degree.load(Ordering::Acquire);
+        if degree == 0 || degree > 64 || self.dim == 0 || rows_flat.len() % self.dim != 0 {
+            return None;
+        }
+        if l_build == 0 || l_build > 256 || batch_max == 0 || batch_mates > 64 {
+            return None;
+        }
+        let m = rows_flat.len() / self.dim;
+        let n1 = self.n.checked_add(m)?;
+        let words = if want_adjacency { n1.checked_mul(degree)? } else { 0 };
+        let mut adjacency = vec![u32::MAX; words];
+        let mut stats = [0i64; 8];
+        let mut err = [0 as core::ffi::c_char; 256];
+        let ret = unsafe {
+            diskann_hip_add_rows(
+                self.h,
+                rows_flat.as_ptr(),
+                m as i64,
+                l_build as i32,
+                alpha,
+                0,
+                entry_point,
+                batch_max.min(i32::MAX as usize) as i32,
+                batch_mates as i32,
+                if want_adjacency { adjacency.as_mut_ptr() } else { core::ptr::null_mut() },
+                stats.as_mut_ptr(),
+                err.as_mut_ptr(),
+                err.len() as i32,
+            )
+        };
+        if ret < 0 {
+            return None;  // (refusals and failures both keep n rows)
+        }
+        self.n = n1;
+        Some((adjacency, stats))
+    }
+
+    /// The mates step of add_rows alone over rows row0 .. row0+b−1 (hip_diskann_bridge.h): b × t ids.
+    pub fn batch_mates(&self, row0: usize, b: usize, t: usize) -> Option<Vec<u32>> {
+        if t == 0 || t > 64 || b > i32::MAX as usize || row0.checked_add(b).map_or(true, |e| e > self.n) {
+            return None;
+        }
+        let mut out = vec![u32::MAX; b * t];
+        let mut err = [0 as core::ffi::c_char; 256];
+        let ret = unsafe {
+            diskann_hip_batch_mates(self.h, row0 as i64, b as i32, t as i32, out.as_mut_ptr(), err.as_mut_ptr(), err.len() as i32)
+        };
+        if ret != 0 {
+            return None;
+        }
+        Some(out)
     }
 
     /// prune() of DESIGN §6 for `targets.len()` nodes over `pools` (targets.len() × pool_cap ids, u32::MAX padding).

@@ -52,6 +52,12 @@ void launch_vamana_fill_targets(uint32_t *tg, int b, uint32_t o0, uint32_t ep, h
 void launch_vamana_backedges(uint32_t *adj, int R, const uint32_t *tg, int b, int *cnt, int *slot, uint32_t *touched,
                              int *off, int *fill, uint32_t *src, int *ctr, uint32_t *pool, uint32_t *ptgt, int *pbeg,
                              int *plen, hipStream_t st);
+// diskann_add.hip
+void launch_vamana_batch_mates(const float *xb, int b, int d, uint32_t row0, int T, float *nrm, uint32_t *out,
+                               unsigned long long *written, hipStream_t st);
+void launch_vamana_concat_pool(const int64_t *sid, int K, const uint32_t *mates, int T, int b, uint32_t *pool,
+                               int *pbeg, int *plen, hipStream_t st);
+void launch_vamana_check_finite(const float *x, int64_t count, int *flag, hipStream_t st);
 // diskann_remove.hip
 int64_t diskann_remove_scan_blocks(int64_t n);
 void launch_diskann_remove_mark(const int64_t *labels, int64_t m, int64_t n, uint32_t *bits, uint32_t *wpre,
@@ -367,6 +373,7 @@ struct DiskDB {
     bool adj_host_stale = false;
     double build_s[3] = {0.0, 0.0, 0.0};
     double remove_s[3] = {0.0, 0.0, 0.0};  // the last diskann_hip_remove_ids: pool build, prune, compact
+    double add_s[4] = {0.0, 0.0, 0.0, 0.0};  // the last diskann_hip_add_rows: searches, mates, out-edge prunes, back-edges
     ~DiskDB() {
         if (stream) { DeviceGuard g(device); (void)hipStreamDestroy(stream); }
     }
@@ -1327,6 +1334,14 @@ static void build_shape_check(const DiskDB *db, int R, float alpha, int metric, 
     HIPANN_REQUIRE(alpha >= 1.0f, w + "alpha must be >= 1");  // (a NaN fails the comparison)
 }
 
+// the host copy of the adjacency brought level with the device's (the caller holds db->mu and the device)
+static void refresh_adj_host(DiskDB *db, hipStream_t st) {
+    db->adj_host.resize((size_t)db->n * db->R);
+    HIPANN_CHECK(hipMemcpyAsync(db->adj_host.data(), db->adj_dev.p, db->adj_host.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPANN_CHECK(hipStreamSynchronize(st));
+    db->adj_host_stale = false;
+}
+
 // rows a walk from entry_point over the host adjacency does not reach (rows end at the first UINT32_MAX)
 static int64_t unreached_rows(const std::vector<uint32_t> &a, int64_t n, int R, uint32_t entry_point) {
     std::vector<uint8_t> seen((size_t)n, 0);
@@ -1376,6 +1391,7 @@ int diskann_hip_build_graph(void *h, int R, int l_build, float alpha, int metric
             std::vector<uint32_t> &hst;
             int &R;
             bool keep = false;
+            bool stale0;  // whether the former graph's host copy was behind its device copy (after add_rows)
             void exchange() {
                 swap_buf(db->adj_dev, a);
                 swap_buf(db->dupw, w);
@@ -1384,10 +1400,11 @@ int diskann_hip_build_graph(void *h, int R, int l_build, float alpha, int metric
             }
             ~Slots() {
                 if (!keep) exchange();
-                db->adj_host_stale = false;
+                db->adj_host_stale = keep ? false : stale0;
             }
-        } slots{db, nadj, ndupw, nhost, nR};
+        } slots{db, nadj, ndupw, nhost, nR, false, db->adj_host_stale};
         slots.exchange();
+        db->adj_host_stale = false;
         double secs[3] = {0.0, 0.0, 0.0};
         using clk = std::chrono::steady_clock;
         auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
@@ -1500,6 +1517,256 @@ int diskann_hip_build_phase_seconds(void *h, double *seconds) {
     return 0;
 }
 
+// ---- row insertion into the device graph (kernels in diskann_add.hip and diskann_build.hip) ----
+// `buf` with room for `need` bytes and its first `keep` bytes preserved: in place when the capacity suffices, else
+// a new buffer a quarter larger than the old one (at least `need`) in `grown`, for the caller to swap in.
+static void *grow_keep(DevBuf &buf, DevBuf &grown, size_t need, size_t keep, int dev, hipStream_t st) {
+    if (buf.p && need <= buf.bytes) return buf.p;
+    grown.ensure(std::max(need, buf.bytes + buf.bytes / 4), dev);
+    if (keep) HIPANN_CHECK(hipMemcpyAsync(grown.p, buf.p, keep, hipMemcpyDeviceToDevice, st));
+    return grown.p;
+}
+
+int64_t diskann_hip_add_rows(void *h, const float *rows, int64_t m, int l_build, float alpha, int metric,
+                             uint32_t entry_point, int batch_max, int batch_mates, uint32_t *adjacency_out,
+                             int64_t *stats, char *eb, int el) {
+    try {
+        HIPANN_REQUIRE(h, "add_rows: null db");
+        auto *db = static_cast<DiskDB *>(h);
+        std::lock_guard<std::mutex> lk(db->mu);
+        HIPANN_REQUIRE(db->R > 0, "add_rows: no graph registered (diskann_hip_register_graph / _build_graph)");
+        build_shape_check(db, db->R, alpha, metric, "add_rows");
+        HIPANN_REQUIRE(l_build >= 1 && l_build <= 256, "add_rows: L must be in [1, 256]");
+        HIPANN_REQUIRE(batch_max >= 1, "add_rows: batch_max must be >= 1");
+        HIPANN_REQUIRE(batch_mates >= 0 && batch_mates <= 64, "add_rows: batch_mates must be in [0, 64]");
+        HIPANN_REQUIRE(l_build + batch_mates <= 512, "add_rows: L + batch_mates must be at most 512");
+        HIPANN_REQUIRE((int64_t)entry_point < db->n, "add_rows: entry_point must be below n");
+        HIPANN_REQUIRE(m >= 0 && (m == 0 || rows), "add_rows: null rows");
+        HIPANN_REQUIRE(db->n + m < ((int64_t)1 << 31), "add_rows: n + m must be below 2^31");
+        DeviceGuard g(db->device);
+        const hipStream_t st = db->stream;
+        const int64_t n0 = db->n, n1 = n0 + m;
+        const int R = db->R, d = db->dim, dev = db->device, T = batch_mates, L = l_build;
+        int64_t s8[8] = {0, 0, 0, 0, 0, 0, -1, 0};
+        if (m == 0) {  // nothing moves
+            if (adjacency_out) {
+                if (db->adj_host_stale) refresh_adj_host(db, st);
+                s8[6] = unreached_rows(db->adj_host, n0, R, entry_point);
+                std::memcpy(adjacency_out, db->adj_host.data(), (size_t)n0 * R * 4);
+            }
+            if (stats) std::memcpy(stats, s8, sizeof(s8));
+            return 0;
+        }
+        RoctxRange rr("hipann.diskann.add_rows");
+        using clk = std::chrono::steady_clock;
+        auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
+        double secs[4] = {0.0, 0.0, 0.0, 0.0};
+        const uint32_t ep = entry_point;
+
+        // ---- everything that can refuse or allocate, before anything a search reads changes ----
+        const int bmax = (int)std::min<int64_t>(batch_max, m);
+        const int W = L + T;  // pool slots of an out-edge prune with mates
+        const int64_t pairs = (int64_t)bmax * R;
+        const int64_t rows_max = std::min<int64_t>(pairs, n1);  // rows one batch's back-edges can touch
+        const int64_t pool_words = rows_max * R + pairs;
+        HIPANN_REQUIRE(pairs < INT32_MAX && pool_words < INT32_MAX && (int64_t)bmax * W < INT32_MAX,
+                       "add_rows: batch_max too large");
+        DevBuf sid, sd, tg, cnt, slot, touched, off, fill, src, pool, ptgt, pbeg, plen, ctr, pctr, gram;
+        DevBuf mates, nrm, opool, obeg, olen;
+        sid.ensure((size_t)bmax * L * 8, dev);
+        sd.ensure((size_t)bmax * L * 4, dev);
+        tg.ensure((size_t)bmax * 4, dev);
+        cnt.ensure((size_t)n1 * 4, dev);
+        slot.ensure((size_t)n1 * 4, dev);
+        touched.ensure((size_t)pairs * 4, dev);
+        off.ensure((size_t)pairs * 4, dev);
+        fill.ensure((size_t)pairs * 4, dev);
+        src.ensure((size_t)pairs * 4, dev);
+        pool.ensure((size_t)pool_words * 4, dev);
+        ptgt.ensure((size_t)rows_max * 4, dev);
+        pbeg.ensure((size_t)rows_max * 4, dev);
+        plen.ensure((size_t)rows_max * 4, dev);
+        ctr.ensure(16, dev);
+        pctr.ensure(48, dev);  // [0..3] the prunes' counters, [4] mate ids written, [5] (int) the non-finite flag
+        if (T > 0) {
+            mates.ensure((size_t)bmax * T * 4, dev);
+            nrm.ensure((size_t)bmax * 4, dev);
+            opool.ensure((size_t)bmax * W * 4, dev);
+            obeg.ensure((size_t)bmax * 4, dev);
+            olen.ensure((size_t)bmax * 4, dev);
+        }
+        const int blocks = vamana_prune_blocks(std::max<int64_t>(bmax, rows_max));
+        gram.ensure(vamana_gram_bytes(blocks), dev);
+        {  // the traversal's own scratch at its largest (resident_search_locked sizes it the same way)
+            const int64_t vwords = (n1 + 31) / 32;
+            const int64_t per = std::max<int64_t>(1, std::min<int64_t>(bmax, ((int64_t)2 << 30) / (vwords * 4)));
+            db->visited.ensure((size_t)per * vwords * 4, dev);
+            db->flags.ensure((size_t)bmax * 4, dev);
+            db->bstats.ensure(80, dev);
+            db->eps_dev.ensure(4, dev);
+        }
+        db->adj_host.reserve((size_t)n1 * R);
+        // rows, adjacency and repeated-id bits with room for n1 rows: in place, or grown copies swapped in below
+        DevBuf gdata, gadj, gdupw;
+        const size_t w0 = (size_t)((n0 + 31) / 32), w1 = (size_t)((n1 + 31) / 32);
+        float *x = static_cast<float *>(grow_keep(db->data, gdata, (size_t)n1 * d * 4 + 16, (size_t)n0 * d * 4, dev, st));
+        uint32_t *adj =
+            static_cast<uint32_t *>(grow_keep(db->adj_dev, gadj, (size_t)n1 * R * 4 + 16, (size_t)n0 * R * 4, dev, st));
+        uint32_t *dupw = static_cast<uint32_t *>(grow_keep(db->dupw, gdupw, w1 * 4 + 16, w0 * 4, dev, st));
+        // the tails no search reads yet: the new rows, empty adjacency rows, clear bits (the bits past n0 in word
+        // w0 − 1 are clear already)
+        HIPANN_CHECK(hipMemcpyAsync(x + (size_t)n0 * d, rows, (size_t)m * d * 4, hipMemcpyHostToDevice, st));
+        HIPANN_CHECK(hipMemsetAsync(adj + (size_t)n0 * R, 0xff, (size_t)m * R * 4, st));
+        if (w1 > w0) HIPANN_CHECK(hipMemsetAsync(dupw + w0, 0, (w1 - w0) * 4, st));
+        HIPANN_CHECK(hipMemsetAsync(pctr.p, 0, 48, st));
+        launch_vamana_check_finite(x + (size_t)n0 * d, m * (int64_t)d, pctr.get<int>() + 10, st);
+        int bad = 0;
+        HIPANN_CHECK(hipMemcpyAsync(&bad, pctr.get<int>() + 10, 4, hipMemcpyDeviceToHost, st));
+        HIPANN_CHECK(hipStreamSynchronize(st));
+        HIPANN_REQUIRE(!bad, "add_rows: rows hold a non-finite value");
+
+        // ---- from here on the handle changes; a failure leaves it without a graph (it cannot be rolled back) ----
+        struct Guard {
+            DiskDB *db;
+            int64_t n0;
+            bool armed = true;
+            ~Guard() {
+                if (!armed) return;
+                db->n = n0;
+                db->R = 0;
+                db->adj_host.clear();
+                db->adj_host_stale = false;
+            }
+        } guard{db, n0};
+        if (gdata.p) swap_buf(db->data, gdata);
+        if (gadj.p) swap_buf(db->adj_dev, gadj);
+        if (gdupw.p) swap_buf(db->dupw, gdupw);
+        gdata.release();
+        gadj.release();
+        gdupw.release();
+        const uint32_t eps1[1] = {ep};
+        unsigned long long *pc64 = pctr.get<unsigned long long>();
+        int64_t c = n0;  // rows in the graph
+        while (c < n1) {
+            const int b = (int)std::min<int64_t>(std::min<int64_t>(bmax, c), n1 - c);
+            const int K = (int)std::min<int64_t>(L, c);
+            db->n = c;  // the searches see the graph as it stands at the batch's start
+            // 1. search
+            auto t0 = clk::now();
+            int64_t sst[4] = {0, 0, 0, 0};
+            resident_search_locked(db, eps1, 1, x + (size_t)c * d, b, K, K, kL2, sid.get<int64_t>(), sd.get<float>(), sst,
+                                   st);
+            s8[0] += sst[0];
+            s8[4] += sst[3];
+            secs[0] += since(t0);
+            // 2. mates
+            const bool with_mates = T > 0 && b > 1;
+            if (with_mates) {
+                auto tm = clk::now();
+                launch_vamana_batch_mates(x + (size_t)c * d, b, d, (uint32_t)c, T, nrm.get<float>(),
+                                          mates.get<uint32_t>(), pc64 + 4, st);
+                HIPANN_CHECK(hipStreamSynchronize(st));
+                secs[1] += since(tm);
+            }
+            // 3. out-edges (the targets are rows c .. c + b − 1: insertion order c − 1 + i with the entry point below)
+            auto t1 = clk::now();
+            launch_vamana_fill_targets(tg.get<uint32_t>(), b, (uint32_t)(c - 1), ep, st);
+            if (T == 0) {
+                launch_vamana_prune(x, d, (uint32_t)(c + b), tg.get<uint32_t>(), b, nullptr, nullptr, sid.get<int64_t>(),
+                                    sd.get<float>(), nullptr, nullptr, K, R, alpha, adj, true, gram.get<float>(), blocks,
+                                    pc64 + 2, st);
+            } else {
+                launch_vamana_concat_pool(sid.get<int64_t>(), K, with_mates ? mates.get<uint32_t>() : nullptr, T, b,
+                                          opool.get<uint32_t>(), obeg.get<int>(), olen.get<int>(), st);
+                launch_vamana_prune(x, d, (uint32_t)(c + b), tg.get<uint32_t>(), b, nullptr, opool.get<uint32_t>(),
+                                    nullptr, nullptr, obeg.get<int>(), olen.get<int>(), 0, R, alpha, adj, true,
+                                    gram.get<float>(), blocks, pc64 + 2, st);
+            }
+            HIPANN_CHECK(hipStreamSynchronize(st));
+            secs[2] += since(t1);
+            // 4. back-edges (a target may be a batch row: the stream puts every read of the out-edges before be_merge)
+            auto t2 = clk::now();
+            HIPANN_CHECK(hipMemsetAsync(cnt.p, 0, (size_t)(c + b) * 4, st));
+            HIPANN_CHECK(hipMemsetAsync(ctr.p, 0, 16, st));
+            launch_vamana_backedges(adj, R, tg.get<uint32_t>(), b, cnt.get<int>(), slot.get<int>(),
+                                    touched.get<uint32_t>(), off.get<int>(), fill.get<int>(), src.get<uint32_t>(),
+                                    ctr.get<int>(), pool.get<uint32_t>(), ptgt.get<uint32_t>(), pbeg.get<int>(),
+                                    plen.get<int>(), st);
+            launch_vamana_prune(x, d, (uint32_t)(c + b), ptgt.get<uint32_t>(),
+                                (int)std::min<int64_t>((int64_t)b * R, c + b), ctr.get<int>() + 3, pool.get<uint32_t>(),
+                                nullptr, nullptr, pbeg.get<int>(), plen.get<int>(), 0, R, alpha, adj, true,
+                                gram.get<float>(), blocks, pc64, st);
+            HIPANN_CHECK(hipStreamSynchronize(st));
+            secs[3] += since(t2);
+            db->adj_host_stale = true;
+            s8[1] += 1;
+            s8[2] += b;
+            c += b;
+        }
+        unsigned long long pc[5] = {0, 0, 0, 0, 0};
+        HIPANN_CHECK(hipMemcpyAsync(pc, pctr.p, 40, hipMemcpyDeviceToHost, st));
+        // the repeated-id row bits of all rows (one pass over the adjacency; no pruned or appended row repeats an id)
+        launch_diskann_dup_rows(adj, R, n1, dupw, st);
+        HIPANN_CHECK(hipStreamSynchronize(st));
+        s8[3] = (int64_t)pc[0];
+        s8[5] = (int64_t)(pc[1] + pc[3]);
+        s8[7] = (int64_t)pc[4];
+        db->adj_host.resize((size_t)n1 * R);  // (reserved above: cannot throw)
+        db->n = n1;
+        guard.armed = false;
+        // the host copy stays behind (the next host re-run refreshes it) unless the caller wants the graph
+        if (adjacency_out) {
+            refresh_adj_host(db, st);
+            s8[6] = unreached_rows(db->adj_host, n1, R, ep);
+            std::memcpy(adjacency_out, db->adj_host.data(), (size_t)n1 * R * 4);
+        }
+        if (stats) std::memcpy(stats, s8, sizeof(s8));
+        for (int i = 0; i < 4; ++i) db->add_s[i] = secs[i];
+        return n1;
+    } catch (const std::exception &e) {
+        set_err(eb, el, e.what());
+    } catch (...) {
+        set_err(eb, el, "hipann: unknown error");
+    }
+    return -1;
+}
+
+int diskann_hip_batch_mates(void *h, int64_t row0, int b, int T, uint32_t *out, char *eb, int el) {
+    try {
+        HIPANN_REQUIRE(h, "batch_mates: null db");
+        auto *db = static_cast<DiskDB *>(h);
+        std::lock_guard<std::mutex> lk(db->mu);
+        build_shape_check(db, 1, 1.0f, kL2, "batch_mates");
+        HIPANN_REQUIRE(T >= 1 && T <= 64, "batch_mates: T must be in [1, 64]");
+        HIPANN_REQUIRE(row0 >= 0 && b >= 0 && row0 + b <= db->n, "batch_mates: rows out of range");
+        HIPANN_REQUIRE(b == 0 || out, "batch_mates: null out");
+        if (b == 0) return 0;
+        DeviceGuard g(db->device);
+        const hipStream_t st = db->stream;
+        DevBuf nrm, od;
+        nrm.ensure((size_t)b * 4, db->device);
+        od.ensure((size_t)b * T * 4, db->device);
+        launch_vamana_batch_mates(db->data.get<float>() + (size_t)row0 * db->dim, b, db->dim, (uint32_t)row0, T,
+                                  nrm.get<float>(), od.get<uint32_t>(), nullptr, st);
+        HIPANN_CHECK(hipMemcpyAsync(out, od.p, (size_t)b * T * 4, hipMemcpyDeviceToHost, st));
+        HIPANN_CHECK(hipStreamSynchronize(st));
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(eb, el, e.what());
+    } catch (...) {
+        set_err(eb, el, "hipann: unknown error");
+    }
+    return -1;
+}
+
+int diskann_hip_add_phase_seconds(void *h, double *seconds) {
+    if (!h || !seconds) return -1;
+    auto *db = static_cast<DiskDB *>(h);
+    std::lock_guard<std::mutex> lk(db->mu);
+    for (int i = 0; i < 4; ++i) seconds[i] = db->add_s[i];
+    return 0;
+}
+
 // ---- row removal from the device graph (kernels in diskann_remove.hip) ----
 int64_t diskann_hip_remove_ids(void *h, const int64_t *labels, int64_t n_labels, float alpha, int metric,
                                uint32_t *entry_point, int64_t scratch_words, uint32_t *adjacency_out, int64_t *stats,
@@ -1525,6 +1792,10 @@ int64_t diskann_hip_remove_ids(void *h, const int64_t *labels, int64_t n_labels,
         dead.erase(std::unique(dead.begin(), dead.end()), dead.end());
         const int64_t nd = (int64_t)dead.size(), n2 = n - nd;
         if (nd == 0) {  // nothing moves
+            if (db->adj_host_stale) {  // (add_rows leaves the host copy behind)
+                DeviceGuard g(db->device);
+                refresh_adj_host(db, db->stream);
+            }
             s8[6] = unreached_rows(db->adj_host, n, R, ep);
             if (adjacency_out) std::memcpy(adjacency_out, db->adj_host.data(), (size_t)n * R * 4);
             if (stats) std::memcpy(stats, s8, sizeof(s8));

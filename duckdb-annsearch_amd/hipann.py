@@ -161,6 +161,10 @@ def lib() -> C.CDLL:
             "diskann_hip_remove_ids": ([vp, i64p, i64, C.c_float, i32, C.POINTER(C.c_uint32), i64,
                                         C.POINTER(C.c_uint32), i64p, cp, i32], i64),
             "diskann_hip_remove_phase_seconds": ([vp, C.POINTER(C.c_double)], i32),
+            "diskann_hip_add_rows": ([vp, f, i64, i32, C.c_float, i32, C.c_uint32, i32, i32, C.POINTER(C.c_uint32),
+                                      i64p, cp, i32], i64),
+            "diskann_hip_batch_mates": ([vp, i64, i32, i32, C.POINTER(C.c_uint32), cp, i32], i32),
+            "diskann_hip_add_phase_seconds": ([vp, C.POINTER(C.c_double)], i32),
         }
         missing = [name for name in sig if not hasattr(L, name)]
         if missing:
@@ -845,6 +849,47 @@ class DiskannDeviceDB:
                                     "slabs": int(stats[4]), "entry_replaced": int(stats[5]),
                                     "unreachable": int(stats[6]), "pool_s": sec[0], "prune_s": sec[1],
                                     "compact_s": sec[2]}
+
+    def add_rows(self, rows, entry_point: int, L: int = 128, alpha: float = 1.2, batch_max: int = 4096,
+                 batch_mates: int = 16, metric: int = METRIC_L2, want_adjacency: bool = True):
+        """Append ``rows`` (m, dim) to this fp32 DB and insert them into its registered graph in place (DESIGN §6.3:
+        the build's batches continued, each batch row's ``batch_mates`` nearest batch-mates joined to its prune pool).
+        The rows get ids n .. n+m−1.  Returns (adjacency (n+m, R) uint32, or None without ``want_adjacency`` — then
+        nothing of the graph is copied to the host and stats["unreachable"] is −1 —, stats) and updates self.n."""
+        x = np.ascontiguousarray(rows, np.float32)
+        if x.ndim == 1:
+            x = x.reshape(-1, self.dim)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise HipAnnError(f"add_rows: rows must be (m, {self.dim})")
+        if not 0 <= int(entry_point) < 2 ** 32:
+            raise HipAnnError("add_rows: entry_point must be below n")
+        m, R = x.shape[0], self.R
+        adj = np.empty((self.n + m, R), np.uint32) if want_adjacency and R else None
+        stats = np.zeros(8, np.int64)
+        eb = _err()
+        rc = lib().diskann_hip_add_rows(self._h, _ptr(x, C.c_float) if m else None, m, L, alpha, metric,
+                                        int(entry_point), batch_max, batch_mates, _ptr(adj, C.c_uint32),
+                                        _ptr(stats, C.c_int64), eb, 1024)
+        if rc < 0:
+            self.n = int(lib().diskann_hip_db_size(self._h))
+            raise HipAnnError(eb.value.decode(errors="replace") or "hipann error")
+        self.n = int(lib().diskann_hip_db_size(self._h))
+        sec = (C.c_double * 4)()
+        if lib().diskann_hip_add_phase_seconds(self._h, sec) != 0:
+            raise HipAnnError("diskann_hip_add_phase_seconds failed")
+        return adj, {"search_evals": int(stats[0]), "batches": int(stats[1]), "out_prunes": int(stats[2]),
+                     "back_prunes": int(stats[3]), "host_requeries": int(stats[4]), "pools_truncated": int(stats[5]),
+                     "unreachable": int(stats[6]), "mate_ids": int(stats[7]), "search_s": sec[0], "mates_s": sec[1],
+                     "out_prune_s": sec[2], "back_edge_s": sec[3]}
+
+    def batch_mates(self, row0: int, b: int, T: int) -> np.ndarray:
+        """The mates step of add_rows alone: for each of the rows row0 .. row0+b−1 the ids of its min(T, b−1) nearest
+        other rows of that range, by (distance, id); (b, T) uint32, UINT32_MAX-padded."""
+        out = np.empty((max(int(b), 0), max(int(T), 0)), np.uint32)
+        eb = _err()
+        rc = lib().diskann_hip_batch_mates(self._h, int(row0), int(b), int(T), _ptr(out, C.c_uint32), eb, 1024)
+        _check(rc, eb)
+        return out
 
     def robust_prune(self, targets, pools, R: int, alpha: float = 1.2, metric: int = METRIC_L2) -> np.ndarray:
         """prune() of DESIGN §6 for each target over its row of `pools` (m, pool_cap) uint32 ids (UINT32_MAX padding;

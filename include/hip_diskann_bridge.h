@@ -165,6 +165,49 @@ int64_t diskann_hip_remove_ids(void *db, const int64_t *labels, int64_t n_labels
  * call (entry point, compaction, copies to the host).  seconds: 3 doubles. */
 int diskann_hip_remove_phase_seconds(void *db, double *seconds);
 
+/* ---- extension: row insertion into the device graph ---------------------------------
+ * Appends m fp32 rows (host, m*dim) to the registered DB and inserts them into its registered graph — the device
+ * counterpart of InMemoryIndex::add (rust_lib/src/index_manager.rs:262-313), in place of register_db + build_graph
+ * over all rows.  The rows get ids n .. n+m-1 in order (the labels `next_label` assigns).  Batches follow the build's
+ * rule continued, b = min(batch_max, rows in the graph, rows left); each batch is searched against the graph as it
+ * stood at the batch's start, pruned and back-linked as in the build.  batch_mates = T > 0 adds every batch row's
+ * min(T, b-1) nearest other batch rows to its prune pool, so that a burst of mutually similar rows links to itself
+ * (without it such rows only see the old graph); T = 0 is bit for bit the build's own loop continued.
+ * Refused with a message (never a slow path): whatever the build refuses (IP, an SQ8 DB, d % 4 != 0, d > 2048,
+ * alpha < 1 or NaN), no graph registered, L outside [1, 256], batch_max < 1, batch_mates outside [0, 64],
+ * L + batch_mates > 512, entry_point >= n, rows NULL with m > 0, n + m >= 2^31, a non-finite value in rows.  A refused
+ * call leaves the handle answering as before; m = 0 returns 0 and nothing moves.  A device failure after the first
+ * change cannot be rolled back: the handle keeps its n rows but drops its graph, and searches refuse until a graph is
+ * registered or built again.
+ * Device storage grows by a quarter when it is full (rows, adjacency, repeated-id bits), so repeated small calls are
+ * amortised.  The host copy of the adjacency is not refreshed unless adjacency_out is given ((n+m)*R words, host):
+ * a one-row call copies nothing of the graph back.  stats (may be NULL, 8 int64): [0] search distance evaluations,
+ * [1] batches, [2] out-edge prunes, [3] back-edge prunes, [4] searches re-run on the host, [5] pools truncated to 256,
+ * [6] rows unreachable from entry_point (-1 when adjacency_out is NULL: the walk needs the host copy), [7] mate ids
+ * written.  Synchronous, on the DB's stream under the DB's mutex.  Returns the new n, or -1 (message in err_buf).
+ * Measured against register_db + build_graph over all rows (100K x 128, R 64, L 128, batch_max 4096, 16 mates, one
+ * MI355X, both in one process, adjacency read back; profiles/diskann_add/README.md): 0.09 / 0.21 / 0.46 of the
+ * rebuild's time at 1 / 10 / 30 % added on i.i.d. rows, 0.09 / 0.19 / 0.45 for added rows from new cluster centres,
+ * where recall@10 on queries like the added rows is 1.00 / 1.00 / 0.999 with mates, 0.53 / 0.86 / 0.95 without and
+ * 0.54 / 0.95 / 0.96 for the rebuild.  The mates step is 1 - 5 % of the call (0.45 ms per batch of 4096 against 1.2 ms
+ * of out-edge prunes).  One row into the 100K-row graph: 2.2 ms without adjacency_out, 15 - 21 ms with it.  Other
+ * shapes, and fractions above 30 %, are not measured. */
+int64_t diskann_hip_add_rows(void *db, const float *rows, int64_t m, int l_build, float alpha, int metric,
+                             uint32_t entry_point, int batch_max, int batch_mates,
+                             uint32_t *adjacency_out /* (n+m) * R, host, may be NULL */,
+                             int64_t *stats /* 8, may be NULL */, char *err_buf, int err_len);
+
+/* The mates step of add_rows alone, over the registered rows row0 .. row0+b-1 (fp32 DB, d % 4 == 0, d <= 2048,
+ * 1 <= T <= 64): out[i*T + j] = the id of the j-th nearest other row of the range to row row0+i, ordered by
+ * (max(0, (G_ii + G_jj) - 2 G_ij), id) with G the range's Gram matrix; UINT32_MAX past min(T, b-1).  Host pointer;
+ * synchronous. */
+int diskann_hip_batch_mates(void *db, int64_t row0, int b, int T, uint32_t *out /* b * T */, char *err_buf,
+                            int err_len);
+
+/* Measurement: host seconds of the last diskann_hip_add_rows on `db`, per phase: [0] searches, [1] mates,
+ * [2] out-edge prunes, [3] back-edges.  seconds: 4 doubles. */
+int diskann_hip_add_phase_seconds(void *db, double *seconds);
+
 int64_t diskann_hip_db_size(void *db);
 
 /* Measurement: record HIP events around every id-gather kernel launch of `db` (on its stream) from now
