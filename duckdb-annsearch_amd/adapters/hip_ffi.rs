@@ -11,7 +11,7 @@
 //! (Alternatively keep metal_ffi.rs unchanged and link libhipann.so, which also exports the
 //! `diskann_metal_*` C names.)
 //!
-//! The implementation lives in libhipann.so (duckdb-annsearch_amd/csrc/diskann.hip); its C ABI is
+//! The implementation lives in libhipann.so (duckdb-annsearch_amd/csrc/diskann.hip, diskann_graph.cpp); its C ABI is
 //! include/hip_diskann_bridge.h.  Symbols are resolved at link time when the Rust static lib is
 //! linked with the C++ extension (metal_ffi.rs:5-6, CMakeLists.txt:231-236).
 //!

@@ -14,7 +14,7 @@
 //     them 64 candidates at a time, ordered by (distance, id); the row itself never enters.
 //   No floating-point atomics and no dependence on the block schedule: a row's list is one wave's, fed in column
 //   order.  Exact whenever every partial sum is representable.
-#include "common.hpp"
+#include "diskann_kernels.hpp"
 #include "wave_topk.hpp"
 
 #include <algorithm>
@@ -26,7 +26,6 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr uint32_t kNone = 0xffffffffu;
 constexpr int kKS = 64;        // dims per K-slice
 constexpr int kLD = kKS + 4;   // LDS row stride: rows 16-B aligned, 4 banks of skew
 constexpr int kRB = 32;        // rows per workgroup

@@ -27,7 +27,7 @@
 // form here computes (q − min) − code·a in one fma (L2) and −(Σ(q·a)·code + Σ q·min) (IP): within the
 // bridge tolerance of the reference's dequantise-then-diff order.
 // A query whose spill list overflows (64 boundary ties) is flagged and re-run by the host BFS.
-#include "common.hpp"
+#include "diskann_kernels.hpp"
 
 #include <cfloat>
 #include <cstdint>
@@ -51,7 +51,6 @@ namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-constexpr unsigned kNone = 0xffffffffu;
 constexpr unsigned kExpanded = 0x80000000u;
 #ifndef HIPANN_BFS_BULK
 #define HIPANN_BFS_BULK 6  // admitted candidates from which a step merges them at once (65: never)
@@ -71,11 +70,6 @@ __device__ __forceinline__ float rl_f(float v, int l) {
 __device__ __forceinline__ unsigned rl_u(unsigned v, int l) { return (unsigned)__builtin_amdgcn_readlane((int)v, l); }
 __device__ __forceinline__ uint64_t rl_u64(uint64_t v, int l) {
     return ((uint64_t)rl_u((unsigned)(v >> 32), l) << 32) | rl_u((unsigned)v, l);
-}
-__device__ __forceinline__ float wsum(float s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    return s;
 }
 __device__ __forceinline__ float xshfl(float x, int o);
 // wave minimum of a u64: DPP exchanges inside 16-lane rows, ds_bpermute for the last two levels
@@ -303,7 +297,7 @@ diskann_bfs(const float *__restrict__ Qs, int nq, int d, const uint8_t *__restri
             qp[t][e >> 1][e & 1] = x;
             av[t][e >> 1][e & 1] = y;
         }
-    if (SQ8 && IP) cq = wsum(cq);
+    if (SQ8 && IP) cq = wave_sum(cq);
 
     auto load_row = [&](uint32_t rid, Chunk (&v)[T]) {
         const uint8_t *base = data + (size_t)rid * rowbytes;

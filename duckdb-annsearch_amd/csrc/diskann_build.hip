@@ -22,7 +22,7 @@
 // Back-edges of a batch — count (atomic per target row; integer), offsets, fill, then one wave per touched row:
 // the row's new sources rank-sorted ascending (the order of arrival never shows), appended when the row has room,
 // else row + sources become a pool for vamana_prune.
-#include "common.hpp"
+#include "diskann_kernels.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -34,38 +34,11 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr uint32_t kNone = 0xffffffffu;
 constexpr unsigned long long kBadKey = ~0ull;
 constexpr int kPoolMax = 256;  // pool positions kept (the crate's u16 positions)
 constexpr int kGK = 32;        // dims per MFMA group (16 MFMAs of K = 2 per tile pair)
 // LDS floats of a staged K-slice: 256 rows × (64 + 4) or 128 rows × (128 + 4); rows 16-B aligned, 4 banks of skew
 constexpr int kTileFloats = kPoolMax * (64 + 4);
-
-struct PruneArgs {
-    const float *x;
-    int d;
-    uint32_t n;
-    const uint32_t *targets;
-    const int *m_ptr;  // the target count on the device (nullptr: m)
-    int m;
-    const uint32_t *pool32;  // pool ids, or ...
-    const int64_t *pool64;   // ... the traversal's labels (−1 = empty)
-    const float *pool_d;     // distances to the target (nullptr: computed here)
-    const int *pool_beg, *pool_len;  // per target (nullptr: target t owns [t·pool_cap, (t+1)·pool_cap))
-    int pool_cap;
-    int R;
-    float alpha;
-    uint32_t *out;
-    int out_by_target;  // rows of `out` indexed by the target's id (the adjacency) instead of its position
-    float *gram;        // gridDim.x × 256² floats
-    unsigned long long *counters;  // [0] += targets, [1] += pools truncated to 256 (nullptr: none)
-};
-
-__device__ __forceinline__ float wave_sum_f(float s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
 
 // a word another wave of this workgroup (or this wave's other lanes) stored earlier in the launch: past this CU's L1
 __device__ __forceinline__ float load_l2(const float *p) {
@@ -136,7 +109,7 @@ __global__ void __launch_bounds__(256) vamana_prune(PruneArgs a) {
                     }
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
-                        const float r = wave_sum_f(s[u]);
+                        const float r = wave_sum(s[u]);
                         if (lane == j0 + u) dist = r;
                     }
                 }
@@ -426,18 +399,10 @@ __global__ void __launch_bounds__(256) be_merge(uint32_t *adj, int R, const uint
 int vamana_prune_blocks(int64_t m) { return (int)(m < 1 ? 1 : m > 512 ? 512 : m); }
 size_t vamana_gram_bytes(int blocks) { return (size_t)blocks * kPoolMax * kPoolMax * sizeof(float); }
 
-void launch_vamana_prune(const float *x, int d, uint32_t n, const uint32_t *targets, int m, const int *m_ptr,
-                         const uint32_t *pool32, const int64_t *pool64, const float *pool_d, const int *pool_beg,
-                         const int *pool_len, int pool_cap, int R, float alpha, uint32_t *out, bool out_by_target,
-                         float *gram, int blocks, unsigned long long *counters, hipStream_t st) {
-    if (m <= 0) return;  // (m: the count, or its upper bound when m_ptr holds the count)
-    HIPANN_REQUIRE(d > 0 && d % 4 == 0 && R >= 1 && R <= 64 && blocks >= 1, "vamana_prune: unsupported shape");
-    PruneArgs a;
-    a.x = x; a.d = d; a.n = n; a.targets = targets; a.m_ptr = m_ptr; a.m = m;
-    a.pool32 = pool32; a.pool64 = pool64; a.pool_d = pool_d; a.pool_beg = pool_beg; a.pool_len = pool_len;
-    a.pool_cap = pool_cap; a.R = R; a.alpha = alpha; a.out = out; a.out_by_target = out_by_target ? 1 : 0;
-    a.gram = gram; a.counters = counters;
-    hipLaunchKernelGGL(vamana_prune, dim3((unsigned)std::min(blocks, m)), dim3(256), 0, st, a);
+void launch_vamana_prune(const PruneArgs &a, int blocks, hipStream_t st) {
+    if (a.m <= 0) return;
+    HIPANN_REQUIRE(a.d > 0 && a.d % 4 == 0 && a.R >= 1 && a.R <= 64 && blocks >= 1, "vamana_prune: unsupported shape");
+    hipLaunchKernelGGL(vamana_prune, dim3((unsigned)std::min(blocks, a.m)), dim3(256), 0, st, a);
     HIPANN_CHECK(hipGetLastError());
 }
 

@@ -1,0 +1,72 @@
+// diskann_db.hpp — (internal) what diskann.hip (bridge, host BFS, DB registry, resident search) and diskann_graph.cpp
+// (graph build, add, remove, prune) share on the host: the HBM-resident DB, the resident search, and the C ABI's
+// error epilogue.
+#pragma once
+#include "../../include/hip_diskann_bridge.h"
+#include "common.hpp"
+#include "runtime.hpp"
+
+#include <cstring>
+#include <exception>
+
+namespace hipann {
+
+struct DiskDB {
+    int device = 0;
+    int64_t n = 0;
+    int dim = 0;
+    int fmt = DISKANN_HIP_FMT_F32;
+    DevBuf data;  // fp32 rows or u8 codes
+    DevBuf ab;    // float2 per dim (SQ8): (scale/255, min), the traversal's fused decode
+    DevBuf ab_raw;  // float2 per dim (SQ8): (scale, min), the id-gather kernels' exact decode
+    hipStream_t stream = nullptr;
+    std::mutex mu;
+    DevBuf q, ids, m, out;
+    HostBuf hids, hm, hout;
+    KernelTimer timer;
+    // resident graph + BFS scratch (diskann_hip_register_graph / _search_batch_resident)
+    int R = 0;
+    DevBuf adj_dev, dupw, visited, flags, bstats, eps_dev;
+    DevBuf vbits;  // host BFS: the queries' visited bits on the device (one bit per row and query)
+    DevBuf bfs_ctr;   // host BFS: per group, the id-gather launch's finished-block count (zero between launches)
+    HostBuf bfs_tok;  // host BFS: per group, the token word the launch posts when it is done (polled)
+    unsigned bfs_seq = 0;
+    std::vector<uint32_t> adj_host;
+    // diskann_hip_build_graph: adj_dev is ahead of adj_host (the resident search refreshes the host copy before it
+    // re-runs a flagged query on it); the last build's seconds in search / out-edge prunes / back-edges
+    bool adj_host_stale = false;
+    double build_s[3] = {0.0, 0.0, 0.0};
+    double remove_s[3] = {0.0, 0.0, 0.0};  // the last diskann_hip_remove_ids: pool build, prune, compact
+    double add_s[4] = {0.0, 0.0, 0.0, 0.0};  // the last diskann_hip_add_rows: searches, mates, out-edge prunes, back-edges
+    ~DiskDB() {
+        if (stream) { DeviceGuard g(device); (void)hipStreamDestroy(stream); }
+    }
+};
+
+// Resident search: queries / outputs in HBM, asynchronous launch on `st`, then a wait for the per-query flags (the
+// rare flagged queries and unsupported shapes go through the host BFS).  The caller holds db->mu and the device; the
+// graph build and add_rows search their own frozen graph through this.
+void resident_search_locked(DiskDB *db, const uint32_t *eps, int n_ep, const float *queries_dev, int nq, int k,
+                            int l_search, int metric, int64_t *out_ids_dev, float *out_d_dev, int64_t *stats,
+                            hipStream_t st);
+
+inline void set_err(char *buf, int len, const char *msg) {
+    if (!buf || len <= 0) return;
+    std::strncpy(buf, msg, (size_t)len - 1);
+    buf[len - 1] = '\0';
+}
+
+// The epilogue of a C entry point with an error buffer: the body's value, or −1 with the exception's text in (eb, el).
+template <typename F>
+auto abi_call(char *eb, int el, F &&body) -> decltype(body()) {
+    try {
+        return body();
+    } catch (const std::exception &e) {
+        set_err(eb, el, e.what());
+    } catch (...) {
+        set_err(eb, el, "hipann: unknown error");
+    }
+    return -1;
+}
+
+}  // namespace hipann

@@ -17,7 +17,7 @@
 //   rm_compact_adj   one wave per surviving row: the repaired row written at its new position, every id replaced by
 //                    its rank; slots past the first UINT32_MAX become UINT32_MAX
 // No floating-point atomics: every result is the same from run to run.
-#include "common.hpp"
+#include "diskann_kernels.hpp"
 
 #include <algorithm>
 #include <cstdint>
@@ -25,7 +25,6 @@
 namespace hipann {
 namespace {
 
-constexpr uint32_t kNone = 0xffffffffu;
 constexpr int kScanThreads = 256;
 constexpr int kScanPer = 4;                          // bitmap words per thread of the prefix kernels
 constexpr int kScanWords = kScanThreads * kScanPer;  // words per block
@@ -175,12 +174,6 @@ __global__ void __launch_bounds__(256) rm_pool_fill(const uint32_t *__restrict__
     }
 }
 
-__device__ __forceinline__ float wave_sum_f(float s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
-
 __global__ void __launch_bounds__(256) rm_nearest_live(const float *__restrict__ x, int d, int64_t n,
                                                        const uint32_t *__restrict__ bits, uint32_t ep,
                                                        unsigned long long *best) {
@@ -199,7 +192,7 @@ __global__ void __launch_bounds__(256) rm_nearest_live(const float *__restrict__
             w = p4.z - c4.z; s = fmaf(w, w, s);
             w = p4.w - c4.w; s = fmaf(w, w, s);
         }
-        s = wave_sum_f(s);
+        s = wave_sum(s);
         const unsigned long long key = ((unsigned long long)__float_as_uint(s) << 32) | (uint32_t)row;
         mine = key < mine ? key : mine;
     }

@@ -110,6 +110,23 @@ def test_build_exact(gpu, oracle, case):
         assert st["host_requeries"] > 0, "the input no longer overflows the spill list: the host re-run went untested"
 
 
+@pytest.mark.parametrize("ep", [137, 299])
+def test_build_exact_entry_point_gap(gpu, ep):
+    """The entry point inside the insertion order: a batch's rows are searched in two segments around it.  Row 137 falls
+    inside the 64-row batch of insertion orders 127..190 (both segments non-empty); row 299 is the last row (the second
+    segment always empty).  With entry_point=0, as in test_build_exact, the first segment never runs."""
+    x = np.random.default_rng(77).integers(-8, 9, (300, 16)).astype(np.float32)
+    db = gpu.DiskannDeviceDB(x)
+    adj, st = db.build_graph(R=8, L=16, alpha=1.2, entry_point=ep, batch_max=64)
+    db.close()
+    print(ep, st)
+    ref, counts = V.build(x, 8, 16, 1.2, ep, 64)
+    assert np.array_equal(adj, ref), np.nonzero((adj != ref).any(axis=1))[0][:10]
+    assert (st["batches"], st["out_prunes"], st["back_prunes"], st["pools_truncated"]) == \
+        (counts["batches"], counts["out_prunes"], counts["back_prunes"], counts["pools_truncated"])
+    assert st["unreachable"] == int((~V.reachable(ref, ep)).sum())
+
+
 def recall_resident(db, x, oracle, q, L, ep):
     ids, _, _ = db.search_batch_resident([ep], q, 10, L)
     _, truth = oracle.flat_search(x, q, 10)
