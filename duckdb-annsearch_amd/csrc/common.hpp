@@ -70,6 +70,9 @@ constexpr int kRerankK = 16, kRerankMaxK = 12;
 // request_k in (kRerankMaxK, kIvfSubMaxK] on the IVF exact forms: sub-list slots (one 16-list per scan wave) and a
 // rerank filter of min(64, max(kout + 4, 2·kout)) candidates (ivf.cpp); above: the 3-term scan
 constexpr int kIvfSubMaxK = 60;
+// The seeded int8 scan (ivf.cpp): the chunk-0 items' sub-lists are reduced to the kSeedK best per query
+// (ivf_seed_bound), whose kSeedK-th key gates the other chunks' items.
+constexpr int kSeedK = 64;
 // Flat exact form, IP: 32 candidates per (split, query).  At 10M × 768 (U(-1,1) rows) 16 left ≈0.2% of
 // the IP queries failing the bound (each a re-scan of the shard: 61 → 67 ms per batch), 32 none (65 ms);
 // L2 had no failures at 16, and 32 costs it 60 → 66 ms (the fuller epilogue lists), so L2 keeps 16.
@@ -115,6 +118,34 @@ __host__ __device__ inline int ivf_ngroups(int c, int group) {
 __host__ __device__ inline int ivf_group_min(int group) {
     return ivf_group_narrow(group) > 0 ? ivf_group_narrow(group) : ivf_group_wide(group);
 }
+
+// The item order of the fp16 / int8 image scans' launches.  Phase 0: every item, list l's at item_off[l], (row chunk,
+// query group) with the group fastest.  The seeded int8 scan runs the same items in two launches: phase 1 the chunk-0
+// items, list l's ng(l) at goff[l] = Σ_{l' < l} ng(l'); phase 2 the others, list l's at item_off[l] − goff[l], chunk 1's
+// groups first.
+__host__ __device__ inline int ivf_phase_first(int phase, int item_off_l, int goff_l) {
+    return phase == 1 ? goff_l : phase == 2 ? item_off_l - goff_l : item_off_l;
+}
+// the list of a launch's item: the last l < nlist whose first item is <= item (item < the launch's total)
+__host__ __device__ inline int ivf_phase_list(int phase, const int *item_off, const int *goff, int nlist, int item) {
+    int lo = 0, hi = nlist - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (ivf_phase_first(phase, item_off[mid], phase ? goff[mid] : 0) <= item) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// rem = the item's index among its list's items of the launch, ng = the list's query groups
+__host__ __device__ inline void ivf_phase_decode(int phase, int rem, int ng, int &chunk, int &grp) {
+    chunk = phase == 1 ? 0 : rem / ng + (phase == 2 ? 1 : 0);
+    grp = phase == 1 ? rem : rem % ng;
+}
+// A query's candidates after the seeded scan, in slots of kslot entries (one 16-list per scan wave): query q owns the
+// slots from slot_off[q·nprobe] + q on — one whose last kSeedK entries are its seed list, then nch − 1 per pair (the
+// chunks >= 1 of the pair's list), so the candidates are one contiguous run that starts kslot − kSeedK entries into
+// the first slot.
+__host__ __device__ inline int64_t ivf_seed_run_slot(int slot0, int64_t q) { return (int64_t)slot0 + q; }
+__host__ __device__ inline int ivf_seed_pair_slots(int nch) { return nch > 1 ? nch - 1 : 0; }
 
 // XCD-aware block remap (cdna_hip_programming.md §5.5 T1, bijective form): blocks b and b+8 are
 // dealt to the same XCD; map so that each XCD receives a contiguous run of logical blocks.

@@ -469,6 +469,15 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
         ix.last_kfilt = exact ? kfilt : 0;
         ix.last_sublists = sub ? ivf_scan_sublists() : 0;
     }
+    // The seeded int8 scan: the chunk-0 items first, every wave's list a sub-list of the pair's slot;
+    // then the 64 best of a query's chunk-0 entries, whose 64th key is min'ed into the query's bound
+    // (ivf_seed_bound); then the other items under that bound, sub-lists again (so the rerank's bound B — the 64th
+    // candidate key or the smallest full sub-list's 16th — is the single launch's).  Needs the per-row
+    // certificate's lower-bound keys (int8 image, L2), a list of more than one chunk, and chunk-0 entries the seed
+    // kernel's select holds.  HIPANN_IVF_SEED=0 (A/B): the single launch.
+    static const bool seed_env = [] { const char *e = std::getenv("HIPANN_IVF_SEED"); return !e || std::atoi(e) != 0; }();
+    const bool seeded = seed_env && i8 && metric == kL2 && sub && sh.max_nch > 1 && ivf_seed_supported(np, kslot);
+    if (form_override < 0) ix.last_seeded = seeded ? 1 : 0;
     const bool tiled = form == kFormDecomposed || ivf_form_split(form);  // the matrix-core scans
     const int group = i8 ? ivf_mfma_i8_group(d) : half ? ivf_mfma_h_group(d) : ivf_group_size(form, d);
     float xmax2 = 0.f;
@@ -552,6 +561,7 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
     sh.cnt.ensure(sizeof(int) * (nlist + 1), sh.device);
     sh.bucket_off.ensure(sizeof(int) * (nlist + 1), sh.device);
     sh.item_off.ensure(sizeof(int) * (nlist + 1), sh.device);
+    sh.goff.ensure(sizeof(int) * (nlist + 1), sh.device);
     sh.bucket.ensure(sizeof(int) * (size_t)nq * np, sh.device);
     HIPANN_REQUIRE((int64_t)nq * np < (int64_t)0x7fffffff, "nq * nprobe too large");
     sh.slot_off.ensure(sizeof(int) * ((size_t)nq * np + 1), sh.device);
@@ -560,16 +570,19 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
     launch_ivf_plan(sh.coarse_i.get<int64_t>(), nq, np, sh.list_len.get<int>(), nlist, group, sh.cnt.get<int>(),
                     sh.bucket_off.get<int>(), sh.item_off.get<int>(), cur_cur, sh.bucket.get<int>(),
                     sh.slot_off.get<int>(), st, exact ? sh.nflag.get<int>() : nullptr, qbound, ccnt_cur,
-                    sh.qtot.get<int>(), hook.done, ccnt_next, cur_next);
+                    sh.qtot.get<int>(), hook.done, ccnt_next, cur_next, sh.goff.get<int>());
     }
     sh.plan_batch++;
     ccnt_reset.armed = false;
     // 3. scan: one k-list per (query, probe, row chunk) slot — every slot is written by exactly one item
-    const size_t parts = (size_t)np * nq * sh.max_nch * kslot;
+    // (the seeded scan: the pairs' chunk-0 slots, then the queries' candidate slots — one more per query, see below)
+    const size_t parts = ((size_t)np * nq * sh.max_nch + (seeded ? (size_t)np * nq + (size_t)nq : 0)) * kslot;
     HIPANN_REQUIRE((int64_t)np * nq * sh.max_nch < (int64_t)0x7fffffff, "too many partial lists");
     sh.part_d.ensure(parts * sizeof(float), sh.device);
     sh.part_i.ensure(parts * sizeof(int), sh.device);
     const int64_t max_items = ivf_max_items(nq, np, nlist, sh.max_nch, sh.n, group);
+    float *cand_d = nullptr;  // the seeded scan: the queries' candidate runs (inside part_d / part_i)
+    int *cand_i = nullptr;
     const float *qn = nullptr;
     if (form != kFormDirect && metric == kL2) {
         const FlatShard &qs = *sh.quant->shards[0];
@@ -597,14 +610,32 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
         if (img) {
             // (int8: its query units, scales and residuals in the fp16 form's slots; L2: ‖q̂‖² of the dequantised
             // queries as the key's query term)
-            launch_ivf_scan_mfma_h(nq, i8 ? sh.qi8.p : sh.hsplit.p, i8 ? sh.qs8.get<float>() : sh.hits.get<float>(),
-                                   i8 ? sh.qres8.get<float>() : sh.hres.get<float>(), cert8 ? sh.qhn2.get<float>() : qn, d,
-                                   metric, i8 ? sh.codes_i8.p : sh.codes_h.p, sh.tpass_off.get<int64_t>(), sh.xnorm.get<float>(),
-                                   sh.list_off.get<int64_t>(), sh.list_len.get<int>(), sh.cnt.get<int>(), sh.bucket_off.get<int>(),
-                                   sh.item_off.get<int>(), sh.bucket.get<int>(), sh.slot_off.get<int>(), nlist, np, k,
-                                   max_items, qbound, sh.part_d.get<float>(), sh.part_i.get<int>(), st, sub ? 1 : 0,
-                                   i8 ? 1 : 0, i8 ? sh.xs8.get<float>() : nullptr,
-                                   cert8 ? sh.xr8.get<float>() : nullptr, cert8 ? sh.qhn.get<float>() : nullptr);
+            auto scan_h = [&](int phase, const int *slots, int64_t items, float *pd, int *pi, int subl) {
+                launch_ivf_scan_mfma_h(nq, i8 ? sh.qi8.p : sh.hsplit.p, i8 ? sh.qs8.get<float>() : sh.hits.get<float>(),
+                                       i8 ? sh.qres8.get<float>() : sh.hres.get<float>(), cert8 ? sh.qhn2.get<float>() : qn, d,
+                                       metric, i8 ? sh.codes_i8.p : sh.codes_h.p, sh.tpass_off.get<int64_t>(), sh.xnorm.get<float>(),
+                                       sh.list_off.get<int64_t>(), sh.list_len.get<int>(), sh.cnt.get<int>(), sh.bucket_off.get<int>(),
+                                       sh.item_off.get<int>(), sh.bucket.get<int>(), slots, nlist, np, k,
+                                       items, qbound, pd, pi, st, subl,
+                                       i8 ? 1 : 0, i8 ? sh.xs8.get<float>() : nullptr,
+                                       cert8 ? sh.xr8.get<float>() : nullptr, cert8 ? sh.qhn.get<float>() : nullptr, phase,
+                                       sh.goff.get<int>());
+            };
+            if (seeded) {
+                // the chunk-0 slots (one per pair) take the head of part_d / part_i, the queries' candidate slots
+                // (common.hpp ivf_seed_run_slot) the rest
+                HIPANN_REQUIRE((int64_t)np * nq * sh.max_nch + nq < (int64_t)0x7fffffff, "too many candidate slots");
+                sh.cslot.ensure(sizeof(int) * (size_t)nq * np, sh.device);
+                sh.bcnt.ensure(sizeof(int) * (size_t)nq, sh.device);
+                cand_d = sh.part_d.get<float>() + (size_t)np * nq * kslot;
+                cand_i = sh.part_i.get<int>() + (size_t)np * nq * kslot;
+                scan_h(1, nullptr, ivf_max_items(nq, np, nlist, 1, 0, group), sh.part_d.get<float>(), sh.part_i.get<int>(), 1);
+                launch_ivf_seed_bound(sh.part_d.get<float>(), sh.part_i.get<int>(), sh.slot_off.get<int>(), np, nq, kslot,
+                                      sh.n, qbound, cand_d, cand_i, sh.cslot.get<int>(), sh.bcnt.get<int>(), st);
+                scan_h(2, sh.cslot.get<int>(), ivf_max_items(nq, np, nlist, sh.max_nch - 1, sh.n, group), cand_d, cand_i, 1);
+            } else {
+                scan_h(0, sh.slot_off.get<int>(), max_items, sh.part_d.get<float>(), sh.part_i.get<int>(), sub ? 1 : 0);
+            }
         }
         else if (bigk)
             launch_ivf_scan_bigk(xq, d, metric, sh.codes, sh.list_off.get<int64_t>(), sh.list_len.get<int>(),
@@ -666,14 +697,16 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
     {
         RoctxRange rr("hipann.ivf.rerank");
         ScopedTiming t(ix.timer_merge, st);
-        launch_ivf_rerank(sh.part_d.get<float>(), sh.part_i.get<int>(), sh.slot_off.get<int>(), np, nq, kfilt, kout,
+        launch_ivf_rerank(seeded ? cand_d : sh.part_d.get<float>(), seeded ? cand_i : sh.part_i.get<int>(),
+                          sh.slot_off.get<int>(), np, nq, kfilt, kout,
                           metric, xq, sh.codes, d, sh.ids, sh.n, 0, xmax2, D, I, sh.nflag.get<int>(),
                           sh.flagged.get<int>(), st, kSplit2Eps, i8 ? rxmax8 : half ? sh.half_rxmax : -1.f,
                           i8 ? sh.qres8.get<float>() : half ? sh.hres.get<float>() : nullptr, sh.coarse_i.get<int64_t>(),
                           sh.list_off.get<int64_t>(), nlist, qbound, img && metric == kL2 ? qn : nullptr, kslot,
                           sub ? 1 : 0, inline_fb ? sh.list_len.get<int>() : nullptr,
                           inline_fb ? sh.fpd.get<float>() : nullptr, inline_fb ? sh.fpi.get<long long>() : nullptr,
-                          inline_fb ? sh.fb_total.get<unsigned long long>() : nullptr, fb_cap, cert8 ? 1 : 0);
+                          inline_fb ? sh.fb_total.get<unsigned long long>() : nullptr, fb_cap, cert8 ? 1 : 0,
+                          seeded ? sh.bcnt.get<int>() : nullptr);
         if (fb_cap > 0)
             launch_ivf_fallback_chunks(sh.nflag.get<int>(), sh.flagged.get<int>(), fb_cap, np, fb_maxch, ivf_chunk_rows(),
                                        kout, metric, xq, sh.codes, d, sh.ids, 0, sh.coarse_i.get<int64_t>(),
@@ -1560,6 +1593,13 @@ int hipann_ivf_last_filter_image(void *h) {
     auto *ix = static_cast<IndexBase *>(h);
     if (ix->kind != Kind::IVF) return -1;
     return static_cast<IvfIndex *>(ix)->last_filter_image;
+}
+
+int hipann_ivf_last_seeded(void *h) {
+    if (!h) return -1;
+    auto *ix = static_cast<IndexBase *>(h);
+    if (ix->kind != Kind::IVF) return -1;
+    return static_cast<IvfIndex *>(ix)->last_seeded;
 }
 
 int64_t hipann_ivf_i8_passes_tiled(void *h) {

@@ -53,36 +53,45 @@ __global__ void ivf_count(const int64_t *__restrict__ probes, int64_t npairs, co
 // (query group, row chunk) of each list); cursor[l] = 0; total items in item_off[nlist].
 __global__ void __launch_bounds__(1024) ivf_plan(const int *__restrict__ cnt, const int *__restrict__ list_len,
                                                  int nlist, int group, int *__restrict__ bucket_off,
-                                                 int *__restrict__ item_off, int *__restrict__ cursor) {
-    __shared__ int sb[1024], si[1024];
-    __shared__ int carry_b, carry_i;
-    if (threadIdx.x == 0) { carry_b = 0; carry_i = 0; }
+                                                 int *__restrict__ item_off, int *__restrict__ cursor,
+                                                 int *__restrict__ goff) {
+    __shared__ int sb[1024], si[1024], sg[1024];
+    __shared__ int carry_b, carry_i, carry_g;
+    if (threadIdx.x == 0) { carry_b = 0; carry_i = 0; carry_g = 0; }
     __syncthreads();
     for (int base = 0; base < nlist; base += 1024) {
         const int l = base + threadIdx.x;
         const int c = l < nlist ? cnt[l] : 0;
-        const int items = l < nlist ? ivf_ngroups(c, group) * ivf_nch(list_len[l]) : 0;
+        const int groups = l < nlist ? ivf_ngroups(c, group) : 0;
+        const int items = l < nlist ? groups * ivf_nch(list_len[l]) : 0;
         sb[threadIdx.x] = c;
         si[threadIdx.x] = items;
+        sg[threadIdx.x] = groups;
         __syncthreads();
         for (int o = 1; o < 1024; o <<= 1) {  // Hillis-Steele inclusive scan
-            int vb = 0, vi = 0;
-            if ((int)threadIdx.x >= o) { vb = sb[threadIdx.x - o]; vi = si[threadIdx.x - o]; }
+            int vb = 0, vi = 0, vg = 0;
+            if ((int)threadIdx.x >= o) { vb = sb[threadIdx.x - o]; vi = si[threadIdx.x - o]; vg = sg[threadIdx.x - o]; }
             __syncthreads();
             sb[threadIdx.x] += vb;
             si[threadIdx.x] += vi;
+            sg[threadIdx.x] += vg;
             __syncthreads();
         }
         if (l < nlist) {
             bucket_off[l] = carry_b + sb[threadIdx.x] - c;
             item_off[l] = carry_i + si[threadIdx.x] - items;
+            if (goff) goff[l] = carry_g + sg[threadIdx.x] - groups;
             cursor[l] = 0;
         }
         __syncthreads();
-        if (threadIdx.x == 1023) { carry_b += sb[1023]; carry_i += si[1023]; }
+        if (threadIdx.x == 1023) { carry_b += sb[1023]; carry_i += si[1023]; carry_g += sg[1023]; }
         __syncthreads();
     }
-    if (threadIdx.x == 0) { bucket_off[nlist] = carry_b; item_off[nlist] = carry_i; }
+    if (threadIdx.x == 0) {
+        bucket_off[nlist] = carry_b;
+        item_off[nlist] = carry_i;
+        if (goff) goff[nlist] = carry_g;
+    }
 }
 
 __global__ void ivf_fill(const int64_t *__restrict__ probes, int64_t npairs, const int *__restrict__ list_len,
@@ -203,11 +212,11 @@ __global__ void __launch_bounds__(1024) ivf_plan_q(int *__restrict__ ccnt, const
                                                    int *__restrict__ item_off, int *__restrict__ cursor,
                                                    int *__restrict__ qtot, int64_t nq, int64_t npairs,
                                                    int *__restrict__ slot_off, int *__restrict__ nflag_reset,
-                                                   unsigned *__restrict__ qbound) {
-    __shared__ int sb[1024], si[1024];
-    __shared__ int carry_b, carry_i;
+                                                   unsigned *__restrict__ qbound, int *__restrict__ goff) {
+    __shared__ int sb[1024], si[1024], sg[1024];
+    __shared__ int carry_b, carry_i, carry_g;
     const int tid = threadIdx.x;
-    if (tid == 0) { carry_b = 0; carry_i = 0; }
+    if (tid == 0) { carry_b = 0; carry_i = 0; carry_g = 0; }
     if (nflag_reset && tid == 0) *nflag_reset = 0;
     if (qbound)
         for (int64_t q = tid; q < nq; q += 1024) qbound[q] = 0xff800000u;
@@ -217,22 +226,26 @@ __global__ void __launch_bounds__(1024) ivf_plan_q(int *__restrict__ ccnt, const
         int c = 0;
         if (l < nlist)
             for (int cp = 0; cp < kPlanCopies; ++cp) c += ccnt[(int64_t)cp * nlist + l];
-        const int items = l < nlist ? ivf_ngroups(c, group) * ivf_nch(list_len[l]) : 0;
+        const int groups = l < nlist ? ivf_ngroups(c, group) : 0;
+        const int items = l < nlist ? groups * ivf_nch(list_len[l]) : 0;
         sb[tid] = c;
         si[tid] = items;
+        sg[tid] = groups;
         __syncthreads();
         for (int o = 1; o < 1024; o <<= 1) {  // Hillis-Steele inclusive scan
-            int vb = 0, vi = 0;
-            if (tid >= o) { vb = sb[tid - o]; vi = si[tid - o]; }
+            int vb = 0, vi = 0, vg = 0;
+            if (tid >= o) { vb = sb[tid - o]; vi = si[tid - o]; vg = sg[tid - o]; }
             __syncthreads();
             sb[tid] += vb;
             si[tid] += vi;
+            sg[tid] += vg;
             __syncthreads();
         }
         if (l < nlist) {
             cnt[l] = c;
             bucket_off[l] = carry_b + sb[tid] - c;
             item_off[l] = carry_i + si[tid] - items;
+            if (goff) goff[l] = carry_g + sg[tid] - groups;
             int pre = 0;  // copy cp's fills start after copies 0..cp-1 (ivf_fill_q adds to its copy's cursor)
             for (int cp = 0; cp < kPlanCopies; ++cp) {
                 const int64_t e = (int64_t)cp * nlist + l;
@@ -243,10 +256,14 @@ __global__ void __launch_bounds__(1024) ivf_plan_q(int *__restrict__ ccnt, const
             }
         }
         __syncthreads();
-        if (tid == 1023) { carry_b += sb[1023]; carry_i += si[1023]; }
+        if (tid == 1023) { carry_b += sb[1023]; carry_i += si[1023]; carry_g += sg[1023]; }
         __syncthreads();
     }
-    if (tid == 0) { bucket_off[nlist] = carry_b; item_off[nlist] = carry_i; }
+    if (tid == 0) {
+        bucket_off[nlist] = carry_b;
+        item_off[nlist] = carry_i;
+        if (goff) goff[nlist] = carry_g;
+    }
     // query slot bases: exclusive scan of qtot, in place
     __syncthreads();
     if (tid == 0) carry_b = 0;
@@ -320,25 +337,30 @@ __global__ void __launch_bounds__(256) ivf_planfill_q(const int64_t *__restrict_
                                                       const int *__restrict__ qtot, int *__restrict__ slot_off,
                                                       int64_t npairs, int *__restrict__ cnt, int *__restrict__ bucket_off,
                                                       int *__restrict__ item_off, int *__restrict__ bucket,
-                                                      int *__restrict__ nflag_reset, unsigned *__restrict__ qbound) {
+                                                      int *__restrict__ nflag_reset, unsigned *__restrict__ qbound,
+                                                      int *__restrict__ goff) {
     __shared__ int s_boff[kPlanFillMaxList];
     __shared__ int s_w[4], s_qb[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t q0 = (int64_t)blockIdx.x * 4;
     // list bucket offsets: thread t owns lists [t·per, (t+1)·per)
     const int per = (nlist + 255) / 256;
-    int sum = 0, isum = 0;
+    int sum = 0, isum = 0, gsum = 0;
     for (int j = 0; j < per; ++j) {
         const int l = tid * per + j;
         if (l < nlist) {
             int c = 0;
             for (int cp = 0; cp < kPlanCopies; ++cp) c += ccnt[(int64_t)cp * nlist + l];
             sum += c;
-            if (blockIdx.x == 0) isum += ivf_ngroups(c, group) * ivf_nch(list_len[l]);
+            if (blockIdx.x == 0) {
+                isum += ivf_ngroups(c, group) * ivf_nch(list_len[l]);
+                gsum += ivf_ngroups(c, group);
+            }
         }
     }
     int b = block_excl_scan256(sum, s_w);
     int ib = blockIdx.x == 0 ? block_excl_scan256(isum, s_w) : 0;
+    int gb = blockIdx.x == 0 && goff ? block_excl_scan256(gsum, s_w) : 0;  // (block-uniform)
     for (int j = 0; j < per; ++j) {
         const int l = tid * per + j;
         if (l < nlist) {
@@ -350,6 +372,8 @@ __global__ void __launch_bounds__(256) ivf_planfill_q(const int64_t *__restrict_
                 bucket_off[l] = b;
                 item_off[l] = ib;
                 ib += ivf_ngroups(c, group) * ivf_nch(list_len[l]);
+                if (goff) goff[l] = gb;
+                gb += ivf_ngroups(c, group);
             }
             b += c;
         }
@@ -357,6 +381,7 @@ __global__ void __launch_bounds__(256) ivf_planfill_q(const int64_t *__restrict_
     if (blockIdx.x == 0 && tid == 255) {
         bucket_off[nlist] = b;
         item_off[nlist] = ib;
+        if (goff) goff[nlist] = gb;
     }
     // the next batch's counts and cursors start at zero (each block clears a slice)
     for (int64_t l = (int64_t)blockIdx.x * 256 + tid; l < (int64_t)kPlanCopies * nlist; l += (int64_t)gridDim.x * 256) {
@@ -1143,7 +1168,7 @@ bool ivf_plan_query_major() {
 void launch_ivf_plan(const int64_t *probes, int64_t nq, int nprobe, const int *list_len, int nlist, int group,
                      int *cnt, int *bucket_off, int *item_off, int *cursor, int *bucket, int *slot_off,
                      hipStream_t st, int *nflag_reset, unsigned *qbound, int *ccnt, int *qtot, bool counted,
-                     int *ccnt_next, int *cursor_next) {
+                     int *ccnt_next, int *cursor_next, int *goff) {
     const int64_t npairs = nq * nprobe;
     if (ivf_plan_query_major() && ccnt && qtot) {
         const unsigned gq = (unsigned)std::max<int64_t>(1, ceil_div(nq, (int64_t)4));
@@ -1156,12 +1181,12 @@ void launch_ivf_plan(const int64_t *probes, int64_t nq, int nprobe, const int *l
         if (fused_env && ccnt_next && cursor_next && nlist <= kPlanFillMaxList && nq > 0) {
             hipLaunchKernelGGL(ivf_planfill_q, dim3(gq), dim3(256), 0, st, probes, nq, nprobe, list_len, nlist, group,
                                ccnt, ccnt_next, cursor, cursor_next, qtot, slot_off, npairs, cnt, bucket_off, item_off,
-                               bucket, nflag_reset, qbound);
+                               bucket, nflag_reset, qbound, goff);
             HIPANN_CHECK(hipGetLastError());
             return;
         }
         hipLaunchKernelGGL(ivf_plan_q, dim3(1), dim3(1024), 0, st, ccnt, list_len, nlist, group, cnt, bucket_off,
-                           item_off, cursor, qtot, nq, npairs, slot_off, nflag_reset, qbound);
+                           item_off, cursor, qtot, nq, npairs, slot_off, nflag_reset, qbound, goff);
         if (nq > 0)
             hipLaunchKernelGGL(ivf_fill_q, dim3(gq), dim3(256), 0, st, probes, nq, nprobe, list_len, nlist, qtot,
                                bucket_off, cursor, bucket, slot_off);
@@ -1177,7 +1202,7 @@ void launch_ivf_plan(const int64_t *probes, int64_t nq, int nprobe, const int *l
         hipLaunchKernelGGL(ivf_count, dim3((unsigned)ceil_div(npairs, 256)), dim3(256), 0, st, probes, npairs, list_len,
                            nlist, cnt);
     hipLaunchKernelGGL(ivf_plan, dim3(1), dim3(1024), 0, st, cnt, list_len, nlist, group, bucket_off, item_off,
-                       cursor);
+                       cursor, goff);
     hipLaunchKernelGGL(ivf_slot_scan, dim3(1), dim3(1024), 0, st, probes, npairs, list_len, nlist, slot_off);
     if (npairs > 0)
         hipLaunchKernelGGL(ivf_fill, dim3((unsigned)ceil_div(npairs, 256)), dim3(256), 0, st, probes, npairs, list_len,
@@ -1584,7 +1609,8 @@ __device__ __forceinline__ void rerank_wave_select(const float *__restrict__ pd,
                                                    int64_t total, int k, int64_t nrows, float bound,
                                                    float *wk, int *wp, float *sk, int *sp, int *scnt,
                                                    WaveList<1, int> &L, bool &bad, long long &rr_t, int64_t rr_q,
-                                                   float *ntk, int *ntp) {
+                                                   float *ntk, int *ntp, const int *__restrict__ pair_slot = nullptr,
+                                                   int kslot = 0) {
     (void)rr_t;
     (void)rr_q;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -1594,8 +1620,12 @@ __device__ __forceinline__ void rerank_wave_select(const float *__restrict__ pd,
 #pragma unroll
     for (int j = 0; j < J; ++j) {
         const int64_t c = ((int64_t)j * WV + wv) * 64 + lane;
-        v[j] = c < total ? pd[c] : __builtin_inff();
-        r[j] = c < total ? pi[c] : -1;
+        bool live = c < total;
+        // pair_slot (ivf_seed_bound): candidate c belongs to the query's pair c / kslot, whose entries no item wrote
+        // when the pair has no slot (an empty list, or one on another shard)
+        if (pair_slot && live) live = pair_slot[c / kslot + 1] > pair_slot[c / kslot];
+        v[j] = live ? pd[c] : __builtin_inff();
+        r[j] = live ? pi[c] : -1;
     }
     RR_MARK(1);  // candidate loads issued
     float *mk = wk + wv * 64 * J;
@@ -2038,7 +2068,7 @@ ivf_rerank_topk(const float *__restrict__ pd, const int *__restrict__ pi, const 
                 const int64_t *__restrict__ list_off, int nlist, const unsigned *__restrict__ qbound,
                 const float *__restrict__ qnorm, int kslot, int sub, const int *__restrict__ list_len,
                 float *__restrict__ fpd, long long *__restrict__ fpi, unsigned long long *__restrict__ fb_total,
-                int fb_cap, int i8_l2) {
+                int fb_cap, int i8_l2, const int *__restrict__ seed_cnt) {
     const int64_t q = WV == 1 ? (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6) : (int64_t)blockIdx.x;
     if (q >= nq) return;
     const int lane = threadIdx.x & 63;
@@ -2052,10 +2082,13 @@ ivf_rerank_topk(const float *__restrict__ pd, const int *__restrict__ pi, const 
     // (the Flat exact form: one list per database split, query-major)
     const int64_t s0 = slot_off ? slot_off[q * nprobe] : q * nprobe;
     const int64_t s1 = slot_off ? slot_off[(q + 1) * nprobe] : (q + 1) * nprobe;
-    const int64_t total = (s1 - s0) * kslot;
+    // seed_cnt (the seeded int8 scan): the query's run instead — its seed list at the end of its first slot, then the
+    // seed_cnt[q] slots of its (probe, chunk >= 1) lists (common.hpp ivf_seed_run_slot)
+    const int64_t total = seed_cnt ? kSeedK + (int64_t)seed_cnt[q] * kslot : (s1 - s0) * kslot;
+    const int64_t first = seed_cnt ? (ivf_seed_run_slot((int)s0, q) + 1) * kslot - kSeedK : s0 * kslot;
     if constexpr (HIPANN_RR_STAMP != 0) { if (total >= 0) RR_STAMP(1); }
-    pd += s0 * kslot;
-    pi += s0 * kslot;
+    pd += first;
+    pi += first;
     // sub-list slots (the IVF scans at request_k > 12, mf_finish_item): T_sub = qbound[q], the smallest k-th key
     // over the query's full sub-lists — every row a sub-list or the running bound pruned has scan key ≥ T_sub.
     // Candidates with key ≥ T_sub never matter when the check below passes (their exact distance is ≥ T_sub − E
@@ -2488,6 +2521,122 @@ __global__ void __launch_bounds__(256) ivf_scatter_results(const float *__restri
     I[(int64_t)idx[j] * kout + e] = If[t];
 }
 
+// ---------------------------------------------------------------------------------------------
+// ivf_seed_bound — the seeded int8 scan's step between its two launches (ivf.cpp), one block per query.
+// The chunk-0 items left nprobe slots of kslot entries (one 16-list per scan wave) in (pa_d, pa_i), query-major.  The
+// block selects their kSeedK smallest (key, row) with the rerank's select (rerank_wave_select: at most 64·4·16
+// entries), candidates above the query's bound so far left out, and writes them as the last kSeedK entries of the
+// query's first candidate slot (common.hpp ivf_seed_run_slot).  When all kSeedK are real their largest key is min'ed into qbound[q]: every chunk-0 entry left
+// out has a key at or above it, and it gates the items of the second launch.  With fewer than kSeedK nothing at or
+// below the bound was left out and the bound stays.  Wave 0 also lays out the query's other slots: cslot[pair] = the
+// slot of the pair's chunk 1 (nch - 1 slots), bcnt[q] = their count over the query's pairs.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSeedWaves = 4, kSeedJ = 16;
+__global__ void __launch_bounds__(64 * kSeedWaves)
+ivf_seed_bound(const float *__restrict__ pa_d, const int *__restrict__ pa_i, const int *__restrict__ slot_off, int nprobe,
+               int64_t nq, int kslot, int64_t nrows, unsigned *__restrict__ qbound, float *__restrict__ cd,
+               int *__restrict__ ci, int *__restrict__ cslot, int *__restrict__ bcnt) {
+    const int64_t q = blockIdx.x;
+    if (q >= nq) return;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t p0 = q * nprobe;
+    const int64_t s0 = ivf_seed_run_slot(slot_off[p0], q);  // the query's first candidate slot
+    if (wv == 0) {
+        int carry = 0;
+        for (int pb = 0; pb < nprobe; pb += 64) {
+            const int p = pb + lane;
+            const int nch = p < nprobe ? slot_off[p0 + p + 1] - slot_off[p0 + p] : 0;
+            const int nb = ivf_seed_pair_slots(nch);
+            int x = nb;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int t = __shfl_up(x, o);
+                if (lane >= o) x += t;
+            }
+            if (p < nprobe) cslot[p0 + p] = (int)(s0 + 1 + carry + x - nb);
+            carry += __shfl(x, 63);
+        }
+        if (lane == 0) bcnt[q] = carry;
+    }
+    const unsigned b = qbound[q];
+    const float t = __uint_as_float((b & 0x80000000u) ? (b & 0x7fffffffu) : ~b);
+    const float bound = t == t ? t : __builtin_inff();
+    __shared__ float wk[kSeedWaves * 64 * kSeedJ], sk[kSeedWaves * 64], ntk[kSeedWaves * 64];
+    __shared__ int wp[kSeedWaves * 64 * kSeedJ], sp[kSeedWaves * 64], ntp[kSeedWaves * 64];
+    __shared__ int scnt[kSeedWaves];
+    WaveList<1, int> L;
+    L.init();
+    bool bad = false;
+    long long rr_t = 0;
+    rerank_wave_select<kSeedWaves, kSeedJ>(pa_d + p0 * kslot, pa_i + p0 * kslot, (int64_t)nprobe * kslot, kSeedK, nrows,
+                                           bound, wk, wp, sk, sp, scnt, L, bad, rr_t, q, ntk, ntp, slot_off + p0, kslot);
+    if (wv != 0) return;  // (wave 0 holds the list: lanes < kSeedK, ascending, pads last)
+    const bool real = L.id[0] != IdTraits<int>::pad();
+    cd[(s0 + 1) * kslot - kSeedK + lane] = real ? L.d[0] : __builtin_inff();
+    ci[(s0 + 1) * kslot - kSeedK + lane] = L.id[0];
+    if (lane == kSeedK - 1 && real) {
+        const unsigned u = __float_as_uint(L.d[0]);  // the scan's order-preserving bits (mf_sortable, ivf_mfma.hip)
+        atomicMin(qbound + q, (u & 0x80000000u) ? ~u : (u | 0x80000000u));
+    }
+}
+
+// Host-only (tests/test_ivf_seed_plan.py): the plan's tables for the given lists and the seeded scan's decode of every
+// item of both launches, by the functions the kernels use.  item_off / goff: nlist + 1 entries; a_* / b_*: (list, chunk,
+// group) of launch 1's goff[nlist] and launch 2's item_off[nlist] − goff[nlist] items (cap entries each).  Returns 0, or
+// -1 when cap is too small.
+extern "C" int hipann_debug_ivf_seed_items(const int *list_len, const int *cnt, int nlist, int group, int *item_off,
+                                           int *goff, int cap, int *a_lcg, int *b_lcg) {
+    int io = 0, go = 0;
+    for (int l = 0; l < nlist; ++l) {
+        item_off[l] = io;
+        goff[l] = go;
+        io += ivf_ngroups(cnt[l], group) * (int)ceil_div(list_len[l], IVF_CH);
+        go += ivf_ngroups(cnt[l], group);
+    }
+    item_off[nlist] = io;
+    goff[nlist] = go;
+    for (int phase = 1; phase <= 2; ++phase) {
+        const int total = ivf_phase_first(phase, io, go);
+        if (total > cap) return -1;
+        int *out = phase == 1 ? a_lcg : b_lcg;
+        for (int item = 0; item < total; ++item) {
+            const int l = ivf_phase_list(phase, item_off, goff, nlist, item);
+            int chunk, grp;
+            ivf_phase_decode(phase, item - ivf_phase_first(phase, item_off[l], goff[l]), ivf_ngroups(cnt[l], group), chunk, grp);
+            out[3 * item] = l;
+            out[3 * item + 1] = chunk;
+            out[3 * item + 2] = grp;
+        }
+    }
+    return 0;
+}
+// ... and the slot a (pair, chunk >= 1) item writes: slot_off = the nq·nprobe + 1 slot prefixes of the plan;
+// cslot[pair] = the slot of the pair's chunk 1 (ivf_seed_bound's), bcnt[q] = the query's slots after its seed slot.
+extern "C" void hipann_debug_ivf_seed_slots(const int *slot_off, int nprobe, int64_t nq, int64_t *cslot, int *bcnt) {
+    for (int64_t q = 0; q < nq; ++q) {
+        int64_t s = ivf_seed_run_slot(slot_off[q * nprobe], q) + 1;
+        for (int p = 0; p < nprobe; ++p) {
+            cslot[q * nprobe + p] = s;
+            s += ivf_seed_pair_slots(slot_off[q * nprobe + p + 1] - slot_off[q * nprobe + p]);
+        }
+        bcnt[q] = (int)(s - ivf_seed_run_slot(slot_off[q * nprobe], q) - 1);
+    }
+}
+
+bool ivf_seed_supported(int nprobe, int kslot) {
+    return nprobe >= 1 && kslot >= kSeedK && (int64_t)nprobe * kslot <= (int64_t)64 * kSeedWaves * kSeedJ;
+}
+
+void launch_ivf_seed_bound(const float *pa_d, const int *pa_i, const int *slot_off, int nprobe, int64_t nq, int kslot,
+                           int64_t nrows, unsigned *qbound, float *cd, int *ci, int *cslot, int *bcnt, hipStream_t st) {
+    if (nq <= 0) return;
+    HIPANN_REQUIRE(ivf_seed_supported(nprobe, kslot) && nq < (int64_t)0x7fffffff, "ivf seed bound: too many chunk-0 entries");
+    static_assert(kSeedK == 64, "the seed list is one wave wide");
+    hipLaunchKernelGGL(ivf_seed_bound, dim3((unsigned)nq), dim3(64 * kSeedWaves), 0, st, pa_d, pa_i, slot_off, nprobe, nq,
+                       kslot, nrows, qbound, cd, ci, cslot, bcnt);
+    HIPANN_CHECK(hipGetLastError());
+}
+
 #ifndef HIPANN_RR_WIDE
 #define HIPANN_RR_WIDE (1 << 30)  // below this many queries: one 4-wave block per query (nq 1024: 80 -> 65 us)
 #endif
@@ -2498,9 +2647,10 @@ void launch_ivf_rerank(const float *pd, const int *pi, const int *slot_off, int 
                        hipStream_t st, float eps, float rxmax, const float *qres, const int64_t *probes,
                        const int64_t *list_off, int nlist, const unsigned *qbound, const float *qnorm, int kslot,
                        int sub, const int *list_len, float *fpd, long long *fpi, unsigned long long *fb_total,
-                       int fb_cap, int i8_l2) {
+                       int fb_cap, int i8_l2, const int *seed_cnt) {
     if (nq <= 0) return;
     if (kslot <= 0) kslot = k;
+    HIPANN_REQUIRE(!seed_cnt || (slot_off && sub && qbound), "ivf rerank: candidate runs need the slot table and the bound");
     HIPANN_REQUIRE(!i8_l2 || (metric == kL2 && qres && qnorm), "ivf rerank: the int8 L2 certificate needs ‖q − q̂‖ and ‖q‖²");
     // the filter depth k bounds kout (kout = k leaves no margin: those queries are flagged and re-run exactly)
     HIPANN_REQUIRE(k >= kRerankK && k <= 64 && kout >= 1 && kout <= k && kslot >= 1 && (!sub || qbound),
@@ -2511,7 +2661,7 @@ void launch_ivf_rerank(const float *pd, const int *pi, const int *slot_off, int 
     dim3 grid((unsigned)(wide ? nq : ceil_div(nq, 4))), block(256);
 #define RR_ARGS pd, pi, slot_off, nprobe, nq, k, kout, Q, codes, d, ids, nrows, label_offset, xmax2, D, I, nflag, flagged, \
                 eps, rxmax, qres, probes, list_off, nlist, qbound, qnorm, kslot, sub, list_len, fpd, fpi, fb_total, \
-                fpd ? fb_cap : 0, i8_l2
+                fpd ? fb_cap : 0, i8_l2, seed_cnt
     if (metric == kIP) {
         if (wide) hipLaunchKernelGGL((ivf_rerank_topk<true, 4>), grid, block, 0, st, RR_ARGS);
         else hipLaunchKernelGGL((ivf_rerank_topk<true, 1>), grid, block, 0, st, RR_ARGS);

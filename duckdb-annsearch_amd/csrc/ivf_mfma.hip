@@ -234,7 +234,8 @@ __device__ __forceinline__ void mf_finish_item(uint64_t (&lst)[QT][4], float *sm
                 const int q = qt * 16 + 4 * g + v;
                 if (q < nqi) {
                     const int pr = bucket[boff + q];
-                    const int64_t slot = (int64_t)slot_off[pr] + chunk;
+                    // (slot_off == nullptr: one slot per (query, probe) pair, the seeded scan's chunk-0 launch)
+                    const int64_t slot = (slot_off ? (int64_t)slot_off[pr] : (int64_t)pr) + chunk;
                     const int64_t off = (sub ? slot * MF_WAVES + wave : slot) * k + m;
                     const uint64_t e = lst[qt][v];
                     const unsigned id = (unsigned)e;
@@ -960,12 +961,12 @@ typedef _Float16 mh_f16x8 __attribute__((ext_vector_type(8)));
 #ifndef HIPANN_MH_STATS
 // 1 (tuning builds): count the epilogue's work per image (fp16 | int8) — passes, (row tile, query tile, register)
 // steps, steps that admitted a row, the rows they admitted and the steps that took the insertions — the first fifth
-// of a launch's blocks (the ones that start with the loosest bounds) apart from the rest; printed once, when an index
-// closes (ivf_mh_stats_report)
+// of a launch's blocks (the ones that start with the loosest bounds) apart from the rest, and the seeded scan's two
+// launches (ivf.cpp) each on their own; printed once, when an index closes (ivf_mh_stats_report)
 #define HIPANN_MH_STATS 0
 #endif
 #if HIPANN_MH_STATS
-__device__ unsigned long long mh_stats_dev[2][2][5];
+__device__ unsigned long long mh_stats_dev[2][4][5];
 #endif
 constexpr int MH_P = HIPANN_MH_P;  // super-steps in flight per wave: 6 × 2 row tiles × 16 B = 192 B per lane
 __host__ __device__ inline int mh_nsup(int d) { return (int)ceil_div(ceil_div(d, 32), MH_P) * MH_P; }
@@ -1653,22 +1654,20 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
                 const int *__restrict__ item_off, const int *__restrict__ bucket, const int *__restrict__ slot_off,
                 int nlist, int nprobe, int group, int k, int sub, unsigned *__restrict__ qbound, float *__restrict__ part_d,
                 int *__restrict__ part_i, float *__restrict__ qres, int nq, int remap, const float *__restrict__ xs8,
-                const float *__restrict__ xr8, const float *__restrict__ qhn) {
+                const float *__restrict__ xr8, const float *__restrict__ qhn, int phase, const int *__restrict__ goff) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int total = item_off[nlist];
+    // phase: 0 every item of the plan; 1 | 2 the seeded scan's two launches (common.hpp ivf_phase_first)
+    const int total = ivf_phase_first(phase, item_off[nlist], phase ? goff[nlist] : 0);
     if ((int)blockIdx.x >= total) return;
     const int item = remap ? xcd_remap((int)blockIdx.x, total) : (int)blockIdx.x;
-    int lo = 0, hi = nlist - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (item_off[mid] <= item) lo = mid; else hi = mid - 1;
-    }
-    const int l = lo;
+    const int l = ivf_phase_list(phase, item_off, goff, nlist, item);
     const int64_t lr0 = list_off[l], lr1 = lr0 + list_len[l];
     const int c = cnt[l];
     const int ng = ivf_ngroups(c, group);
-    const int rem = item - item_off[l];
-    const int chunk = rem / ng, grp = rem - chunk * ng;
+    int chunk, grp;
+    ivf_phase_decode(phase, item - ivf_phase_first(phase, item_off[l], phase ? goff[l] : 0), ng, chunk, grp);
+    // the slot's chunk index: phase 2 writes chunk c of a pair to the pair's (c - 1)-th slot (slot_off = chunk 1's)
+    const int slot_chunk = phase == 2 ? chunk - 1 : chunk;
     const int q_begin = (int)((int64_t)grp * c / ng), q_end = (int)((int64_t)(grp + 1) * c / ng);
     const int nqi = q_end - q_begin;
     const int64_t r0 = lr0 + (int64_t)chunk * MF_CH;
@@ -1696,7 +1695,8 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
     // (no barrier here: mh_item waits for the fill after issuing its first row loads)
 
     const int lane = threadIdx.x & 63, g = lane >> 4;
-    const int stat_part = (int64_t)blockIdx.x * 5 < (int64_t)total ? 0 : 1;  // (HIPANN_MH_STATS)
+    // (HIPANN_MH_STATS: the first fifth of a launch's blocks | the rest; the seeded scan's phases apart)
+    const int stat_part = phase ? 1 + phase : (int64_t)blockIdx.x * 5 < (int64_t)total ? 0 : 1;
 #define MH_CASE(QTV)                                                                                        \
     {                                                                                                       \
         unsigned qb[QTV][4];                                                                                \
@@ -1706,7 +1706,7 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
             qb[qt][v] = q < nqi ? __atomic_load_n(qbound + qi, __ATOMIC_RELAXED) : 0xffffffffu;             \
         }                                                                                                   \
         mh_item<QTV, IP, I8>(d, codes_h, tp0, xn, r0, r1, nqi, qs, stride, qb, qpar, bucket, boff, nprobe, slot_off, \
-                             chunk, k, sub, smem, qbound, part_d, part_i, xs8, xr8, stat_part);             \
+                             slot_chunk, k, sub, smem, qbound, part_d, part_i, xs8, xr8, stat_part);        \
     }
     // (a switch: compiled as an if-else chain over nqt the kernel spills about 150 more scalar registers to
     // vector-register lanes and takes one more VGPR, profiles/ivf_scan_prune/resource_usage.txt)
@@ -1724,12 +1724,13 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
 // HIPANN_MH_STATS builds: print the epilogue's counters (and clear them); every other build: nothing
 void ivf_mh_stats_report() {
 #if HIPANN_MH_STATS
-    unsigned long long h[2][2][5];
+    unsigned long long h[2][4][5];
+    static const char *const names[4] = {"first_fifth", "rest", "seeded_chunk0", "seeded_rest"};
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(mh_stats_dev), sizeof(h)) != hipSuccess) return;
     for (int i8 = 0; i8 < 2; ++i8)
-        for (int part = 0; part < 2; ++part)
+        for (int part = 0; part < 4; ++part)
             std::fprintf(stderr, "HIPANN_MH_STATS image=%s blocks=%s passes=%llu steps=%llu hit_steps=%llu admitted_rows=%llu "
-                                 "insert_steps=%llu\n", i8 ? "int8" : "fp16", part ? "rest" : "first_fifth", h[i8][part][0],
+                                 "insert_steps=%llu\n", i8 ? "int8" : "fp16", names[part], h[i8][part][0],
                          h[i8][part][1], h[i8][part][2], h[i8][part][3], h[i8][part][4]);
     std::memset(h, 0, sizeof(h));
     (void)hipMemcpyToSymbol(HIP_SYMBOL(mh_stats_dev), h, sizeof(h));
@@ -1826,8 +1827,10 @@ void launch_ivf_scan_mfma_h(int64_t nq, const void *qsplit, const float *its, fl
                             const int64_t *list_off, const int *list_len, const int *cnt, const int *bucket_off,
                             const int *item_off, const int *bucket, const int *slot_off, int nlist, int nprobe, int k,
                             int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub, int i8mode,
-                            const float *xs8, const float *xr8, const float *qhn) {
+                            const float *xs8, const float *xr8, const float *qhn, int phase, const int *goff) {
     if (max_items <= 0 || nq <= 0) return;
+    HIPANN_REQUIRE(phase == 0 ? slot_off != nullptr : goff && (phase == 1) == (slot_off == nullptr),
+                   "fp16 / int8 IVF scan: phase 1 writes pair slots, phase 2 needs the pairs' chunk-1 slots");
     HIPANN_REQUIRE(max_items < (int64_t)0x7fffffff, "too many IVF work items");
     HIPANN_REQUIRE(qsplit && its && qres && codes_h, "fp16 IVF scan: missing buffers");
     HIPANN_REQUIRE(i8mode ? ivf_mfma_i8_supported(d, k) && xs8 : ivf_mfma_h_supported(d, k),
@@ -1848,7 +1851,7 @@ void launch_ivf_scan_mfma_h(int64_t nq, const void *qsplit, const float *its, fl
     // contiguous runs per XCD
     static const int remap = [] { const char *e = std::getenv("HIPANN_IVF_REMAP"); return !e || std::atoi(e) ? 1 : 0; }();
 #define MH_LAUNCH_ARGS qs, qn, its, d, ch, tpass_off, xn, list_off, list_len, cnt, bucket_off, item_off, bucket, slot_off, nlist, nprobe, \
-                       group, k, sub, qbound, pd, pi, qres, (int)nq, remap, xs8, xr8, qhn
+                       group, k, sub, qbound, pd, pi, qres, (int)nq, remap, xs8, xr8, qhn, phase, goff
     if (i8mode) {
         if (metric == kIP) hipLaunchKernelGGL((ivf_scan_mfma_h<true, true>), grid, block, smem, st, MH_LAUNCH_ARGS);
         else hipLaunchKernelGGL((ivf_scan_mfma_h<false, true>), grid, block, smem, st, MH_LAUNCH_ARGS);

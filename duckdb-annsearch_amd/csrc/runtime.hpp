@@ -394,6 +394,7 @@ struct IvfShard {
     // scratch
     DevBuf q, qn, coarse_d, coarse_i, cnt, bucket_off, item_off, cursor, bucket, slot_off, part_d, part_i, out_d, out_i;
     DevBuf qbound;                 // per query: best known k-th key (order-preserving u32; MFMA scan)
+    DevBuf goff, cslot, bcnt;      // the plan's group prefix; seeded int8 scan: the pairs' first units, the queries' unit counts
     DevBuf qsplit;                 // split-bf16 scans: the batch's queries as bf16 terms
     // kFormSplit2Exact: max row ‖x‖² (for the rerank's error bound; −1 until computed), the flagged
     // queries of the last batch and the re-run's buffers
@@ -461,6 +462,7 @@ struct IvfIndex : IndexBase {
     std::vector<int> owner;  // list → shard (size-balanced at create; appended rows follow their list)
     int form = kFormHalfExact;
     int filter_image = 2, last_filter_image = 0;  // hipann_ivf_set_filter_image (0 fp16, 1 int8, 2 auto); the last search's
+    int last_seeded = 0;  // the last search's int8 scan ran seeded: two launches around ivf_seed_bound (hipann_ivf_last_seeded)
     int64_t rerank_fallbacks = 0;  // queries re-run from the host (HIPANN_IVF_HOST_FALLBACK); device re-runs: fb_total
     std::vector<std::unique_ptr<IvfShard>> shards;
     int64_t last_nq = 0;
@@ -524,7 +526,9 @@ void launch_flat_scan_topk(const float *Q, int nq, const float *X, int64_t N, in
 void launch_ivf_plan(const int64_t *probes, int64_t nq, int nprobe, const int *list_len, int nlist, int group,
                      int *cnt, int *bucket_off, int *item_off, int *cursor, int *bucket, int *slot_off,
                      hipStream_t st, int *nflag_reset = nullptr, unsigned *qbound = nullptr, int *ccnt = nullptr,
-                     int *qtot = nullptr, bool counted = false, int *ccnt_next = nullptr, int *cursor_next = nullptr);
+                     int *qtot = nullptr, bool counted = false, int *ccnt_next = nullptr, int *cursor_next = nullptr,
+                     // goff[l] = the query groups of the lists before l (nlist + 1 entries): list l's chunk-0 items
+                     int *goff = nullptr);
 int64_t ivf_max_items(int64_t nq, int nprobe, int nlist, int max_nch, int64_t nrows, int group);
 int ivf_mfma_bf_group(int d, int np);
 bool ivf_mfma_bf_supported(const float *Q, int d, const float *codes, int k, int np);
@@ -547,7 +551,10 @@ void launch_ivf_rerank(const float *pd, const int *pi, const int *slot_off, int 
                        const int *list_len = nullptr, float *fpd = nullptr, long long *fpi = nullptr,
                        unsigned long long *fb_total = nullptr,  // fpd != nullptr: flagged IVF queries re-run inline
                        int fb_cap = 0,  // ... except the first fb_cap, left to launch_ivf_fallback_chunks
-                       int i8_l2 = 0);  // the int8 image's L2 certificate (qres = ‖q − q̂‖, lower-bound scan keys)
+                       int i8_l2 = 0,  // the int8 image's L2 certificate (qres = ‖q − q̂‖, lower-bound scan keys)
+                       // the seeded int8 scan: pd / pi hold every query's candidate run (common.hpp
+                       // ivf_seed_run_slot), query q's of kSeedK + seed_cnt[q]·kslot entries; slot_off only places the runs
+                       const int *seed_cnt = nullptr);
 // the rerank's first fb_cap flagged queries re-run in parallel (one wave per (query, probe, chunk) item); cpd/cpi:
 // fb_cap·nprobe·maxch·kout entries, done: fb_cap counters (zero on entry; left zero)
 void launch_ivf_fallback_chunks(const int *nflag, const int *flagged, int fb_cap, int nprobe, int maxch, int chunk_rows,
@@ -576,7 +583,18 @@ void launch_ivf_scan_mfma_h(int64_t nq, const void *qsplit, const float *its, fl
                             const int *item_off, const int *bucket, const int *slot_off, int nlist, int nprobe, int k,
                             int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub = 0,
                             int i8mode = 0, const float *xs8 = nullptr, const float *xr8 = nullptr,
-                            const float *qhn = nullptr);
+                            const float *qhn = nullptr,
+                            // the seeded scan's two launches (ivf_scan_mfma_h): 1 = the chunk-0 items (slot_off ==
+                            // nullptr: one slot per pair), 2 = the others (slot_off = the slots of the pairs' chunk 1);
+                            // goff = the plan's group prefix
+                            int phase = 0, const int *goff = nullptr);
+// The seeded int8 scan's step between its two launches, one block per query: the kSeedK best of the query's nprobe·kslot
+// chunk-0 entries (pa_d / pa_i, one kslot-entry slot per pair; pairs without rows skipped) into the tail of the query's
+// first candidate slot (cd / ci), the kSeedK-th key min'ed into qbound[q] when all kSeedK are real; cslot[pair] = the
+// slot of the pair's chunk 1 (one per chunk >= 1), bcnt[q] = the query's count of those slots.
+bool ivf_seed_supported(int nprobe, int kslot);
+void launch_ivf_seed_bound(const float *pa_d, const int *pa_i, const int *slot_off, int nprobe, int64_t nq, int kslot,
+                           int64_t nrows, unsigned *qbound, float *cd, int *ci, int *cslot, int *bcnt, hipStream_t st);
 // int8 image (kFormI8Exact): packed group (wide items only), pass / query-image bytes, support, the tiling (one scale
 // and one residual per row into xs8 / xr8; *nonfin != 0 afterwards: a non-finite row), the batch's int8 queries (units,
 // scales, residuals, ‖q̂‖² and ‖q̂‖ of the dequantised queries)

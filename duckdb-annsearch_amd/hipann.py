@@ -126,6 +126,7 @@ def lib() -> C.CDLL:
             "hipann_ivf_set_filter_image": ([vp, i32], i32),
             "hipann_ivf_get_filter_image": ([vp], i32),
             "hipann_ivf_last_filter_image": ([vp], i32),
+            "hipann_ivf_last_seeded": ([vp], i32),
             "hipann_ntotal": ([vp], i64),
             "hipann_dim": ([vp], i32),
             "hipann_metric": ([vp], i32),
@@ -249,12 +250,16 @@ class _Handle:
     def set_kernel_timing(self, on: bool) -> None:
         lib().hipann_set_kernel_timing(self._h, 1 if on else 0)
 
-    def last_search_path(self) -> dict:
+    def last_search_path(self, seeded: bool = False) -> dict:
         """hipann_last_search_path: the form the last search's scan ran, its rerank filter depth (0 = none) and
-        the IVF sub-lists per slot (0 = merged lists)."""
+        the IVF sub-lists per slot (0 = merged lists).  seeded=True (IVF indexes) adds "seeded": 1 when the int8 scan
+        ran as two launches around its per-query seed bound (hipann_ivf_last_seeded), else 0."""
         f, kf, sl = C.c_int(-1), C.c_int(0), C.c_int(0)
         lib().hipann_last_search_path(self._h, C.byref(f), C.byref(kf), C.byref(sl))
-        return {"form": f.value, "filter_k": kf.value, "sublists": sl.value}
+        path = {"form": f.value, "filter_k": kf.value, "sublists": sl.value}
+        if seeded:
+            path["seeded"] = int(lib().hipann_ivf_last_seeded(self._h))
+        return path
 
     def kernel_ms(self, which: int = 0) -> float:
         return float(lib().hipann_last_kernel_ms(self._h, which))

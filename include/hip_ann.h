@@ -350,6 +350,11 @@ int hipann_ivf_get_form(void *index);
 int hipann_ivf_set_filter_image(void *index, int mode);
 int hipann_ivf_get_filter_image(void *index);
 int hipann_ivf_last_filter_image(void *index);
+/* 1 when the last search's int8 scan ran seeded: the first 2048-row chunk of every probed list, then a per-query gate
+ * from the 64 best of those keys, then the other chunks under it (L2, lists of more than one chunk, nprobe <= 32);
+ * 0 for the single launch (every other path, or HIPANN_IVF_SEED=0 in the environment, A/B).  The results are the
+ * same either way.  −1 for a bad handle. */
+int hipann_ivf_last_seeded(void *index);
 /* 32-row passes of the int8 image tiled since the index was created, summed over its shards (the first int8 search
  * tiles every pass; an add or a remove only the passes it touched).  −1 for a bad handle. */
 int64_t hipann_ivf_i8_passes_tiled(void *index);
