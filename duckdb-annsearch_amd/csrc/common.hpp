@@ -141,9 +141,10 @@ __host__ __device__ inline void ivf_phase_decode(int phase, int rem, int ng, int
     grp = phase == 1 ? rem : rem % ng;
 }
 // A query's candidates after the seeded scan, in slots of kslot entries (one 16-list per scan wave): query q owns the
-// slots from slot_off[q·nprobe] + q on — one whose last kSeedK entries are its seed list, then nch − 1 per pair (the
-// chunks >= 1 of the pair's list), so the candidates are one contiguous run that starts kslot − kSeedK entries into
-// the first slot.
+// slots from slot_off[q·nprobe] + q on — one whose last kSeedK entries are its seed list, then room for nch − 1 per
+// pair (the chunks >= 1 of the pair's list), into which the second launch's waves append the rows they admitted, in
+// the order they finish.  So the candidates are one contiguous run that starts kslot − kSeedK entries into the first
+// slot: the seed list, then as many entries as the query's cursor counts.
 __host__ __device__ inline int64_t ivf_seed_run_slot(int slot0, int64_t q) { return (int64_t)slot0 + q; }
 __host__ __device__ inline int ivf_seed_pair_slots(int nch) { return nch > 1 ? nch - 1 : 0; }
 

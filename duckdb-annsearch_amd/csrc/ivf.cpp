@@ -610,7 +610,8 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
         if (img) {
             // (int8: its query units, scales and residuals in the fp16 form's slots; L2: ‖q̂‖² of the dequantised
             // queries as the key's query term)
-            auto scan_h = [&](int phase, const int *slots, int64_t items, float *pd, int *pi, int subl) {
+            auto scan_h = [&](int phase, const int *slots, int64_t items, float *pd, int *pi, int subl,
+                              int *run_cnt = nullptr) {
                 launch_ivf_scan_mfma_h(nq, i8 ? sh.qi8.p : sh.hsplit.p, i8 ? sh.qs8.get<float>() : sh.hits.get<float>(),
                                        i8 ? sh.qres8.get<float>() : sh.hres.get<float>(), cert8 ? sh.qhn2.get<float>() : qn, d,
                                        metric, i8 ? sh.codes_i8.p : sh.codes_h.p, sh.tpass_off.get<int64_t>(), sh.xnorm.get<float>(),
@@ -619,20 +620,36 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
                                        items, qbound, pd, pi, st, subl,
                                        i8 ? 1 : 0, i8 ? sh.xs8.get<float>() : nullptr,
                                        cert8 ? sh.xr8.get<float>() : nullptr, cert8 ? sh.qhn.get<float>() : nullptr, phase,
-                                       sh.goff.get<int>());
+                                       sh.goff.get<int>(), run_cnt);
             };
             if (seeded) {
                 // the chunk-0 slots (one per pair) take the head of part_d / part_i, the queries' candidate slots
-                // (common.hpp ivf_seed_run_slot) the rest
+                // (common.hpp ivf_seed_run_slot) the rest: a query's run is its seed list, then the rows the second
+                // launch's waves append under run_cnt[q] — room for every (pair, chunk >= 1) sub-list in full, so no
+                // append can overflow; the rerank reads kSeedK + run_cnt[q] entries
                 HIPANN_REQUIRE((int64_t)np * nq * sh.max_nch + nq < (int64_t)0x7fffffff, "too many candidate slots");
-                sh.cslot.ensure(sizeof(int) * (size_t)nq * np, sh.device);
-                sh.bcnt.ensure(sizeof(int) * (size_t)nq, sh.device);
+                HIPANN_REQUIRE((int64_t)np * sh.max_nch * kslot < (int64_t)0x7fffffff, "candidate run too long");
+                sh.run_cnt.ensure(sizeof(int) * (size_t)nq, sh.device);
                 cand_d = sh.part_d.get<float>() + (size_t)np * nq * kslot;
                 cand_i = sh.part_i.get<int>() + (size_t)np * nq * kslot;
                 scan_h(1, nullptr, ivf_max_items(nq, np, nlist, 1, 0, group), sh.part_d.get<float>(), sh.part_i.get<int>(), 1);
                 launch_ivf_seed_bound(sh.part_d.get<float>(), sh.part_i.get<int>(), sh.slot_off.get<int>(), np, nq, kslot,
-                                      sh.n, qbound, cand_d, cand_i, sh.cslot.get<int>(), sh.bcnt.get<int>(), st);
-                scan_h(2, sh.cslot.get<int>(), ivf_max_items(nq, np, nlist, sh.max_nch - 1, sh.n, group), cand_d, cand_i, 1);
+                                      sh.n, qbound, cand_d, cand_i, sh.run_cnt.get<int>(), st);
+                scan_h(2, sh.slot_off.get<int>(), ivf_max_items(nq, np, nlist, sh.max_nch - 1, sh.n, group), cand_d, cand_i, 1,
+                       sh.run_cnt.get<int>());
+                // HIPANN_IVF_RUN_STATS=1 (measurement only: a stream sync and a readback per batch): the appended
+                // entries per query
+                static const bool run_stats = [] { const char *e = std::getenv("HIPANN_IVF_RUN_STATS"); return e && std::atoi(e) != 0; }();
+                if (run_stats) {
+                    std::vector<int> h((size_t)nq);
+                    HIPANN_CHECK(hipMemcpyAsync(h.data(), sh.run_cnt.p, sizeof(int) * (size_t)nq, hipMemcpyDeviceToHost, st));
+                    HIPANN_CHECK(hipStreamSynchronize(st));
+                    int64_t sum = 0, over = 0;
+                    int mx = 0;
+                    for (int c : h) { sum += c; mx = std::max(mx, c); over += kSeedK + c > 4096; }
+                    std::fprintf(stderr, "HIPANN_IVF_RUN_STATS nq=%lld appended_total=%lld mean=%.1f max=%d runs_over_4096=%lld\n",
+                                 (long long)nq, (long long)sum, (double)sum / (double)nq, mx, (long long)over);
+                }
             } else {
                 scan_h(0, sh.slot_off.get<int>(), max_items, sh.part_d.get<float>(), sh.part_i.get<int>(), sub ? 1 : 0);
             }
@@ -706,7 +723,7 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
                           sub ? 1 : 0, inline_fb ? sh.list_len.get<int>() : nullptr,
                           inline_fb ? sh.fpd.get<float>() : nullptr, inline_fb ? sh.fpi.get<long long>() : nullptr,
                           inline_fb ? sh.fb_total.get<unsigned long long>() : nullptr, fb_cap, cert8 ? 1 : 0,
-                          seeded ? sh.bcnt.get<int>() : nullptr);
+                          seeded ? sh.run_cnt.get<int>() : nullptr);
         if (fb_cap > 0)
             launch_ivf_fallback_chunks(sh.nflag.get<int>(), sh.flagged.get<int>(), fb_cap, np, fb_maxch, ivf_chunk_rows(),
                                        kout, metric, xq, sh.codes, d, sh.ids, 0, sh.coarse_i.get<int64_t>(),

@@ -2082,9 +2082,10 @@ ivf_rerank_topk(const float *__restrict__ pd, const int *__restrict__ pi, const 
     // (the Flat exact form: one list per database split, query-major)
     const int64_t s0 = slot_off ? slot_off[q * nprobe] : q * nprobe;
     const int64_t s1 = slot_off ? slot_off[(q + 1) * nprobe] : (q + 1) * nprobe;
-    // seed_cnt (the seeded int8 scan): the query's run instead — its seed list at the end of its first slot, then the
-    // seed_cnt[q] slots of its (probe, chunk >= 1) lists (common.hpp ivf_seed_run_slot)
-    const int64_t total = seed_cnt ? kSeedK + (int64_t)seed_cnt[q] * kslot : (s1 - s0) * kslot;
+    // seed_cnt (the seeded int8 scan): the query's run instead — its seed list at the end of its first slot
+    // (common.hpp ivf_seed_run_slot), then the seed_cnt[q] entries the second launch appended (memory past them is
+    // stale and never read)
+    const int64_t total = seed_cnt ? kSeedK + (int64_t)seed_cnt[q] : (s1 - s0) * kslot;
     const int64_t first = seed_cnt ? (ivf_seed_run_slot((int)s0, q) + 1) * kslot - kSeedK : s0 * kslot;
     if constexpr (HIPANN_RR_STAMP != 0) { if (total >= 0) RR_STAMP(1); }
     pd += first;
@@ -2528,36 +2529,20 @@ __global__ void __launch_bounds__(256) ivf_scatter_results(const float *__restri
 // entries), candidates above the query's bound so far left out, and writes them as the last kSeedK entries of the
 // query's first candidate slot (common.hpp ivf_seed_run_slot).  When all kSeedK are real their largest key is min'ed into qbound[q]: every chunk-0 entry left
 // out has a key at or above it, and it gates the items of the second launch.  With fewer than kSeedK nothing at or
-// below the bound was left out and the bound stays.  Wave 0 also lays out the query's other slots: cslot[pair] = the
-// slot of the pair's chunk 1 (nch - 1 slots), bcnt[q] = their count over the query's pairs.
+// below the bound was left out and the bound stays.  The block also zeroes cursor[q], the count of entries the
+// second launch appends after the seed list (mf_finish_item, ivf_mfma.hip).
 // ---------------------------------------------------------------------------------------------
 constexpr int kSeedWaves = 4, kSeedJ = 16;
 __global__ void __launch_bounds__(64 * kSeedWaves)
 ivf_seed_bound(const float *__restrict__ pa_d, const int *__restrict__ pa_i, const int *__restrict__ slot_off, int nprobe,
                int64_t nq, int kslot, int64_t nrows, unsigned *__restrict__ qbound, float *__restrict__ cd,
-               int *__restrict__ ci, int *__restrict__ cslot, int *__restrict__ bcnt) {
+               int *__restrict__ ci, int *__restrict__ cursor) {
     const int64_t q = blockIdx.x;
     if (q >= nq) return;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t p0 = q * nprobe;
     const int64_t s0 = ivf_seed_run_slot(slot_off[p0], q);  // the query's first candidate slot
-    if (wv == 0) {
-        int carry = 0;
-        for (int pb = 0; pb < nprobe; pb += 64) {
-            const int p = pb + lane;
-            const int nch = p < nprobe ? slot_off[p0 + p + 1] - slot_off[p0 + p] : 0;
-            const int nb = ivf_seed_pair_slots(nch);
-            int x = nb;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(x, o);
-                if (lane >= o) x += t;
-            }
-            if (p < nprobe) cslot[p0 + p] = (int)(s0 + 1 + carry + x - nb);
-            carry += __shfl(x, 63);
-        }
-        if (lane == 0) bcnt[q] = carry;
-    }
+    if (threadIdx.x == 0) cursor[q] = 0;
     const unsigned b = qbound[q];
     const float t = __uint_as_float((b & 0x80000000u) ? (b & 0x7fffffffu) : ~b);
     const float bound = t == t ? t : __builtin_inff();
@@ -2611,7 +2596,8 @@ extern "C" int hipann_debug_ivf_seed_items(const int *list_len, const int *cnt, 
     return 0;
 }
 // ... and the slot a (pair, chunk >= 1) item writes: slot_off = the nq·nprobe + 1 slot prefixes of the plan;
-// cslot[pair] = the slot of the pair's chunk 1 (ivf_seed_bound's), bcnt[q] = the query's slots after its seed slot.
+// cslot[pair] = the first of the pair's nch - 1 slots, bcnt[q] = the query's slots after its seed slot: the capacity
+// of the query's candidate run, bcnt[q]·kslot entries after the seed list (the second launch appends at most that).
 extern "C" void hipann_debug_ivf_seed_slots(const int *slot_off, int nprobe, int64_t nq, int64_t *cslot, int *bcnt) {
     for (int64_t q = 0; q < nq; ++q) {
         int64_t s = ivf_seed_run_slot(slot_off[q * nprobe], q) + 1;
@@ -2628,12 +2614,12 @@ bool ivf_seed_supported(int nprobe, int kslot) {
 }
 
 void launch_ivf_seed_bound(const float *pa_d, const int *pa_i, const int *slot_off, int nprobe, int64_t nq, int kslot,
-                           int64_t nrows, unsigned *qbound, float *cd, int *ci, int *cslot, int *bcnt, hipStream_t st) {
+                           int64_t nrows, unsigned *qbound, float *cd, int *ci, int *cursor, hipStream_t st) {
     if (nq <= 0) return;
     HIPANN_REQUIRE(ivf_seed_supported(nprobe, kslot) && nq < (int64_t)0x7fffffff, "ivf seed bound: too many chunk-0 entries");
     static_assert(kSeedK == 64, "the seed list is one wave wide");
     hipLaunchKernelGGL(ivf_seed_bound, dim3((unsigned)nq), dim3(64 * kSeedWaves), 0, st, pa_d, pa_i, slot_off, nprobe, nq,
-                       kslot, nrows, qbound, cd, ci, cslot, bcnt);
+                       kslot, nrows, qbound, cd, ci, cursor);
     HIPANN_CHECK(hipGetLastError());
 }
 

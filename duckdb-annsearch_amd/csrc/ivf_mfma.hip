@@ -194,15 +194,49 @@ __device__ __forceinline__ unsigned row_kth_key(uint64_t l, int kth, int g) {
 // query's running bound, so at the end qbound[q] is the smallest k-th key over the query's full sub-lists:
 // every row some sub-list (or the bound) pruned has a scan key ≥ it, which is what ivf_rerank_topk certifies
 // against besides its own k-th merged key.
+// cursor != nullptr (sub = 1, the seeded int8 scan's second launch; slot_off = the plan's slot prefixes): no slots —
+// every wave appends the real entries of its list (the list is sorted and a real entry precedes the bound's pads, so
+// they are its leading lanes) to the query's candidate run, which starts after the query's seed list
+// (common.hpp ivf_seed_run_slot) and has room for every sub-list in full.  One atomicAdd on cursor[query] per
+// non-empty list reserves the entries; a list without a real entry touches no global memory.  The k-th key is
+// published as above.
 template <int QT>
 __device__ __forceinline__ void mf_finish_item(uint64_t (&lst)[QT][4], float *smem, int nqi,
                                                const int *__restrict__ bucket, int boff, int nprobe,
                                                const int *__restrict__ slot_off, int chunk, int k, int sub,
                                                unsigned *__restrict__ qbound, float *__restrict__ part_d,
-                                               int *__restrict__ part_i) {
+                                               int *__restrict__ part_i, int *__restrict__ cursor = nullptr) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = lane & 15, g = lane >> 4;
+    if (cursor) {  // kernel-uniform
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int q = qt * 16 + 4 * g + v;
+                const uint64_t e = lst[qt][v];
+                const unsigned id = (unsigned)e;
+                const bool real = q < nqi && m < k && e != MF_EMPTY && id != MF_PAD_ID;
+                const uint64_t rm = __ballot(real);
+                if (rm) {  // wave-uniform: one of the four queries' lists holds a row
+                    const int n = __popc((unsigned)(rm >> (16 * g)) & 0xffffu);
+                    const int qi = n ? bucket[boff + q] / nprobe : 0;
+                    int base = 0;
+                    if (m == 0 && n) base = atomicAdd(cursor + qi, n);
+                    base = __shfl(base, lane & 48);
+                    if (m < n) {
+                        const int64_t off =
+                            (ivf_seed_run_slot(slot_off[(int64_t)qi * nprobe], qi) + 1) * (MF_WAVES * k) + base + m;
+                        part_d[off] = mf_unsortable((unsigned)(e >> 32));
+                        part_i[off] = (int)id;
+                        // a real k-th tightens the query's bound for the items that start later
+                        if (m == k - 1) atomicMin(qbound + qi, (unsigned)(e >> 32));
+                    }
+                }
+            }
+        return;
+    }
     if (!sub) {  // block-uniform
         // the query image is dead once every wave has left its main loop (first barrier)
         uint64_t *scratch = reinterpret_cast<uint64_t *>(smem);
@@ -1418,7 +1452,7 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
                                         const int *__restrict__ slot_off, int chunk, int k, int sub, float *smem,
                                         unsigned *__restrict__ qbound, float *__restrict__ part_d,
                                         int *__restrict__ part_i, const float *__restrict__ xs8,
-                                        const float *__restrict__ xr8, int stat_part) {
+                                        const float *__restrict__ xr8, int stat_part, int *__restrict__ cursor) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = lane & 15, g = lane >> 4;
@@ -1627,7 +1661,7 @@ __device__ __forceinline__ void mh_item(int d, const uint4 *__restrict__ codes_h
         atomicAdd(st + 4, (unsigned long long)st_ins);
     }
 #endif
-    mf_finish_item<QT>(lst, smem, nqi, bucket, boff, nprobe, slot_off, chunk, k, sub, qbound, part_d, part_i);
+    mf_finish_item<QT>(lst, smem, nqi, bucket, boff, nprobe, slot_off, chunk, k, sub, qbound, part_d, part_i, cursor);
 }
 
 // Copy the item's queries' first term (of the TS in qsplit [query][term][S][g][4 dwords]: the two fp16 terms, or the
@@ -1654,7 +1688,8 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
                 const int *__restrict__ item_off, const int *__restrict__ bucket, const int *__restrict__ slot_off,
                 int nlist, int nprobe, int group, int k, int sub, unsigned *__restrict__ qbound, float *__restrict__ part_d,
                 int *__restrict__ part_i, float *__restrict__ qres, int nq, int remap, const float *__restrict__ xs8,
-                const float *__restrict__ xr8, const float *__restrict__ qhn, int phase, const int *__restrict__ goff) {
+                const float *__restrict__ xr8, const float *__restrict__ qhn, int phase, const int *__restrict__ goff,
+                int *__restrict__ cursor) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // phase: 0 every item of the plan; 1 | 2 the seeded scan's two launches (common.hpp ivf_phase_first)
     const int total = ivf_phase_first(phase, item_off[nlist], phase ? goff[nlist] : 0);
@@ -1666,8 +1701,7 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
     const int ng = ivf_ngroups(c, group);
     int chunk, grp;
     ivf_phase_decode(phase, item - ivf_phase_first(phase, item_off[l], phase ? goff[l] : 0), ng, chunk, grp);
-    // the slot's chunk index: phase 2 writes chunk c of a pair to the pair's (c - 1)-th slot (slot_off = chunk 1's)
-    const int slot_chunk = phase == 2 ? chunk - 1 : chunk;
+    // (phase 2 writes no slots: its waves append to the queries' candidate runs through cursor, mf_finish_item)
     const int q_begin = (int)((int64_t)grp * c / ng), q_end = (int)((int64_t)(grp + 1) * c / ng);
     const int nqi = q_end - q_begin;
     const int64_t r0 = lr0 + (int64_t)chunk * MF_CH;
@@ -1706,7 +1740,8 @@ ivf_scan_mfma_h(const uint4 *__restrict__ qsplit, const float *__restrict__ qnor
             qb[qt][v] = q < nqi ? __atomic_load_n(qbound + qi, __ATOMIC_RELAXED) : 0xffffffffu;             \
         }                                                                                                   \
         mh_item<QTV, IP, I8>(d, codes_h, tp0, xn, r0, r1, nqi, qs, stride, qb, qpar, bucket, boff, nprobe, slot_off, \
-                             slot_chunk, k, sub, smem, qbound, part_d, part_i, xs8, xr8, stat_part);        \
+                             chunk, k, sub, smem, qbound, part_d, part_i, xs8, xr8, stat_part,         \
+                             I8 && !IP ? cursor : nullptr);                                                 \
     }
     // (a switch: compiled as an if-else chain over nqt the kernel spills about 150 more scalar registers to
     // vector-register lanes and takes one more VGPR, profiles/ivf_scan_prune/resource_usage.txt)
@@ -1827,10 +1862,13 @@ void launch_ivf_scan_mfma_h(int64_t nq, const void *qsplit, const float *its, fl
                             const int64_t *list_off, const int *list_len, const int *cnt, const int *bucket_off,
                             const int *item_off, const int *bucket, const int *slot_off, int nlist, int nprobe, int k,
                             int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub, int i8mode,
-                            const float *xs8, const float *xr8, const float *qhn, int phase, const int *goff) {
+                            const float *xs8, const float *xr8, const float *qhn, int phase, const int *goff,
+                            int *cursor) {
     if (max_items <= 0 || nq <= 0) return;
     HIPANN_REQUIRE(phase == 0 ? slot_off != nullptr : goff && (phase == 1) == (slot_off == nullptr),
-                   "fp16 / int8 IVF scan: phase 1 writes pair slots, phase 2 needs the pairs' chunk-1 slots");
+                   "fp16 / int8 IVF scan: phase 1 writes pair slots, phase 2 needs the plan's slot prefixes");
+    HIPANN_REQUIRE((phase == 2) == (cursor != nullptr) && (!cursor || (i8mode && metric == kL2 && sub)),
+                   "int8 IVF scan: phase 2 (int8 image, L2, sub-lists) appends through the queries' cursors");
     HIPANN_REQUIRE(max_items < (int64_t)0x7fffffff, "too many IVF work items");
     HIPANN_REQUIRE(qsplit && its && qres && codes_h, "fp16 IVF scan: missing buffers");
     HIPANN_REQUIRE(i8mode ? ivf_mfma_i8_supported(d, k) && xs8 : ivf_mfma_h_supported(d, k),
@@ -1851,7 +1889,7 @@ void launch_ivf_scan_mfma_h(int64_t nq, const void *qsplit, const float *its, fl
     // contiguous runs per XCD
     static const int remap = [] { const char *e = std::getenv("HIPANN_IVF_REMAP"); return !e || std::atoi(e) ? 1 : 0; }();
 #define MH_LAUNCH_ARGS qs, qn, its, d, ch, tpass_off, xn, list_off, list_len, cnt, bucket_off, item_off, bucket, slot_off, nlist, nprobe, \
-                       group, k, sub, qbound, pd, pi, qres, (int)nq, remap, xs8, xr8, qhn, phase, goff
+                       group, k, sub, qbound, pd, pi, qres, (int)nq, remap, xs8, xr8, qhn, phase, goff, cursor
     if (i8mode) {
         if (metric == kIP) hipLaunchKernelGGL((ivf_scan_mfma_h<true, true>), grid, block, smem, st, MH_LAUNCH_ARGS);
         else hipLaunchKernelGGL((ivf_scan_mfma_h<false, true>), grid, block, smem, st, MH_LAUNCH_ARGS);

@@ -394,7 +394,7 @@ struct IvfShard {
     // scratch
     DevBuf q, qn, coarse_d, coarse_i, cnt, bucket_off, item_off, cursor, bucket, slot_off, part_d, part_i, out_d, out_i;
     DevBuf qbound;                 // per query: best known k-th key (order-preserving u32; MFMA scan)
-    DevBuf goff, cslot, bcnt;      // the plan's group prefix; seeded int8 scan: the pairs' first units, the queries' unit counts
+    DevBuf goff, run_cnt;          // the plan's group prefix; seeded int8 scan: the queries' appended-entry cursors
     DevBuf qsplit;                 // split-bf16 scans: the batch's queries as bf16 terms
     // kFormSplit2Exact: max row ‖x‖² (for the rerank's error bound; −1 until computed), the flagged
     // queries of the last batch and the re-run's buffers
@@ -553,7 +553,7 @@ void launch_ivf_rerank(const float *pd, const int *pi, const int *slot_off, int 
                        int fb_cap = 0,  // ... except the first fb_cap, left to launch_ivf_fallback_chunks
                        int i8_l2 = 0,  // the int8 image's L2 certificate (qres = ‖q − q̂‖, lower-bound scan keys)
                        // the seeded int8 scan: pd / pi hold every query's candidate run (common.hpp
-                       // ivf_seed_run_slot), query q's of kSeedK + seed_cnt[q]·kslot entries; slot_off only places the runs
+                       // ivf_seed_run_slot), query q's of kSeedK + seed_cnt[q] entries; slot_off only places the runs
                        const int *seed_cnt = nullptr);
 // the rerank's first fb_cap flagged queries re-run in parallel (one wave per (query, probe, chunk) item); cpd/cpi:
 // fb_cap·nprobe·maxch·kout entries, done: fb_cap counters (zero on entry; left zero)
@@ -585,16 +585,17 @@ void launch_ivf_scan_mfma_h(int64_t nq, const void *qsplit, const float *its, fl
                             int i8mode = 0, const float *xs8 = nullptr, const float *xr8 = nullptr,
                             const float *qhn = nullptr,
                             // the seeded scan's two launches (ivf_scan_mfma_h): 1 = the chunk-0 items (slot_off ==
-                            // nullptr: one slot per pair), 2 = the others (slot_off = the slots of the pairs' chunk 1);
-                            // goff = the plan's group prefix
-                            int phase = 0, const int *goff = nullptr);
+                            // nullptr: one slot per pair), 2 = the others (slot_off = the plan's slot prefixes; the
+                            // waves append their rows to the queries' candidate runs through cursor, one int per
+                            // query, zeroed by launch_ivf_seed_bound); goff = the plan's group prefix
+                            int phase = 0, const int *goff = nullptr, int *cursor = nullptr);
 // The seeded int8 scan's step between its two launches, one block per query: the kSeedK best of the query's nprobe·kslot
 // chunk-0 entries (pa_d / pa_i, one kslot-entry slot per pair; pairs without rows skipped) into the tail of the query's
-// first candidate slot (cd / ci), the kSeedK-th key min'ed into qbound[q] when all kSeedK are real; cslot[pair] = the
-// slot of the pair's chunk 1 (one per chunk >= 1), bcnt[q] = the query's count of those slots.
+// first candidate slot (cd / ci), the kSeedK-th key min'ed into qbound[q] when all kSeedK are real; cursor[q] = 0, the
+// query's count of entries appended after its seed list (the second launch adds to it).
 bool ivf_seed_supported(int nprobe, int kslot);
 void launch_ivf_seed_bound(const float *pa_d, const int *pa_i, const int *slot_off, int nprobe, int64_t nq, int kslot,
-                           int64_t nrows, unsigned *qbound, float *cd, int *ci, int *cslot, int *bcnt, hipStream_t st);
+                           int64_t nrows, unsigned *qbound, float *cd, int *ci, int *cursor, hipStream_t st);
 // int8 image (kFormI8Exact): packed group (wide items only), pass / query-image bytes, support, the tiling (one scale
 // and one residual per row into xs8 / xr8; *nonfin != 0 afterwards: a non-finite row), the batch's int8 queries (units,
 // scales, residuals, ‖q̂‖² and ‖q̂‖ of the dequantised queries)

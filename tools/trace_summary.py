@@ -1,5 +1,7 @@
 """Per-step kernel breakdown from a rocprofv3 --kernel-trace csv: mean microseconds and launches per step,
-a step being the window between consecutive launches of the step's anchor kernel (default: the IVF scan)."""
+a step being the window between consecutive launches of the step's anchor kernel (default: the IVF scan).
+A fourth argument "split" reports the IVF scan's launches within a step apart ("launch 1", "launch 2": the seeded
+int8 scan's two launches; use another anchor then, e.g. ivf_planfill_q)."""
 import csv
 import sys
 from collections import defaultdict
@@ -8,6 +10,7 @@ from pathlib import Path
 path = Path(sys.argv[1])
 anchor = sys.argv[2] if len(sys.argv) > 2 else "ivf_scan_mfma_h"
 skip = int(sys.argv[3]) if len(sys.argv) > 3 else 5   # anchors skipped (warm-up); then 10 windows
+split = len(sys.argv) > 4 and sys.argv[4] == "split"
 f = next(path.rglob("*kernel_trace.csv"))
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
@@ -18,8 +21,12 @@ cnt = defaultdict(int)
 span = 0.0
 for a, b in wins:
     span += (int(rows[b]["Start_Timestamp"]) - int(rows[a]["Start_Timestamp"])) / 1e3
+    seen = defaultdict(int)
     for r in rows[a:b]:
         name = r["Kernel_Name"].split("(")[0][:70]
+        seen[name] += 1
+        if split and "ivf_scan_mfma_h" in name:
+            name += f" launch {seen[name]}"
         tot[name] += (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
         cnt[name] += 1
 n = len(wins)
