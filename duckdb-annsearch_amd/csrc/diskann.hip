@@ -73,8 +73,9 @@ __global__ void __launch_bounds__(256) dist_rows(const float *__restrict__ queri
 }
 
 // The host BFS's visited sets on the device (vbits != nullptr): one bit per (query, row), vwords words per query.
-// A candidate whose bit was already set (an earlier step of its query, or an earlier slot of the same step) is not
-// evaluated: its output is kVisitedBits, a NaN payload no distance arithmetic produces.
+// A candidate whose bit was already set (an earlier step of its query; the host sends an id once per step, since the
+// slots of one launch mark in no particular order) is not evaluated: its output is kVisitedBits, a NaN payload no
+// distance arithmetic produces.
 constexpr unsigned kVisitedBits = 0x7fc0deadu;
 __device__ __forceinline__ bool visit_first(unsigned *vbits, int64_t vwords, unsigned qi, unsigned id) {
     const unsigned bit = 1u << (id & 31u);
@@ -561,6 +562,21 @@ void host_bfs(DiskDB *db, const uint32_t *adj, int R, const uint32_t *eps, int n
     }
     unsigned *vbits = gv ? db->vbits.get<unsigned>() : nullptr;
     auto visited_mark = [](float v) { return __builtin_bit_cast(uint32_t, v) == kVisitedBits; };
+    // The device marks each slot's candidate with one atomic, in no order among the slots of a launch: of an id that a
+    // row (or the entry points) holds twice, either slot could come back as the fresh one.  The reference's visited
+    // insert runs in neighbour order — the first occurrence wins, and with it the candidate's place among this step's
+    // inserts — so a repeated id goes over once, in its first slot.
+    // (`seen`: a 256-bit filter over the ids already in `slot`; a clear bit proves the id new, a set one is checked.)
+    auto push_once = [](uint32_t *slot, int &cnt, uint32_t id, uint64_t (&seen)[4]) {
+        const uint32_t h = (id * 0x9E3779B1u) >> 24;
+        uint64_t &w = seen[h >> 6];
+        const uint64_t bit = 1ull << (h & 63);
+        if (w & bit)
+            for (int j = 0; j < cnt; ++j)
+                if (slot[j] == id) return;
+        w |= bit;
+        slot[cnt++] = id;
+    };
     SpinPool pool(bfs_threads(nq));
     const int T = pool.size();
     struct Group {
@@ -636,9 +652,14 @@ void host_bfs(DiskDB *db, const uint32_t *adj, int R, const uint32_t *eps, int n
             s.result.reserve(l + 1);
             uint32_t *slot = hid + (size_t)qi * S;
             int cnt = 0;
+            uint64_t seen[4] = {0, 0, 0, 0};
             for (int e = 0; e < n_ep; ++e) {
                 const uint32_t ep = eps[e];
-                if (gv ? ep < N : (s.visited.insert(ep) && ep < N)) slot[cnt++] = ep;
+                if (gv) {
+                    if (ep < N) push_once(slot, cnt, ep, seen);
+                } else if (s.visited.insert(ep) && ep < N) {
+                    slot[cnt++] = ep;
+                }
             }
             for (size_t j = (size_t)cnt; j < S; ++j) slot[j] = 0xffffffffu;
             s.nnew = cnt;
@@ -704,12 +725,13 @@ void host_bfs(DiskDB *db, const uint32_t *adj, int R, const uint32_t *eps, int n
                             s.active = false;
                         } else {
                             const uint32_t *nbr = adj + (size_t)c.id * R;
-                            if (gv) {  // every valid neighbour: the device keeps the visited sets
+                            if (gv) {  // every valid neighbour, once: the device keeps the visited sets
                                 int cnt = 0;
+                                uint64_t seen[4] = {0, 0, 0, 0};
                                 for (int r = 0; r < R; ++r) {
                                     const uint32_t nb = nbr[r];
                                     if (nb == 0xffffffffu) break;  // get_neighbors trims at the first sentinel
-                                    if (nb < N) slot[cnt++] = nb;
+                                    if (nb < N) push_once(slot, cnt, nb, seen);
                                 }
                                 s.nnew = cnt;
                             } else {

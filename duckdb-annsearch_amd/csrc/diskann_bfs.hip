@@ -745,7 +745,8 @@ diskann_bfs(const float *__restrict__ Qs, int nq, int d, const uint8_t *__restri
     }
     if (lane == 0) {
         flags[qi] = flag;
-        atomicAdd(stats + 0, evals);
+        // a flagged query is re-run on the host, which counts its evaluations from the start
+        if (!flag) atomicAdd(stats + 0, evals);
         atomicMax(stats + 1, (unsigned long long)steps);
         atomicAdd(stats + 2, (unsigned long long)steps);
         atomicAdd(stats + 9, sp_hits);

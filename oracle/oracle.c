@@ -546,7 +546,8 @@ void oracle_diskann_search_batch(const float *vecs, const uint8_t *codes, const 
     for (int qi = 0; qi < nq; ++qi) {
         QState *s = &st[qi];
         us_init(&s->visited, l * 2);
-        s->result = (Cand *)malloc((l + 1) * sizeof(Cand));
+        /* more seeds than l stay in result until the first insert truncates it (Vec::truncate) */
+        s->result = (Cand *)malloc(((l > (size_t)n_ep ? l : (size_t)n_ep) + 1) * sizeof(Cand));
         s->rlen = 0;
         s->active = 1;
         /* seed (disk_provider.rs:524-538): push to heap and result, then stable sort result */
@@ -558,7 +559,7 @@ void oracle_diskann_search_batch(const float *vecs, const uint8_t *codes, const 
                 nevals++;
                 Cand c = {dist, ep};
                 mh_push(&s->cands, c);
-                s->result[s->rlen++] = c;  /* n_ep is small (≤ l) */
+                s->result[s->rlen++] = c;
             }
         }
         /* stable insertion sort by partial_cmp on distance */

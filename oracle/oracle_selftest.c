@@ -219,6 +219,15 @@ static void test_diskann(void) {
                     if (t) CHECK(dist[i * k + t - 1] <= dist[i * k + t], "diskann order");
                 }
         }
+    /* more seeds than l: all of them stay in the result until the first insert truncates it to l */
+    {
+        uint32_t many[20];
+        for (int e = 0; e < 20; ++e) many[e] = (uint32_t)(e * 29);
+        oracle_diskann_search_batch(x, NULL, NULL, NULL, N, d, adj, R, many, 20, q, nq, 4, 8, 0, ids, dist, stats);
+        CHECK(stats[0] >= 20 * nq, "diskann seeds > l: every seed evaluated");
+        for (int i = 0; i < nq; ++i)
+            for (int t = 1; t < 4; ++t) CHECK(dist[i * 4 + t - 1] <= dist[i * 4 + t], "diskann seeds > l order");
+    }
     free(x);
     free(q);
     free(adj);

@@ -15,6 +15,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from _bfs_cases import _ragged_graph
 from _data import mt19937_uniform
 
 pytestmark = pytest.mark.gpu
@@ -246,19 +247,6 @@ def test_bfs_many_queries_parallel_host(gpu, oracle, metric, fmt):
     assert abs(st["steps"] - ost["steps"]) <= 2
     # every row sorted ascending (insert_result keeps the list ordered)
     assert np.all(np.diff(dists, axis=1) >= 0)
-
-
-def _ragged_graph(oracle, x, R, rng, extra_random=2):
-    n = len(x)
-    _, nn = oracle.flat_search(x, x, R - extra_random - 2 + 1, 0)
-    adj = np.full((n, R), 0xFFFFFFFF, np.uint32)
-    adj[:, : R - extra_random - 2] = nn[:, 1:]
-    adj[:, R - extra_random - 2: R - 2] = rng.integers(0, n, (n, extra_random))
-    adj[::7, R - 2] = n + 5          # out of range: skipped, not a sentinel
-    adj[::5, 3] = adj[::5, 2]        # duplicate neighbour
-    deg = rng.integers(R // 2, R + 1, n)
-    adj[np.arange(R)[None, :] >= deg[:, None]] = 0xFFFFFFFF
-    return adj
 
 
 @pytest.mark.parametrize("metric", [0, 1])
