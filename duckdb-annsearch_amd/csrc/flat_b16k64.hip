@@ -60,7 +60,7 @@ template <int MBW> struct K64Geom {
 };
 
 // Epilogue of one tile for accumulator row (MB, I).  On entry sm[jb][i] = s = 2·q·x − ‖x‖² (L2; 2·q·x for IP;
-// −inf past N) of the wave's query 16·MB + 4·(lane >> 4) + i and database row x0 + 16·jb + (lane & 15); a row
+// −inf past N: such a row is neither counted nor appended) of the wave's query 16·MB + 4·(lane >> 4) + i and database row x0 + 16·jb + (lane & 15); a row
 // passes its query's bound when s ≥ cth = ‖q‖² − T (L2) or −2·T (IP) — cthm[i] is the lane's own query's (its
 // 16-lane group).  Passing rows (rare) are appended to the query's buffer with key = ‖q‖² − s
 // (L2, clamped at 0) or −s/2 = −q·x (IP); cntv lane j holds the count of the wave's query j (it keeps
@@ -69,7 +69,7 @@ template <bool L2M, int MB, int I, int NJ>
 __device__ __forceinline__ void k64_epilogue_row(const k64_f32x4 (&sm)[NJ], float mxi, const float (&cthm)[4], float qnl,
                                                  int &cntv, int64_t x0, float *__restrict__ cand_d,
                                                  int *__restrict__ cand_i, int64_t cbase, int64_t cq, int cap,
-                                                 int lane, int JB0) {
+                                                 int lane, int JB0, int64_t N) {
     // sm[j] = s of row block JB0 + j (one half of the tile's 16; the halves keep the epilogue's live registers to 32
     // values).  mxi = max over the lane's 8 rows of sm[·][I] (the caller's reduction): one compare for the 8 (NaN
     // never passes: fmaxf drops NaN operands, an all-NaN max compares false)
@@ -101,6 +101,8 @@ __device__ __forceinline__ void k64_epilogue_row(const k64_f32x4 (&sm)[NJ], floa
                 const int jl = __ffs(pml) - 1;
                 pml &= pml - 1;
                 const int jb = JB0 + jl;
+                // a padding row of the last tile (s = −inf) passes only a bound of +inf (cth = −inf): never a candidate
+                if (x0 + 16 * jb + l >= N) continue;
                 float sv = sm[0][I];
 #pragma unroll
                 for (int j = 1; j < NJ; ++j) sv = jl == j ? sm[j][I] : sv;
@@ -434,10 +436,10 @@ flat_bf16_k64(const k64_u32x4 *__restrict__ Qt, const float *__restrict__ qnorm,
                     k64_f32x4 mx = sm[0];
 #pragma unroll
                     for (int j = 1; j < EJ; ++j) mx = __builtin_elementwise_max(mx, sm[j]);
-                    k64_epilogue_row<L2M, MB, 0, EJ>(sm, mx[0], cth[MB], qnl, cntv, x0, cand_d, cand_i, cbase, cq, cap, lane, EJ * hf);
-                    k64_epilogue_row<L2M, MB, 1, EJ>(sm, mx[1], cth[MB], qnl, cntv, x0, cand_d, cand_i, cbase, cq, cap, lane, EJ * hf);
-                    k64_epilogue_row<L2M, MB, 2, EJ>(sm, mx[2], cth[MB], qnl, cntv, x0, cand_d, cand_i, cbase, cq, cap, lane, EJ * hf);
-                    k64_epilogue_row<L2M, MB, 3, EJ>(sm, mx[3], cth[MB], qnl, cntv, x0, cand_d, cand_i, cbase, cq, cap, lane, EJ * hf);
+                    k64_epilogue_row<L2M, MB, 0, EJ>(sm, mx[0], cth[MB], qnl, cntv, x0, cand_d, cand_i, cbase, cq, cap, lane, EJ * hf, N);
+                    k64_epilogue_row<L2M, MB, 1, EJ>(sm, mx[1], cth[MB], qnl, cntv, x0, cand_d, cand_i, cbase, cq, cap, lane, EJ * hf, N);
+                    k64_epilogue_row<L2M, MB, 2, EJ>(sm, mx[2], cth[MB], qnl, cntv, x0, cand_d, cand_i, cbase, cq, cap, lane, EJ * hf, N);
+                    k64_epilogue_row<L2M, MB, 3, EJ>(sm, mx[3], cth[MB], qnl, cntv, x0, cand_d, cand_i, cbase, cq, cap, lane, EJ * hf, N);
                 }
             };
             [&]<int... M>(std::integer_sequence<int, M...>) {
@@ -984,7 +986,8 @@ __device__ __forceinline__ int i8_quant(float x, float s) {
     return s > 0.f ? (int)fminf(fmaxf(rintf(x / s), -127.f), 127.f) : 0;
 }
 
-// one wave per row: scale[row] = max|x| / 127, resid[row] = ‖x − s·x̂‖ (×1.0001: the fp32 sum of d exact-ish squares)
+// one wave per row: scale[row] = max|x| / 127, resid[row] = ‖x − s·x̂‖ (×1.0001: the fp32 sum of d exact-ish squares);
+// +inf for a row that is not entirely finite (a NaN residual would vanish from ivf_max_norm's fmaxf)
 __global__ void __launch_bounds__(256) i8_row_scale(const float *__restrict__ X, int64_t n, int d,
                                                     float *__restrict__ scale, float *__restrict__ resid) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -998,14 +1001,16 @@ __global__ void __launch_bounds__(256) i8_row_scale(const float *__restrict__ X,
     const float s = m > 0.f && m < 3.0e38f ? m / 127.f : 0.f;
     float r2 = 0.f;
     for (int e = lane; e < d; e += 64) {
-        const float r = x[e] - s * (float)i8_quant(x[e], s);
+        // one rounding of the exact difference: x − fl(s·x̂) lost residuals below half an ulp of x (d = 1: resid 0)
+        const float r = fmaf(-s, (float)i8_quant(x[e], s), x[e]);
         r2 = fmaf(r, r, r2);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) r2 += __shfl_xor(r2, o);
     if (lane == 0) {
         scale[row] = s;
-        resid[row] = m < 3.0e38f ? sqrtf(r2) * 1.0001f : __builtin_inff();  // non-finite rows: no bound
+        // non-finite rows: no bound (+inf) — a ±inf element (m = inf) or a NaN one (fmaxf drops it from m; r2 = NaN)
+        resid[row] = m < 3.0e38f && r2 == r2 ? sqrtf(r2) * 1.0001f : __builtin_inff();
     }
 }
 
@@ -1080,14 +1085,15 @@ __global__ void __launch_bounds__(256) i8_query_prep(const float *__restrict__ X
     const float s = m > 0.f && m < 3.0e38f ? m / 127.f : 0.f;
     float r2 = 0.f;
     for (int e = lane; e < d; e += 64) {
-        const float r = x[e] - s * (float)i8_quant(x[e], s);
+        // one rounding of the exact difference: x − fl(s·x̂) lost residuals below half an ulp of x (d = 1: resid 0)
+        const float r = fmaf(-s, (float)i8_quant(x[e], s), x[e]);
         r2 = fmaf(r, r, r2);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) r2 += __shfl_xor(r2, o);
     if (lane == 0) {
         scale[row] = s;
-        resid[row] = m < 3.0e38f ? sqrtf(r2) * 1.0001f : __builtin_inff();
+        resid[row] = m < 3.0e38f && r2 == r2 ? sqrtf(r2) * 1.0001f : __builtin_inff();  // (as i8_row_scale)
     }
     for (int uc = lane; uc < nk * 4; uc += 64) {
         const int kc = uc >> 2, c = uc & 3;
@@ -1357,10 +1363,11 @@ static bool cand_narrow_on(int k) {
     return env && k <= 64;
 }
 
-void launch_flat_cand_bound(const float *cand_d, const int *cand_n, int nsplit, int cap, int64_t nq, int k,
-                            float *bound, hipStream_t st) {
+// narrow: the one-block-per-query narrowed kernels (k ≤ 64), else the one-wave-per-query wave lists
+static void launch_flat_cand_bound_as(bool narrow, const float *cand_d, const int *cand_n, int nsplit, int cap,
+                                      int64_t nq, int k, float *bound, hipStream_t st) {
     if (nq <= 0) return;
-    if (cand_narrow_on(k))
+    if (narrow)
         hipLaunchKernelGGL(flat_cand_bound_nw, dim3((unsigned)nq), dim3(256), 0, st, cand_d, cand_n, nsplit, cap, nq, k,
                            bound);
     else
@@ -1369,16 +1376,147 @@ void launch_flat_cand_bound(const float *cand_d, const int *cand_n, int nsplit, 
     HIPANN_CHECK(hipGetLastError());
 }
 
-void launch_flat_cand_select(const float *cand_d, const int *cand_i, const int *cand_n, int nsplit, int cap, int64_t nq,
-                             int k, float *out_d, int *out_i, int *nflag, int *flagged, hipStream_t st) {
+static void launch_flat_cand_select_as(bool narrow, const float *cand_d, const int *cand_i, const int *cand_n,
+                                       int nsplit, int cap, int64_t nq, int k, float *out_d, int *out_i, int *nflag,
+                                       int *flagged, hipStream_t st) {
     if (nq <= 0) return;
-    if (cand_narrow_on(k))
+    if (narrow)
         hipLaunchKernelGGL(flat_cand_select_nw, dim3((unsigned)nq), dim3(256), 0, st, cand_d, cand_i, cand_n, nsplit, cap,
                            nq, k, out_d, out_i, nflag, flagged);
     else
         hipLaunchKernelGGL(flat_cand_select, dim3((unsigned)ceil_div(nq, 4)), dim3(256), 0, st, cand_d, cand_i, cand_n,
                            nsplit, cap, nq, k, out_d, out_i, nflag, flagged);
     HIPANN_CHECK(hipGetLastError());
+}
+
+void launch_flat_cand_bound(const float *cand_d, const int *cand_n, int nsplit, int cap, int64_t nq, int k,
+                            float *bound, hipStream_t st) {
+    launch_flat_cand_bound_as(cand_narrow_on(k), cand_d, cand_n, nsplit, cap, nq, k, bound, st);
+}
+
+void launch_flat_cand_select(const float *cand_d, const int *cand_i, const int *cand_n, int nsplit, int cap, int64_t nq,
+                             int k, float *out_d, int *out_i, int *nflag, int *flagged, hipStream_t st) {
+    launch_flat_cand_select_as(cand_narrow_on(k), cand_d, cand_i, cand_n, nsplit, cap, nq, k, out_d, out_i, nflag,
+                               flagged, st);
+}
+
+// ---- test hooks (tests/test_flat_passes_gpu.py): the bounded passes' pieces on device pointers through the
+// product's launchers, synchronous on the null stream; 0 on success, -1 on a bad shape or a HIP error ----------
+static int dbg_sync() {
+    if (hipGetLastError() != hipSuccess) return -1;
+    return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+template <typename F> static int dbg_guard(F f) {
+    try {
+        return f();
+    } catch (...) {
+        (void)hipGetLastError();
+        return -1;
+    }
+}
+
+extern "C" int64_t hipann_debug_flat_i8_img_bytes(int64_t n, int d, int R) {
+    return n > 0 && d > 0 && R > 0 ? (int64_t)flat_i8_img_bytes(n, d, R) : -1;
+}
+extern "C" int64_t hipann_debug_flat_bf16_img_bytes(int64_t n, int d, int R) {
+    return n > 0 && d > 0 && R > 0 ? (int64_t)flat_bf16_img_bytes(n, d, R) : -1;
+}
+extern "C" int hipann_debug_flat_i8_nk(int d) { return d > 0 ? flat_i8_nk(d) : -1; }
+
+// Image prep of fp32 rows X[n × d] in tiles of R rows: scale[n], resid[n], norm[n] (‖x‖², optional), the int8 image
+// img_i8 (flat_i8_img_bytes) by the fused kernel (fused = 1: i8_query_prep) or by i8_row_scale + i8_tile_rows (with
+// launch_row_norms for norm), and the bf16 image img_b16 (flat_bf16_img_bytes, optional).
+extern "C" int hipann_debug_flat_image_prep(const float *X, int64_t n, int d, int R, int fused, float *norm,
+                                            float *scale, float *resid, void *img_i8, void *img_b16) {
+    if (!X || n <= 0 || d <= 0 || R <= 0 || R % 64 != 0 || !scale || !resid || !img_i8) return -1;
+    return dbg_guard([&] {
+        if (fused) {
+            launch_i8_query_prep(X, n, d, norm, scale, resid, R, img_i8, 0);
+        } else {
+            if (norm) launch_row_norms(X, n, d, norm, 0);
+            launch_i8_row_scale(X, n, d, scale, resid, 0);
+            launch_i8_tile_rows(X, scale, n, d, R, img_i8, 0);
+        }
+        if (img_b16) launch_b16_tile_rows(X, n, d, R, img_b16, 0);
+        return dbg_sync();
+    });
+}
+
+// One launch of flat_bf16_k64 over fp32 queries Q[nq × d] and rows X[N × d], prepared as flat_shard_launch prepares
+// them: the rows' tiled image (bf16, or int8 with its scales by i8_row_scale + i8_tile_rows: ensure_i8_image), the
+// queries' (bf16, or int8 by the fused i8_query_prep), ‖q‖² and ‖x‖² by launch_row_norms for L2.  i8: 0 = bf16,
+// 1 = int8, 2 = int8 with the query scales withheld (the launcher must refuse).  keys = 1: cand_d is the dense
+// nq × N key matrix; else the pass's candidate buffers [nq · nsplit · cap] and counts [nq · nsplit].
+extern "C" int hipann_debug_flat_pass(const float *Q, int64_t nq, const float *X, int64_t N, int d, int metric, int i8,
+                                      int keys, int nsplit, int64_t tiles_per_split, int64_t tile_begin,
+                                      int64_t tile_end, const float *bound, float *cand_d, int *cand_i, int *cand_n,
+                                      int cap, int resume) {
+    if (!Q || !X || nq <= 0 || N <= 0 || d <= 0 || (metric != kL2 && metric != kIP) || i8 < 0 || i8 > 2) return -1;
+    if (nsplit < 1 || tiles_per_split < 1 || tile_begin < 0 || tile_end < tile_begin || !cand_d) return -1;
+    if (!keys && (!bound || !cand_i || !cand_n || cap <= 0)) return -1;
+    const int R = flat_bf16_tile_rows();
+    const int nk = i8 ? flat_i8_nk(d) : (d + 31) / 32;
+    if (!flat_bf16_k64_supported(nk, 64)) return -1;  // an odd chunk count: the product takes the 32-dim list kernel
+    return dbg_guard([&] {
+        int dev = 0;
+        HIPANN_CHECK(hipGetDevice(&dev));
+        DevBuf qimg, ximg, qn, xn, qsc, qres, xsc, xres;
+        const float *qnp = nullptr, *xnp = nullptr, *qscp = nullptr, *xscp = nullptr;
+        if (metric == kL2) {
+            qn.ensure(sizeof(float) * (size_t)nq, dev);
+            xn.ensure(sizeof(float) * (size_t)N, dev);
+            launch_row_norms(X, N, d, xn.get<float>(), 0);
+            qnp = qn.get<float>();
+            xnp = xn.get<float>();
+        }
+        if (i8) {
+            ximg.ensure(flat_i8_img_bytes(N, d, R), dev);
+            xsc.ensure(sizeof(float) * (size_t)N, dev);
+            xres.ensure(sizeof(float) * (size_t)N, dev);
+            launch_i8_row_scale(X, N, d, xsc.get<float>(), xres.get<float>(), 0);
+            launch_i8_tile_rows(X, xsc.get<float>(), N, d, R, ximg.p, 0);
+            qimg.ensure(flat_i8_img_bytes(nq, d, K64_QM), dev);
+            qsc.ensure(sizeof(float) * (size_t)nq, dev);
+            qres.ensure(sizeof(float) * (size_t)nq, dev);
+            launch_i8_query_prep(Q, nq, d, qn.get<float>(), qsc.get<float>(), qres.get<float>(), K64_QM, qimg.p, 0);
+            xscp = xsc.get<float>();
+            qscp = i8 == 2 ? nullptr : qsc.get<float>();
+        } else {
+            ximg.ensure(flat_bf16_img_bytes(N, d, R), dev);
+            launch_b16_tile_rows(X, N, d, R, ximg.p, 0);
+            qimg.ensure(flat_bf16_img_bytes(nq, d, K64_QM), dev);
+            launch_b16_tile_rows(Q, nq, d, K64_QM, qimg.p, 0);
+            if (metric == kL2) launch_row_norms(Q, nq, d, qn.get<float>(), 0);
+        }
+        launch_flat_bf16_k64(qimg.p, qnp, nq, ximg.p, xnp, N, nk, metric, (int)ceil_div(nq, (int64_t)K64_QM), nsplit,
+                             tiles_per_split, tile_begin, tile_end, bound, cand_d, cand_i, cand_n, cap, resume != 0,
+                             keys != 0, 0, qscp, xscp);
+        return dbg_sync();  // (before the scratch buffers go)
+    });
+}
+
+// flat_cand_bound over given candidate buffers: the narrowed kernel (narrow = 1) or the wave list (0)
+extern "C" int hipann_debug_flat_cand_bound(const float *cand_d, const int *cand_n, int nsplit, int cap, int64_t nq,
+                                            int k, float *bound, int narrow) {
+    if (!cand_d || !cand_n || !bound || nsplit < 1 || cap < 1 || nq <= 0 || k < 1 || k > 64) return -1;
+    return dbg_guard([&] {
+        launch_flat_cand_bound_as(narrow != 0, cand_d, cand_n, nsplit, cap, nq, k, bound, 0);
+        return dbg_sync();
+    });
+}
+
+// flat_cand_select likewise; nflag is reset first, as flat_shard_launch does
+extern "C" int hipann_debug_flat_cand_select(const float *cand_d, const int *cand_i, const int *cand_n, int nsplit,
+                                             int cap, int64_t nq, int k, float *out_d, int *out_i, int *nflag,
+                                             int *flagged, int narrow) {
+    if (!cand_d || !cand_i || !cand_n || !out_d || !out_i || !nflag || !flagged) return -1;
+    if (nsplit < 1 || cap < 1 || nq <= 0 || k < 1 || k > 64) return -1;
+    return dbg_guard([&] {
+        HIPANN_CHECK(hipMemsetAsync(nflag, 0, sizeof(int), 0));
+        launch_flat_cand_select_as(narrow != 0, cand_d, cand_i, cand_n, nsplit, cap, nq, k, out_d, out_i, nflag, flagged,
+                                   0);
+        return dbg_sync();
+    });
 }
 
 }  // namespace hipann

@@ -483,6 +483,16 @@ static std::vector<int64_t> flat_pass_plan(int64_t tps, int64_t nsplit, int64_t 
     return best;
 }
 
+// Per-(query, split) candidate capacity of a plan pb from its expected fill: pass 0 admits ≈ k·rows₀/S per cell
+// (keys ≤ the k-th of S sample rows), pass p ≈ k·rows_p/(nsplit·rows_<p) (the k-th over all earlier rows); 3× + 32
+// of headroom (clustered 12.5M IP rows peaked at 2.3× the mean), a multiple of 32, at most 2²⁰.
+static int flat_pass_cap(const std::vector<int64_t> &pb, int64_t nsplit, int64_t tile_rows, int64_t sample, int k) {
+    double fill = k * (double)(pb[1] * tile_rows) / (double)sample;
+    for (size_t p = 1; p + 1 < pb.size(); ++p)
+        fill += k * (double)(pb[p + 1] - pb[p]) / ((double)pb[p] * (double)nsplit);
+    return (int)std::min<double>(1 << 20, (double)ceil_div((int64_t)(3.0 * fill + 32.0), 32) * 32);
+}
+
 // The flag count of the launch phase's bound check into the shard's pinned host word (a copy kernel through its
 // device mapping, no DMA round trip), then a fresh token into the word after it; the host reads the count after
 // its next synchronisation with `st` (or once the token arrives, wait_posted).
@@ -782,13 +792,7 @@ static void flat_shard_launch(FlatIndex &ix, FlatShard &sh, int64_t nq, const fl
             ? std::vector<int64_t>(pass_div > 1 && tps / pass_div >= 1 ? std::vector<int64_t>{0, tps / pass_div, tps}
                                                                      : std::vector<int64_t>{0, tps})
             : flat_pass_plan(tps, nsplit, flat_bf16_tile_rows(), sample, k, nq);
-        // per-(query, split) candidate capacity from the expected fill: pass 0 admits ≈ k·rows₀/S per cell (keys ≤
-        // the k-th of S sample rows), pass p ≈ k·rows_p/(nsplit·rows_<p) (the k-th over all earlier rows); 3× + 32
-        // of headroom (clustered 12.5M IP rows peaked at 2.3× the mean), a multiple of 32.
-        double fill = k * (double)(pb[1] * flat_bf16_tile_rows()) / (double)sample;
-        for (size_t p = 1; p + 1 < pb.size(); ++p)
-            fill += k * (double)(pb[p + 1] - pb[p]) / ((double)pb[p] * (double)nsplit);
-        const int cap = (int)std::min<double>(1 << 20, (double)ceil_div((int64_t)(3.0 * fill + 32.0), 32) * 32);
+        const int cap = flat_pass_cap(pb, nsplit, flat_bf16_tile_rows(), sample, k);
         const size_t ncell = (size_t)nq * nsplit;
         // the keys-mode seed pass runs per chunk of 1024 queries (4 query tiles) through one 64 MB slab of keys
         const int64_t seed_qc = 1024;
@@ -1489,3 +1493,21 @@ double hipann_last_kernel_ms(void *h, int which) {
 }
 
 }  // extern "C"
+
+// test hook (tests/test_flat_pass_cases.py): the bounded passes' plan for tps tiles per split — its boundaries into
+// bounds[0 .. *nb) (at most 7) and the candidate capacity flat_shard_launch derives from them (no device needed);
+// 0 on success, -1 on a bad shape
+extern "C" int hipann_debug_flat_pass_plan(int64_t tps, int64_t nsplit, int64_t sample, int k, int64_t nq,
+                                           int64_t *bounds, int *nb, int *cap) {
+    try {
+        if (tps < 1 || nsplit < 1 || sample < 256 || k < 1 || nq < 1 || !bounds || !nb || !cap) return -1;
+        const std::vector<int64_t> pb = hipann::flat_pass_plan(tps, nsplit, hipann::flat_bf16_tile_rows(), sample, k, nq);
+        if (pb.size() < 2 || pb.size() > 7) return -1;
+        for (size_t i = 0; i < pb.size(); ++i) bounds[i] = pb[i];
+        *nb = (int)pb.size();
+        *cap = hipann::flat_pass_cap(pb, nsplit, hipann::flat_bf16_tile_rows(), sample, k);
+        return 0;
+    } catch (...) {
+        return -1;
+    }
+}
