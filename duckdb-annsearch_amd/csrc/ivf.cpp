@@ -229,7 +229,10 @@ float shard_i8_rxmax(IvfShard &sh, hipStream_t st) {
     unsigned bits = 0;
     HIPANN_CHECK(hipMemcpyAsync(&bits, sh.nflag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIPANN_CHECK(hipStreamSynchronize(st));
-    std::memcpy(&sh.i8_rxmax, &bits, sizeof(float));  // (the plane's entries already carry the ×1.0001 of their fp32 sums)
+    // (the plane's entries already carry the ×1.0001 of their fp32 sums); a NaN entry (magnitude bits above +inf's)
+    // reads as +inf: the rerank's `rxmax >= 0` must pick the Cauchy-Schwarz bound, whose non-finite E flags the query
+    if (bits > 0x7f800000u) bits = 0x7f800000u;
+    std::memcpy(&sh.i8_rxmax, &bits, sizeof(float));
     return sh.i8_rxmax;
 }
 
@@ -476,7 +479,8 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
     // certificate's lower-bound keys (int8 image, L2), a list of more than one chunk, and chunk-0 entries the seed
     // kernel's select holds.  HIPANN_IVF_SEED=0 (A/B): the single launch.
     static const bool seed_env = [] { const char *e = std::getenv("HIPANN_IVF_SEED"); return !e || std::atoi(e) != 0; }();
-    const bool seeded = seed_env && i8 && metric == kL2 && sub && sh.max_nch > 1 && ivf_seed_supported(np, kslot);
+    const bool seed_on = sh.dbg_seed < 0 ? seed_env : sh.dbg_seed != 0;  // (a test's per-handle override)
+    const bool seeded = seed_on && i8 && metric == kL2 && sub && sh.max_nch > 1 && ivf_seed_supported(np, kslot);
     if (form_override < 0) ix.last_seeded = seeded ? 1 : 0;
     const bool tiled = form == kFormDecomposed || ivf_form_split(form);  // the matrix-core scans
     const int group = i8 ? ivf_mfma_i8_group(d) : half ? ivf_mfma_h_group(d) : ivf_group_size(form, d);
@@ -678,6 +682,18 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
                             sh.slot_off.get<int>(), nlist, np, nq, k, max_items, qbound, sh.part_d.get<float>(),
                             sh.part_i.get<int>(), st);
     }
+    if (form_override < 0) {  // what the scan saw (hipann_debug_ivf_info / _read)
+        sh.dbg_nq = nq;
+        sh.dbg_np = np;
+        sh.dbg_kslot = kslot;
+        sh.dbg_sub = sub ? 1 : 0;
+        sh.dbg_img = i8 ? 2 : half ? 1 : 0;
+        sh.dbg_seeded = seeded ? 1 : 0;
+        sh.dbg_kfilt = exact ? kfilt : 0;
+        sh.dbg_cand_off = seeded ? (int64_t)np * nq * kslot : -1;
+        sh.dbg_qn = qn;  // (the int8 L2 scan's key term is qhn2 instead; the rerank reads this one)
+    }
+    if (sh.dbg_stop) return;  // a test reads the scan's buffers as they are
     // 4. merge each query's partial lists (kFormSplit2Exact: merge + exact rerank + bound check)
     if (!exact) {
         ScopedTiming t(ix.timer_merge, st);
@@ -1635,6 +1651,100 @@ int hipann_ivf_get_form(void *h) {
     auto *ix = static_cast<IndexBase *>(h);
     if (ix->kind != Kind::IVF) return -1;
     return static_cast<IvfIndex *>(ix)->form;
+}
+
+// ---- test hooks (tests/test_ivf_scan_gpu.py): a single-shard IVF handle's scan stages as the product runs them ------
+static IvfShard *dbg_shard(void *h) {
+    if (!h) return nullptr;
+    auto *ix = static_cast<IndexBase *>(h);
+    if (ix->kind != Kind::IVF) return nullptr;
+    auto *vx = static_cast<IvfIndex *>(ix);
+    return vx->shards.size() == 1 ? vx->shards[0].get() : nullptr;
+}
+
+// stop: 1 = ivf_shard_search returns after its scan step (D / I stay unwritten), 0 = the normal search.
+// seed: the seeded int8 scan by HIPANN_IVF_SEED (-1), off (0), on (1).  -1 on a bad handle or value.
+int hipann_debug_ivf_set(void *h, int stop, int seed) {
+    IvfShard *sh = dbg_shard(h);
+    if (!sh || stop < 0 || stop > 1 || seed < -1 || seed > 1) return -1;
+    std::lock_guard<std::mutex> lk(static_cast<IvfIndex *>(h)->mu);
+    sh->dbg_stop = stop;
+    sh->dbg_seed = seed;
+    return 0;
+}
+
+// A scalar of the shard or of its last search by name; 0 on success, -1 on a bad handle or an unknown name.
+int hipann_debug_ivf_info(void *h, const char *name, double *out) {
+    IvfShard *sh = dbg_shard(h);
+    if (!sh || !name || !out) return -1;
+    auto *vx = static_cast<IvfIndex *>(h);
+    std::lock_guard<std::mutex> lk(vx->mu);
+    const std::string s(name);
+    const int d = vx->d;
+    if (s == "half_state") *out = sh->half_state;
+    else if (s == "half_es") *out = sh->half_es;
+    else if (s == "half_rxmax") *out = sh->half_rxmax;
+    else if (s == "half_nsup") *out = (double)(ivf_half_pass_bytes(d) / 2048);
+    else if (s == "i8_state") *out = sh->i8_state;
+    else if (s == "i8_rxmax") *out = sh->i8_rxmax;
+    else if (s == "i8_nsup") *out = (double)(ivf_i8_pass_bytes(d) / 2048);
+    else if (s == "xmax2") *out = sh->xmax2;
+    else if (s == "max_nch") *out = sh->max_nch;
+    else if (s == "n") *out = (double)sh->n;
+    else if (s == "nq") *out = (double)sh->dbg_nq;
+    else if (s == "nprobe") *out = sh->dbg_np;
+    else if (s == "kslot") *out = sh->dbg_kslot;
+    else if (s == "kfilt") *out = sh->dbg_kfilt;
+    else if (s == "sub") *out = sh->dbg_sub;
+    else if (s == "image") *out = sh->dbg_img;
+    else if (s == "seeded") *out = sh->dbg_seeded;
+    else if (s == "cand_off") *out = (double)sh->dbg_cand_off;
+    else if (s == "group") *out = sh->dbg_img == 2 ? ivf_mfma_i8_group(d) : sh->dbg_img == 1 ? ivf_mfma_h_group(d) : 0;
+    else return -1;
+    return 0;
+}
+
+// A shard buffer by name: copies min(cap, its bytes) into host memory `out` (fill >= 0: instead sets every byte of the
+// buffer to `fill`, for sentinels) after the device has drained.  Returns the buffer's allocated bytes (0: not
+// allocated), or -1 on a bad handle, an unknown name or a HIP error.
+int64_t hipann_debug_ivf_read(void *h, const char *name, void *out, int64_t cap, int fill) {
+    IvfShard *sh = dbg_shard(h);
+    if (!sh || !name || cap < 0 || (cap > 0 && !out) || fill > 255) return -1;
+    auto *vx = static_cast<IvfIndex *>(h);
+    std::lock_guard<std::mutex> lk(vx->mu);
+    const std::string s(name);
+    const void *p = nullptr;
+    size_t bytes = 0;
+    const std::pair<const char *, const DevBuf *> tab[] = {
+        {"codes_h", &sh->codes_h}, {"codes_i8", &sh->codes_i8}, {"xs8", &sh->xs8}, {"xr8", &sh->xr8},
+        {"tpass_off", &sh->tpass_off}, {"xnorm", &sh->xnorm}, {"hsplit", &sh->hsplit}, {"hits", &sh->hits},
+        {"hres", &sh->hres}, {"qi8", &sh->qi8}, {"qs8", &sh->qs8}, {"qres8", &sh->qres8}, {"qhn2", &sh->qhn2},
+        {"qhn", &sh->qhn}, {"cnt", &sh->cnt}, {"bucket_off", &sh->bucket_off}, {"item_off", &sh->item_off},
+        {"goff", &sh->goff}, {"bucket", &sh->bucket}, {"slot_off", &sh->slot_off}, {"part_d", &sh->part_d},
+        {"part_i", &sh->part_i}, {"qbound", &sh->qbound}, {"run_cnt", &sh->run_cnt}, {"list_len", &sh->list_len},
+        {"list_off", &sh->list_off}, {"nflag", &sh->nflag}, {"flagged", &sh->flagged}};
+    bool found = false;
+    for (const auto &e : tab)
+        if (s == e.first) {
+            p = e.second->p;
+            bytes = e.second->bytes;
+            found = true;
+        }
+    if (s == "qn") {  // the ‖q‖² of the last search's queries (the coarse quantizer's or the shard's buffer)
+        p = sh->dbg_qn;
+        bytes = p ? sizeof(float) * (size_t)sh->dbg_nq : 0;
+        found = true;
+    }
+    if (!found) return -1;
+    if (!p) return 0;
+    DeviceGuard g(sh->device);
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (fill >= 0) {
+        if (s == "qn" || hipMemset(const_cast<void *>(p), fill, bytes) != hipSuccess) return -1;
+    } else if (cap > 0) {
+        if (hipMemcpy(out, p, std::min<size_t>((size_t)cap, bytes), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    }
+    return (int64_t)bytes;
 }
 
 }  // extern "C"

@@ -2659,6 +2659,34 @@ void launch_ivf_rerank(const float *pd, const int *pi, const int *slot_off, int 
     HIPANN_CHECK(hipGetLastError());
 }
 
+// Test hook (tests/test_ivf_scan_gpu.py): launch_ivf_rerank over the caller's device arrays, synchronous on the null
+// stream, with no re-run buffers (fpd = nullptr): a flagged query writes its uncertified answer and is listed in
+// flagged[0 .. *nflag), and no fallback runs.  nflag is reset first, as the plan does.  Arguments as the launcher's
+// (qres / probes / list_off / qbound / qnorm / ids / slot_off / seed_cnt may be null where it allows).  0 on success, -1
+// on a shape the launcher rejects or a HIP error.
+extern "C" int hipann_debug_ivf_rerank(const float *pd, const int *pi, const int *slot_off, int nprobe, int64_t nq, int k,
+                                       int kout, int metric, const float *Q, const float *codes, int d,
+                                       const int64_t *ids, int64_t nrows, int64_t label_offset, float xmax2, float *D,
+                                       int64_t *I, int *nflag, int *flagged, float eps, float rxmax, const float *qres,
+                                       const int64_t *probes, const int64_t *list_off, int nlist,
+                                       const unsigned *qbound, const float *qnorm, int kslot, int sub, int i8_l2,
+                                       const int *seed_cnt) {
+    if (!pd || !pi || !Q || !codes || !D || !I || !nflag || !flagged || nq <= 0 || d <= 0 || nprobe < 1 || nrows < 0)
+        return -1;
+    if ((metric != kL2 && metric != kIP) || (probes && (!list_off || nlist < 1))) return -1;
+    try {
+        HIPANN_CHECK(hipMemsetAsync(nflag, 0, sizeof(int), 0));
+        launch_ivf_rerank(pd, pi, slot_off, nprobe, nq, k, kout, metric, Q, codes, d, ids, nrows, label_offset, xmax2, D,
+                          I, nflag, flagged, 0, eps, rxmax, qres, probes, list_off, nlist, qbound, qnorm, kslot, sub,
+                          nullptr, nullptr, nullptr, nullptr, 0, i8_l2, seed_cnt);
+        if (hipGetLastError() != hipSuccess) return -1;
+        return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+    } catch (...) {
+        (void)hipGetLastError();
+        return -1;
+    }
+}
+
 // tuning builds (HIPANN_RR_PROF): the wide rerank's wave-0 clock sums per phase — [0] setup, [1] candidate loads,
 // [5] bound count, [2] compaction / search + sort, [3] distances, [4] order + ties, [8] bound check + write — and the
 // counts [6] compaction path, [9] list path, [7] queries (16 entries); reset after reading

@@ -1066,7 +1066,8 @@ __device__ __forceinline__ uint4 mi_units(const float *x, int dim0, int d, float
     }
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
-// max|x| / 127 of a row (0 for a zero or non-finite row: its units are 0 and its residual +inf, see mi_resid)
+// max|x| / 127 of a row; 0 for a zero row, -1 for a row with a ±inf element.  fmaxf drops a NaN element from the
+// maximum: the callers find it in the residual sum, which is then NaN (ivf_tile_i8: residual +inf and zero units; the queries: residual +inf)
 __device__ __forceinline__ float mi_row_scale(const float *x, int d, int lane) {
     float mx = 0.f;
     for (int e = lane; e < d; e += 64) mx = fmaxf(mx, fabsf(x[e]));
@@ -1100,19 +1101,18 @@ ivf_tile_i8(const float *__restrict__ codes, const int64_t *__restrict__ list_of
         if (row < rend) {
             const float *x = codes + row * (int64_t)d;
             s = mi_row_scale(x, d, lane);
-            if (s < 0.f) {  // non-finite row: zero units, residual +inf
-                s = 0.f;
-                res = __builtin_inff();
-            } else {
-                float r2 = 0.f;
-                for (int e = lane; e < d; e += 64) {
-                    const float t = x[e] - s * (float)mi_quant(x[e], s);
-                    r2 = fmaf(t, t, r2);
-                }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) r2 += __shfl_xor(r2, o);
-                res = sqrtf(r2) * 1.0001f;
+            const bool fin = s >= 0.f;  // no ±inf element (a NaN one: fmaxf drops it from the maximum; r2 = NaN)
+            if (!fin) s = 0.f;
+            float r2 = 0.f;
+            for (int e = lane; e < d; e += 64) {
+                // one rounding of the exact difference: x − fl(s·x̂) lost residuals below half an ulp of x (d = 1: 0)
+                const float t = fmaf(-s, (float)mi_quant(x[e], s), x[e]);
+                r2 = fmaf(t, t, r2);
             }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) r2 += __shfl_xor(r2, o);
+            res = fin && r2 == r2 ? sqrtf(r2) * 1.0001f : __builtin_inff();
+            if (res == __builtin_inff()) s = 0.f;  // non-finite row: zero units, residual +inf
         }
         if (lane == 0) {
             sc[rr] = s;
@@ -1150,7 +1150,8 @@ __global__ void __launch_bounds__(256) ivf_split_queries_i8(const float *__restr
     if (!fin) s = 0.f;
     float r2 = 0.f, h2 = 0.f;
     for (int e = lane; e < d; e += 64) {
-        const float qh = s * (float)mi_quant(x[e], s), rr = x[e] - qh;
+        // (the residual in one rounding, as ivf_tile_i8)
+        const float qh = s * (float)mi_quant(x[e], s), rr = fmaf(-s, (float)mi_quant(x[e], s), x[e]);
         r2 = fmaf(rr, rr, r2);
         h2 = fmaf(qh, qh, h2);
     }
@@ -1161,7 +1162,7 @@ __global__ void __launch_bounds__(256) ivf_split_queries_i8(const float *__restr
     }
     if (lane == 0) {
         qs8[q] = s;
-        qres8[q] = fin ? sqrtf(r2) * 1.0001f : __builtin_inff();
+        qres8[q] = fin && r2 == r2 ? sqrtf(r2) * 1.0001f : __builtin_inff();  // (a NaN element: r2 = NaN)
         qhn2[q] = h2;
         qhn[q] = sqrtf(h2) * 1.0001f;
     }

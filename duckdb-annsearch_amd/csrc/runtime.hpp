@@ -442,6 +442,15 @@ struct IvfShard {
     uint64_t fb_seq = 0, fb_seen = 0;
     bool count_only = false;
     DevBuf probe_D, probe_I;
+    // test hooks (hipann_debug_ivf_*, tests/test_ivf_scan_gpu.py).  dbg_stop: ivf_shard_search returns after its scan
+    // step (no merge, no rerank; D / I stay unwritten).  dbg_seed: the seeded int8 scan by HIPANN_IVF_SEED (-1), off
+    // (0) or on (1).  The last search's shape as the scan saw it: queries, probes, entries per slot, sub-lists, image
+    // (0 none, 1 fp16, 2 int8), seeded, the first entry of the candidate runs inside part_d / part_i (-1: none) and
+    // the ‖q‖² (L2 key term) the scan read.
+    int dbg_stop = 0, dbg_seed = -1;
+    int64_t dbg_nq = 0, dbg_cand_off = -1;
+    int dbg_np = 0, dbg_kslot = 0, dbg_sub = 0, dbg_img = 0, dbg_seeded = 0, dbg_kfilt = 0;
+    const float *dbg_qn = nullptr;
     // an append's staging (hipann_ivf_add): the new rows grouped by list, labels, physical destinations, norms,
     // the tiled passes they touch, and the new rows' maxima (‖x‖², |x|, fp16 residual²)
     DevBuf app_rows, app_norm, app_assign, app_up, app_stat;
