@@ -501,6 +501,17 @@ static void flag_readback(FlatShard &sh, hipStream_t st) {
     launch_post_words(sh.nflag.p, sh.h_nflag.p, 1, ++sh.flag_seq, st);
 }
 
+// The exact Flat forms' rerank over the shard's rows (ivf_rerank_topk, slot lists query-major): the caller adds the
+// lists (pd, pi, nprobe = lists per query), the filter depth k and the image's residual terms.
+static IvfRerankArgs flat_rerank_args(FlatShard &sh, int64_t nq, int kout, int metric, const float *xq, int d,
+                                      float xmax2, float *D, int64_t *I) {
+    IvfRerankArgs a;
+    a.nq = nq, a.kout = kout, a.metric = metric, a.Q = xq, a.codes = sh.xb, a.d = d, a.nrows = sh.n;
+    a.label_offset = sh.label_offset, a.xmax2 = xmax2, a.D = D, a.I = I;
+    a.nflag = sh.nflag.get<int>(), a.flagged = sh.flagged.get<int>();
+    return a;
+}
+
 // Launch phase of a shard search: every kernel of the search up to the exact forms' flag count, enqueued on `st`
 // without a host synchronisation.  pend says what flat_shard_finish has left to do (kNone: the output is complete
 // once `st` drains).
@@ -581,9 +592,9 @@ static void flat_shard_launch(FlatIndex &ix, FlatShard &sh, int64_t nq, const fl
             float *md = sh.mid_d.get<float>();
             int *mi = reinterpret_cast<int *>(sh.mid_i.p);
             launch_flat_i8_group_merge(sh.part_d.get<float>(), sh.part_i.get<int>(), (int)nw, (int)nq, G, md, mi, st);
-            launch_ivf_rerank(md, mi, nullptr, G, nq, kf, kout, metric, xq, sh.xb, d, nullptr, sh.n, sh.label_offset,
-                              xmax2, D, I, sh.nflag.get<int>(), sh.flagged.get<int>(), st, kSplit2Eps, sh.i8_rxmax,
-                              sh.qres.get<float>());
+            IvfRerankArgs a = flat_rerank_args(sh, nq, kout, metric, xq, d, xmax2, D, I);
+            a.pd = md, a.pi = mi, a.nprobe = G, a.k = kf, a.rxmax = sh.i8_rxmax, a.qres = sh.qres.get<float>();
+            launch_ivf_rerank(a, st);
         }
         if (form_override < 0) {
             ix.last_form = kFlatI8Exact;
@@ -929,10 +940,10 @@ static void flat_shard_launch(FlatIndex &ix, FlatShard &sh, int64_t nq, const fl
     {
         ScopedTiming t(ix.timer_merge, st);
         // (int8: the row term and each query's own residual from the int8 images; qres makes the rerank read them)
-        launch_ivf_rerank(sh.part_d.get<float>(), sh.part_i.get<int>(), nullptr, (int)nsplit, nq, k, kout, metric, xq,
-                          sh.xb, d, nullptr, sh.n, sh.label_offset, xmax2, D, I, sh.nflag.get<int>(),
-                          sh.flagged.get<int>(), st, kSplit2Eps, form == kFlatBf16Exact || i8 ? rxmax : -1.f,
-                          i8 ? sh.qres.get<float>() : nullptr);
+        IvfRerankArgs a = flat_rerank_args(sh, nq, kout, metric, xq, d, xmax2, D, I);
+        a.pd = sh.part_d.get<float>(), a.pi = sh.part_i.get<int>(), a.nprobe = (int)nsplit, a.k = k;
+        a.rxmax = form == kFlatBf16Exact || i8 ? rxmax : -1.f, a.qres = i8 ? sh.qres.get<float>() : nullptr;
+        launch_ivf_rerank(a, st);
     }
     pend = FlatPending{};
     pend.kind = FlatPending::kExact;

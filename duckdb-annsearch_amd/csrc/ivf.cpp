@@ -273,9 +273,8 @@ static bool host_fallback() {
     return v;
 }
 
-// One shard: queries on the shard's device → D/I (nq × kout) on the same device, async on `st`.
 // max‖x‖² of the shard (once): the rerank's error bound
-float shard_xmax2(IvfShard &sh, int d, hipStream_t st) {
+static float shard_xmax2(IvfShard &sh, int d, hipStream_t st) {
     if (sh.xmax2 >= 0.f) return sh.xmax2;
     const float *xn = sh.xnorm.get<float>();
     if (!xn) {
@@ -327,389 +326,424 @@ static unsigned long long *auto8_host_word(IvfShard &sh) {
     return static_cast<unsigned long long *>(host_device_ptr(sh.fb_host.p));
 }
 
-// Probation: the batch has been answered through the fp16 image; the same batch runs once more on the same stream
-// through the int8 image into scratch outputs, counting only (no flagged query is re-run, nothing the caller sees is
-// written).  The flag count is read back — probation's one host synchronisation — and decides by the byte rule.
-static void auto8_probation(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, int k, int kout, hipStream_t st,
-                            const int64_t *probes_in) {
-    sh.auto8_live = sh.live;
-    sh.auto8_over = 0;
-    sh.auto8 = -1;
-    if (!ensure_i8_codes(sh, ix.d, ix.nlist, st)) return;
-    sh.probe_D.ensure(sizeof(float) * (size_t)nq * kout, sh.device);
-    sh.probe_I.ensure(sizeof(int64_t) * (size_t)nq * kout, sh.device);
-    sh.count_only = true;
-    try {
-        TimerPause p0(ix.timer_main), p1(ix.timer_merge);
-        ivf_shard_search(ix, sh, nq, xq, k, kout, sh.probe_D.get<float>(), sh.probe_I.get<int64_t>(), st, kFormI8Exact,
-                         probes_in);
-    } catch (...) {
-        sh.count_only = false;
-        throw;
-    }
-    sh.count_only = false;
-    int nf = 0;
-    HIPANN_CHECK(hipMemcpyAsync(&nf, sh.nflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPANN_CHECK(hipStreamSynchronize(st));
-    if (!auto8_over_rule(nf, std::min(ix.nprobe, ix.nlist), ix.nlist, sh.live, ix.d)) sh.auto8 = 1;
+namespace {
+
+// ---- the scan mode: what a batch's requested form resolves to ("Scan modes", has the table) ----
+// Everything ivf_resolve_mode reads; no pointer, no shard, no environment.
+struct IvfModeIn {
+    int form = kFormHalfExact;  // the requested form (IvfForm)
+    bool is_override = false;   // ... from the caller's options (a re-run), not the index
+    int metric = kL2, d = 0, k = 0, kout = 0;
+    int np = 0;                 // min(nprobe, nlist)
+    int max_nch = 1;
+    bool aligned16 = true;      // the queries and the codes both start on 16 bytes
+    bool host_fb = false;       // HIPANN_IVF_HOST_FALLBACK
+    bool seed_on = true;        // HIPANN_IVF_SEED / the test hook's override
+    bool use_int8 = false;      // the fp16 form filters through the int8 image (ivf_choose_filter_image)
+};
+
+struct IvfScanMode {
+    int form = kFormDirect;       // the scan that runs (an image scan: kFormSplit2)
+    int last_form = kFormDirect;  // what hipann_last_search_path reports
+    bool exact = false;           // 16-deep filter + exact rerank
+    int image = 0;                // 0 none, 1 fp16, 2 int8
+    bool as_half = false;         // image 2 standing in for the fp16 form's image
+    bool sub = false;             // every wave's list a sub-list of the slot
+    int kscan = 0;                // per-list k of the scan (the output keeps kout)
+    int kslot = 0, kfilt = 0;     // entries per (query, probe, chunk) slot; the rerank's filter depth
+    bool seeded = false, tiled = false, cert8 = false, bigk = false;
+    int group = 0;                // queries per work item (packed for the image scans)
+};
+
+// The filter-image choice applies to: the index's own fp16 form, L2 (the per-row certificate), kout <= kRerankMaxK
+// without a sub-list request, a shape the int8 scan holds, the device fallback, and a shard whose int8 image exists or
+// can still be built.
+bool ivf_filter_image_eligible(const IvfModeIn &in, int64_t nrows, int i8_state) {
+    return !in.is_override && in.form == kFormHalfExact && in.metric == kL2 && in.kout <= kRerankMaxK && in.k <= 64 &&
+           !in.host_fb && ivf_mfma_i8_supported(in.d, kRerankK) && nrows > 0 && i8_state >= 0;
 }
 
-void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, int k, int kout, float *D, int64_t *I,
-                      hipStream_t st, int form_override, const int64_t *probes_in) {
-    RoctxRange r_all("hipann.ivf.search_shard");
-    DeviceGuard g(sh.device);
-    const int nlist = ix.nlist, d = ix.d, metric = ix.metric;
-    const int np = std::min(ix.nprobe, nlist);
-    const float out_sign = metric == kIP ? -1.f : 1.f;
-    // k > 64: per-slot direct scan + LDS sort (ivf_scan_slot_bigk), same plan / merge
-    const bool bigk = k > 64;
-    if (nq <= 0) return;
-    // 1. coarse quantizer (FAISS: quantizer->search(n, x, nprobe) — Flat rules incl. nq < 20)
-    sh.coarse_d.ensure((size_t)nq * np * sizeof(float), sh.device);
-    sh.coarse_i.ensure((size_t)nq * np * sizeof(int64_t), sh.device);
-    HIPANN_REQUIRE((int64_t)nq * np < (int64_t)0x7fffffff, "nq * nprobe too large");
-    sh.slot_off.ensure(sizeof(int) * ((size_t)nq * np + 1), sh.device);
-    // per-list counts and fill cursors, double-buffered by batch parity (ivf_planfill_q zeroes the other
-    // parity's pair for the next batch; ivf_plan_q zeroes its own after use) — zeroed once per list count
+// ensure(image) builds (or finds) the tiled image 1 = fp16 / 2 = int8 and says whether it is usable; it is asked only
+// once every other condition for that image holds, and a refusal (a non-finite row) falls through to the next form.
+template <typename Ensure>
+IvfScanMode ivf_resolve_mode(const IvfModeIn &in, Ensure &&ensure) {
+    IvfScanMode m;
+    const int d = in.d, kout = in.kout;
+    int req = in.form;
+    m.bigk = in.k > 64;  // per-slot direct scan + LDS sort (ivf_scan_slot_bigk), same plan / merge
+    m.as_half = in.use_int8 && ensure(2);
+    if (m.as_half) req = kFormI8Exact;
+    const bool sub_req = (((req == kFormHalfExact || req == kFormSplit2Exact) && kout > kRerankMaxK) ||
+                          req == kFormI8Exact) && kout <= kIvfSubMaxK && !m.bigk;
+    if (req == kFormHalfExact) {
+        if ((kout <= kRerankMaxK || sub_req) && !m.bigk && ivf_mfma_h_supported(d, kRerankK) && ensure(1)) m.image = 1;
+        req = kFormSplit2Exact;
+    } else if (req == kFormI8Exact) {
+        if (sub_req && ivf_mfma_i8_supported(d, kRerankK) && ensure(2)) m.image = 2;
+        req = kFormSplit2Exact;
+    }
+    const bool want_exact = req == kFormSplit2Exact;
+    if (want_exact) req = kout <= kRerankMaxK || sub_req ? kFormSplit2 : kFormSplit3;
+    m.kscan = want_exact && req == kFormSplit2 ? kRerankK : in.k;
+    m.form = req != kFormDirect && !m.bigk && ivf_dot_supported(d, in.aligned16) ? req : kFormDirect;
+    if (m.image) m.form = kFormSplit2;  // any d: the images are zero-padded to whole super-steps
+    if (!m.image && ivf_form_split(m.form) && !ivf_mfma_bf_supported(d, in.aligned16, m.kscan, ivf_form_terms(m.form)))
+        m.form = kFormDecomposed;
+    if (m.form == kFormDecomposed && !ivf_mfma_supported(d, in.aligned16, m.kscan)) m.form = kFormDecomposedValu;
+    m.exact = want_exact && m.form == kFormSplit2;
+    m.sub = m.exact && sub_req;
+    m.kslot = m.sub ? ivf_scan_sublists() * m.kscan : m.kscan;
+    m.kfilt = m.sub ? (m.image == 2 ? 64 : std::min(64, std::max(kout + 4, 2 * kout))) : m.kscan;
+    m.last_form = !m.exact ? m.form
+                  : m.image == 2 ? (m.as_half ? kFormHalfExact : kFormI8Exact)
+                  : m.image == 1 ? kFormHalfExact : kFormSplit2Exact;
+    m.cert8 = m.image == 2 && in.metric == kL2;
+    m.seeded = in.seed_on && m.cert8 && m.sub && in.max_nch > 1 && ivf_seed_supported(in.np, m.kslot);
+    m.tiled = m.form == kFormDecomposed || ivf_form_split(m.form);  // the matrix-core scans
+    m.group = m.image == 2 ? ivf_mfma_i8_group(d) : m.image == 1 ? ivf_mfma_h_group(d) : ivf_group_size(m.form, d);
+    return m;
+}
+
+// The fp16 form's filter image for this batch (hipann_ivf_set_filter_image): mode 1 always takes the int8 image; auto
+// (2) from kAutoI8MinBatch queries on, per shard: untested -> probation (the batch is answered through the fp16 image
+// and judged afterwards), on -> off after two consecutive batches over the byte rule, read from fb_host (the previous
+// int8 batch's flag count: no host synchronisation), and probation again once the shard has grown by a quarter.
+struct IvfImageChoice {
+    bool use_int8, probation;
+};
+IvfImageChoice ivf_choose_filter_image(IvfShard &sh, bool eligible, int mode, int64_t nq, int np, int nlist, int d) {
+    if (!eligible || mode == 0 || (mode == 2 && nq < kAutoI8MinBatch)) return {false, false};
+    if (mode == 1) return {true, false};
+    if (sh.auto8 == 1 && sh.fb_host.p) {
+        const uint64_t w = __atomic_load_n(sh.fb_host.get<uint64_t>(), __ATOMIC_RELAXED);
+        if (w != sh.fb_seen) {  // a batch not yet judged
+            sh.fb_seen = w;
+            sh.auto8_over = auto8_over_rule((int64_t)(w & 0xffffffffu), np, nlist, sh.live, d) ? sh.auto8_over + 1 : 0;
+            if (sh.auto8_over >= 2) sh.auto8 = -1;
+        }
+    }
+    if (sh.auto8 != 0 && sh.live >= sh.auto8_live + sh.auto8_live / 4 + 1) sh.auto8 = 0;
+    return {sh.auto8 == 1, sh.auto8 == 0};
+}
+
+// ---- one batch on one shard: the stages of ivf_shard_search, in their order on the stream ----
+struct IvfBatch {
+    IvfIndex &ix;
+    IvfShard &sh;
+    const int64_t nq;
+    const float *const xq;
+    const int k_user, kout;
+    float *const D;
+    int64_t *const I;
+    const hipStream_t st;
+    const IvfSearchOpts &opts;
+    const int np;  // min(nprobe, nlist)
+    IvfScanMode m;
+    bool probation = false;
+    FlatShard &qsh;  // the coarse quantizer's shard (its qn holds ‖q‖² of the batch when the preparation wrote it)
+    // this batch's and the next one's plan counts / fill cursors (double-buffered by batch parity)
+    int *ccnt_cur = nullptr, *ccnt_next = nullptr, *cur_cur = nullptr, *cur_next = nullptr;
+    float xmax2 = 0.f, rxmax8 = -1.f;
+    unsigned *qbound = nullptr;
+    const float *qn = nullptr;
+    float *cand_d = nullptr;  // the seeded scan: the queries' candidate runs (inside part_d / part_i)
+    int *cand_i = nullptr;
+    IvfPlanView plan() const {
+        return {sh.list_off.get<int64_t>(), sh.list_len.get<int>(), sh.cnt.get<int>(), sh.bucket_off.get<int>(),
+                sh.item_off.get<int>(), sh.bucket.get<int>(), sh.slot_off.get<int>(), sh.goff.get<int>(), ix.nlist, np};
+    }
+};
+
+// The coarse step's outputs and the plan's per-list counts and fill cursors, double-buffered by batch parity
+// (ivf_planfill_q zeroes the other parity's pair for the next batch; ivf_plan_q zeroes its own after use) — zeroed
+// once per list count.
+void ivf_plan_scratch(IvfBatch &b) {
+    IvfShard &sh = b.sh;
+    const int nlist = b.ix.nlist;
+    sh.coarse_d.ensure((size_t)b.nq * b.np * sizeof(float), sh.device);
+    sh.coarse_i.ensure((size_t)b.nq * b.np * sizeof(int64_t), sh.device);
+    HIPANN_REQUIRE((int64_t)b.nq * b.np < (int64_t)0x7fffffff, "nq * nprobe too large");
+    sh.slot_off.ensure(sizeof(int) * ((size_t)b.nq * b.np + 1), sh.device);
     if (!sh.ccnt.p || !sh.cursor2.p || sh.plan_nlist != nlist) {
         sh.ccnt.ensure(sizeof(int) * 2 * kPlanCopies * (size_t)nlist, sh.device);
         sh.cursor2.ensure(sizeof(int) * 2 * kPlanCopies * (size_t)nlist, sh.device);
-        HIPANN_CHECK(hipMemsetAsync(sh.ccnt.p, 0, sizeof(int) * 2 * kPlanCopies * (size_t)nlist, st));
-        HIPANN_CHECK(hipMemsetAsync(sh.cursor2.p, 0, sizeof(int) * 2 * kPlanCopies * (size_t)nlist, st));
+        HIPANN_CHECK(hipMemsetAsync(sh.ccnt.p, 0, sizeof(int) * 2 * kPlanCopies * (size_t)nlist, b.st));
+        HIPANN_CHECK(hipMemsetAsync(sh.cursor2.p, 0, sizeof(int) * 2 * kPlanCopies * (size_t)nlist, b.st));
         sh.plan_nlist = nlist;
         sh.plan_batch = 0;
     }
     const int par = (int)(sh.plan_batch & 1u);
     const size_t pstride = (size_t)kPlanCopies * nlist;  // one parity's [copy][list] counts / cursors
-    int *ccnt_cur = sh.ccnt.get<int>() + par * pstride, *ccnt_next = sh.ccnt.get<int>() + (1 - par) * pstride;
-    int *cur_cur = sh.cursor2.get<int>() + par * pstride, *cur_next = sh.cursor2.get<int>() + (1 - par) * pstride;
-    sh.qtot.ensure(sizeof(int) * (size_t)nq, sh.device);
-    // this batch's counts must be zero on entry; the coarse select's count step adds to them, so if anything
-    // throws before the plan has consumed them, zero them again on the way out
-    struct CcntReset {
-        int *p;
-        int nlist;
-        hipStream_t st;
-        bool armed;
-        ~CcntReset() {
-            if (armed && std::uncaught_exceptions() > 0)
-                (void)hipMemsetAsync(p, 0, sizeof(int) * kPlanCopies * (size_t)nlist, st);
-        }
-    } ccnt_reset{ccnt_cur, nlist, st, true};
-    // the decomposed form needs float4 rows; other shapes take the direct kernel (also on the GPU)
-    // the decomposed forms need float4 rows (else the direct kernel, also on the GPU); the MFMA kernel
-    // keeps 16-lane lists (k <= 16) and the item's queries in LDS (else the VALU decomposed kernel)
-    int req = form_override >= 0 ? form_override : ix.form;
-    // The exact fp16 form may filter through the int8 image instead (hipann_ivf_set_filter_image): the same exact
-    // rerank certifies either filter, so the results are the same rows and the same direct-form distances, and the int8
-    // image is half the bytes.  Eligible: L2 (the per-row certificate), kout <= kRerankMaxK without a sub-list
-    // request, a shape the int8 scan holds, the device fallback.  Mode 1 always takes it; auto (2) from kAutoI8MinBatch
-    // queries on, per shard: untested -> on / off by probation (below, after this batch's answer), on -> off after two
-    // consecutive batches over the byte rule, read from fb_host (the previous int8 batch's flag count: no host
-    // synchronisation), and probation again once the shard has grown by a quarter.
-    bool as_half = false, probation = false;
-    if (form_override < 0 && req == kFormHalfExact && metric == kL2 && kout <= kRerankMaxK && !bigk && !host_fallback() &&
-        ivf_mfma_i8_supported(d, kRerankK) && sh.n > 0 && sh.i8_state >= 0) {
-        const int mode = filter_image_mode(ix);
-        if (mode == 1) {
-            as_half = true;
-        } else if (mode == 2 && nq >= kAutoI8MinBatch) {
-            if (sh.auto8 == 1 && sh.fb_host.p) {
-                const uint64_t w = __atomic_load_n(sh.fb_host.get<uint64_t>(), __ATOMIC_RELAXED);
-                if (w != sh.fb_seen) {  // a batch not yet judged
-                    sh.fb_seen = w;
-                    sh.auto8_over = auto8_over_rule((int64_t)(w & 0xffffffffu), np, nlist, sh.live, d) ? sh.auto8_over + 1 : 0;
-                    if (sh.auto8_over >= 2) sh.auto8 = -1;
-                }
-            }
-            if (sh.auto8 != 0 && sh.live >= sh.auto8_live + sh.auto8_live / 4 + 1) sh.auto8 = 0;
-            as_half = sh.auto8 == 1;
-            probation = sh.auto8 == 0;
-        }
-        if (as_half && !ensure_i8_codes(sh, d, nlist, st)) as_half = false;  // a non-finite row: the fp16 path's rules
-        if (as_half) req = kFormI8Exact;
+    b.ccnt_cur = sh.ccnt.get<int>() + par * pstride, b.ccnt_next = sh.ccnt.get<int>() + (1 - par) * pstride;
+    b.cur_cur = sh.cursor2.get<int>() + par * pstride, b.cur_next = sh.cursor2.get<int>() + (1 - par) * pstride;
+    sh.qtot.ensure(sizeof(int) * (size_t)b.nq, sh.device);
+}
+
+// this batch's counts must be zero on entry; the coarse select's count step adds to them, so if anything throws
+// before the plan has consumed them, zero them again on the way out
+struct CcntReset {
+    int *p;
+    int nlist;
+    hipStream_t st;
+    bool armed;
+    ~CcntReset() {
+        if (armed && std::uncaught_exceptions() > 0) (void)hipMemsetAsync(p, 0, sizeof(int) * kPlanCopies * (size_t)nlist, st);
     }
-    if (form_override < 0) ix.last_filter_image = 0;
-    // request_k above kRerankMaxK on the exact forms (k + |tombstones|, faiss_index.cpp:713-715): the scans keep
-    // their 16-lane lists but write every wave's list as a sub-list of the slot (mf_finish_item), and the rerank
-    // takes the kf best candidates, certified against its kf-th merged key AND the smallest full sub-list's
-    // 16th key (every pruned row lies above both).  Beyond kIvfSubMaxK: the 3-term scan.
-    // kFormI8Exact always takes the sub-lists (its int8 filter needs the 64-deep rerank, ivf_mfma.hip)
-    const bool sub_req = (((req == kFormHalfExact || req == kFormSplit2Exact) && kout > kRerankMaxK) ||
-                          req == kFormI8Exact) && kout <= kIvfSubMaxK && !bigk;
-    // kFormHalfExact: the fp16-image scan as the filter of the same rerank (else kFormSplit2Exact); kFormI8Exact: the
-    // int8-image scan (else kFormSplit2Exact too)
-    bool half = false, i8 = false;
-    if (req == kFormHalfExact) {
-        half = (kout <= kRerankMaxK || sub_req) && !bigk && ivf_mfma_h_supported(d, kRerankK) &&
-               ensure_half_codes(sh, d, nlist, st);
-        req = kFormSplit2Exact;
-    } else if (req == kFormI8Exact) {
-        i8 = sub_req && ivf_mfma_i8_supported(d, kRerankK) && ensure_i8_codes(sh, d, nlist, st);
-        req = kFormSplit2Exact;
-    }
-    const bool img = half || i8;  // a tiled fp16 / int8 image and the one-term item scan
-    // kFormSplit2Exact: the 2-term scan keeps kRerankK per list (per wave with sub-lists), the rerank makes the
-    // results exact
-    const bool want_exact = req == kFormSplit2Exact;
-    if (want_exact) req = kout <= kRerankMaxK || sub_req ? kFormSplit2 : kFormSplit3;
-    const int k_user = k;
-    const int kscan = want_exact && req == kFormSplit2 ? kRerankK : k;
-    int form = req != kFormDirect && !bigk && ivf_dot_supported(xq, d, sh.codes) ? req : kFormDirect;
-    if (img) form = kFormSplit2;  // any d: the images are zero-padded to whole super-steps
-    if (!img && ivf_form_split(form) && !ivf_mfma_bf_supported(xq, d, sh.codes, kscan, ivf_form_terms(form)))
-        form = kFormDecomposed;
-    if (form == kFormDecomposed && !ivf_mfma_supported(xq, d, sh.codes, kscan)) form = kFormDecomposedValu;
-    const bool exact = want_exact && form == kFormSplit2;
-    const bool sub = exact && sub_req;
-    k = kscan;  // per-list k of the scan (the output keeps kout)
-    // entries per (query, probe, chunk) slot, and the rerank's filter depth
-    const int kslot = sub ? ivf_scan_sublists() * k : k;
-    const int kfilt = sub ? (i8 ? 64 : std::min(64, std::max(kout + 4, 2 * kout))) : k;
-    if (form_override < 0) {
-        ix.last_form = exact ? (i8 ? (as_half ? kFormHalfExact : kFormI8Exact) : half ? kFormHalfExact : kFormSplit2Exact) : form;
-        ix.last_filter_image = exact && i8 ? 1 : 0;
-        ix.last_kfilt = exact ? kfilt : 0;
-        ix.last_sublists = sub ? ivf_scan_sublists() : 0;
-    }
-    // The seeded int8 scan: the chunk-0 items first, every wave's list a sub-list of the pair's slot;
-    // then the 64 best of a query's chunk-0 entries, whose 64th key is min'ed into the query's bound
-    // (ivf_seed_bound); then the other items under that bound, sub-lists again (so the rerank's bound B — the 64th
-    // candidate key or the smallest full sub-list's 16th — is the single launch's).  Needs the per-row
-    // certificate's lower-bound keys (int8 image, L2), a list of more than one chunk, and chunk-0 entries the seed
-    // kernel's select holds.  HIPANN_IVF_SEED=0 (A/B): the single launch.
+};
+
+// The filter image, the mode (building an image at its first use) and the index's record of it.
+void ivf_pick_mode(IvfBatch &b) {
+    IvfIndex &ix = b.ix;
+    IvfShard &sh = b.sh;
+    const int nlist = ix.nlist, d = ix.d;
+    // HIPANN_IVF_SEED=0 (A/B): the single launch
     static const bool seed_env = [] { const char *e = std::getenv("HIPANN_IVF_SEED"); return !e || std::atoi(e) != 0; }();
-    const bool seed_on = sh.dbg_seed < 0 ? seed_env : sh.dbg_seed != 0;  // (a test's per-handle override)
-    const bool seeded = seed_on && i8 && metric == kL2 && sub && sh.max_nch > 1 && ivf_seed_supported(np, kslot);
-    if (form_override < 0) ix.last_seeded = seeded ? 1 : 0;
-    const bool tiled = form == kFormDecomposed || ivf_form_split(form);  // the matrix-core scans
-    const int group = i8 ? ivf_mfma_i8_group(d) : half ? ivf_mfma_h_group(d) : ivf_group_size(form, d);
-    float xmax2 = 0.f;
-    // the int8 image's L2 certificate: lower-bound scan keys from every row's own residual (ivf_rerank_topk); IP
-    // keeps the Cauchy-Schwarz bound with the largest row residual
-    const bool cert8 = i8 && metric == kL2;
-    float rxmax8 = -1.f;
-    if (exact) {  // max‖x‖² (once per row set; nflag is its scratch, so before the plan resets the flag count)
-        xmax2 = shard_xmax2(sh, d, st);
-        if (i8 && !cert8) rxmax8 = shard_i8_rxmax(sh, st);
+    IvfModeIn in;
+    in.is_override = b.opts.form_override >= 0;
+    in.form = in.is_override ? b.opts.form_override : ix.form;
+    in.metric = ix.metric, in.d = d, in.k = b.k_user, in.kout = b.kout, in.np = b.np, in.max_nch = sh.max_nch;
+    in.aligned16 = (uintptr_t)b.xq % 16 == 0 && (uintptr_t)sh.codes % 16 == 0;
+    in.host_fb = host_fallback();
+    in.seed_on = sh.dbg_seed < 0 ? seed_env : sh.dbg_seed != 0;  // (a test's per-handle override)
+    const IvfImageChoice c = ivf_choose_filter_image(sh, ivf_filter_image_eligible(in, sh.n, sh.i8_state),
+                                                     filter_image_mode(ix), b.nq, b.np, nlist, d);
+    in.use_int8 = c.use_int8;
+    b.probation = c.probation;
+    b.m = ivf_resolve_mode(in, [&](int image) {
+        return image == 2 ? ensure_i8_codes(sh, d, nlist, b.st) : ensure_half_codes(sh, d, nlist, b.st);
+    });
+    if (!b.opts.record()) return;
+    const IvfScanMode &m = b.m;
+    ix.last_form = m.last_form;
+    ix.last_filter_image = m.exact && m.image == 2 ? 1 : 0;
+    ix.last_kfilt = m.exact ? m.kfilt : 0;
+    ix.last_sublists = m.sub ? ivf_scan_sublists() : 0;
+    ix.last_seeded = m.seeded ? 1 : 0;
+}
+
+// The rerank's bounds and flags, the queries' bound words, and the batch's query preparation — one launch before the
+// coarse step: the fp16 query terms, 1/(t·s) and the split residuals, or the int8 queries (units, scales, residuals),
+// with ‖q‖² (row_norms_f32's bits) for the coarse quantizer and the scan.
+void ivf_prepare_queries(IvfBatch &b) {
+    IvfShard &sh = b.sh;
+    const IvfScanMode &m = b.m;
+    const int d = b.ix.d;
+    const int64_t nq = b.nq;
+    if (m.exact) {  // max‖x‖² (once per row set; nflag is its scratch, so before the plan resets the flag count)
+        b.xmax2 = shard_xmax2(sh, d, b.st);
+        // the int8 image's L2 certificate reads every row's own residual (ivf_rerank_topk); IP keeps the
+        // Cauchy-Schwarz bound with the largest row residual
+        if (m.image == 2 && !m.cert8) b.rxmax8 = shard_i8_rxmax(sh, b.st);
         sh.nflag.ensure(sizeof(int), sh.device);
         sh.flagged.ensure(sizeof(int) * (size_t)nq, sh.device);
     }
-    unsigned *qbound = nullptr;
-    if (tiled) {  // every query's bound starts at +inf (order-preserving bits 0xff800000), set by the plan
+    if (m.tiled) {  // every query's bound starts at +inf (order-preserving bits 0xff800000), set by the plan
         sh.qbound.ensure(sizeof(unsigned) * (size_t)nq, sh.device);
-        qbound = sh.qbound.get<unsigned>();
+        b.qbound = sh.qbound.get<unsigned>();
     }
-    // the batch's query preparation, one launch before the coarse step (fp16 form): the fp16 query terms, 1/(t·s),
-    // the split residuals and ‖q‖² (row_norms_f32's bits) for the coarse quantizer and the scan
-    FlatShard &qsh0 = *sh.quant->shards[0];
-    if (half) {
+    if (!m.image) return;
+    float *qn_out = nullptr;
+    if (b.ix.metric == kL2) {  // the quantizer's BLAS-form paths (nq >= 20) and the scan's L2 keys read ‖q‖²
+        b.qsh.qn.ensure(sizeof(float) * (size_t)nq, sh.device);
+        qn_out = b.qsh.qn.get<float>();
+    }
+    if (m.image == 1) {
         sh.hsplit.ensure((size_t)ivf_half_qsplit_bytes(nq, d), sh.device);
         sh.hits.ensure(sizeof(float) * (size_t)nq, sh.device);
         sh.hres.ensure(sizeof(float) * 2 * (size_t)nq, sh.device);  // two- and one-term split residuals
-        float *qn_out = nullptr;
-        if (metric == kL2) {  // the quantizer's BLAS-form paths (nq >= 20) and the scan's L2 keys read ‖q‖²
-            qsh0.qn.ensure(sizeof(float) * (size_t)nq, sh.device);
-            qn_out = qsh0.qn.get<float>();
-        }
         RoctxRange rr("hipann.ivf.prepare");
-        launch_ivf_split_queries_h(xq, nq, d, sh.half_es, sh.hsplit.p, sh.hits.get<float>(), sh.hres.get<float>(), qn_out,
-                                   st);
-        qsh0.qn_given = qn_out ? xq : nullptr;
-        qsh0.qn_given_nq = nq;
-    } else if (i8) {
-        // the int8 queries (units, scales, residuals) and ‖q‖² (row_norms_f32 itself: the coarse step's bits)
+        launch_ivf_split_queries_h(b.xq, nq, d, sh.half_es, sh.hsplit.p, sh.hits.get<float>(), sh.hres.get<float>(), qn_out,
+                                   b.st);
+    } else {
         sh.qi8.ensure((size_t)ivf_i8_qimg_bytes(nq, d), sh.device);
         sh.qs8.ensure(sizeof(float) * (size_t)nq, sh.device);
         sh.qres8.ensure(sizeof(float) * (size_t)nq, sh.device);
         sh.qhn2.ensure(sizeof(float) * (size_t)nq, sh.device);
         sh.qhn.ensure(sizeof(float) * (size_t)nq, sh.device);
-        float *qn_out = nullptr;
-        if (metric == kL2) {
-            qsh0.qn.ensure(sizeof(float) * (size_t)nq, sh.device);
-            qn_out = qsh0.qn.get<float>();
-            launch_row_norms(xq, nq, d, qn_out, st);
-        }
+        if (qn_out) launch_row_norms(b.xq, nq, d, qn_out, b.st);  // (row_norms_f32 itself: the coarse step's bits)
         RoctxRange rr("hipann.ivf.prepare");
-        launch_ivf_split_queries_i8(xq, nq, d, sh.qi8.p, sh.qs8.get<float>(), sh.qres8.get<float>(),
-                                    sh.qhn2.get<float>(), sh.qhn.get<float>(), st);
-        qsh0.qn_given = qn_out ? xq : nullptr;
-        qsh0.qn_given_nq = nq;
+        launch_ivf_split_queries_i8(b.xq, nq, d, sh.qi8.p, sh.qs8.get<float>(), sh.qres8.get<float>(),
+                                    sh.qhn2.get<float>(), sh.qhn.get<float>(), b.st);
     }
+    b.qsh.qn_given = qn_out ? b.xq : nullptr;
+    b.qsh.qn_given_nq = nq;
+}
+
+// 1. coarse quantizer (FAISS: quantizer->search(n, x, nprobe) — Flat rules incl. nq < 20), 2. list-major work plan
+void ivf_coarse_and_plan(IvfBatch &b) {
+    IvfShard &sh = b.sh;
+    const int nlist = b.ix.nlist, np = b.np;
+    const int64_t nq = b.nq;
     // the plan's per-query count step rides on the coarse probe select when that path is taken
-    IvfPlanHook hook{sh.list_len.get<int>(), nlist, ivf_chunk_rows(), ccnt_cur, sh.slot_off.get<int>(),
+    IvfPlanHook hook{sh.list_len.get<int>(), nlist, ivf_chunk_rows(), b.ccnt_cur, sh.slot_off.get<int>(),
                      sh.qtot.get<int>(), false};
-    FlatShard &qsh = *sh.quant->shards[0];
     // HIPANN_IVF_SELECT_HOOK=0 (A/B): the count step in its own launch (ivf_count_q) instead of the select's tail
     static const bool hook_env = [] { const char *e = std::getenv("HIPANN_IVF_SELECT_HOOK"); return !e || std::atoi(e); }();
-    if (probes_in) {
+    if (b.opts.probes_in) {
         // the probe lists come from the caller (the coarse step partitioned over ranks, hipann_ivf_coarse_device +
         // one all-gather): no quantizer launch; the plan counts the probes itself
-        HIPANN_CHECK(hipMemcpyAsync(sh.coarse_i.p, probes_in, sizeof(int64_t) * (size_t)nq * np, hipMemcpyDeviceToDevice,
-                                    st));
+        HIPANN_CHECK(hipMemcpyAsync(sh.coarse_i.p, b.opts.probes_in, sizeof(int64_t) * (size_t)nq * np,
+                                    hipMemcpyDeviceToDevice, b.st));
     } else {
         RoctxRange rr("hipann.ivf.coarse");
-        qsh.plan_hook = ivf_plan_query_major() && hook_env ? &hook : nullptr;
-        CoarseKeysScope ck(qsh);
+        b.qsh.plan_hook = ivf_plan_query_major() && hook_env ? &hook : nullptr;
+        CoarseKeysScope ck(b.qsh);
         try {
-            flat_shard_search(*sh.quant, qsh, nq, xq, np, np, sh.coarse_d.get<float>(), sh.coarse_i.get<int64_t>(), st);
+            flat_shard_search(*sh.quant, b.qsh, nq, b.xq, np, np, sh.coarse_d.get<float>(), sh.coarse_i.get<int64_t>(), b.st);
         } catch (...) {
-            qsh.plan_hook = nullptr;
-            qsh.qn_given = nullptr;
+            b.qsh.plan_hook = nullptr;
+            b.qsh.qn_given = nullptr;
             throw;
         }
     }
-    qsh.plan_hook = nullptr;
-    qsh.qn_given = nullptr;
-    // 2. list-major work plan
+    b.qsh.plan_hook = nullptr;
+    b.qsh.qn_given = nullptr;
     sh.cnt.ensure(sizeof(int) * (nlist + 1), sh.device);
     sh.bucket_off.ensure(sizeof(int) * (nlist + 1), sh.device);
     sh.item_off.ensure(sizeof(int) * (nlist + 1), sh.device);
     sh.goff.ensure(sizeof(int) * (nlist + 1), sh.device);
     sh.bucket.ensure(sizeof(int) * (size_t)nq * np, sh.device);
-    HIPANN_REQUIRE((int64_t)nq * np < (int64_t)0x7fffffff, "nq * nprobe too large");
-    sh.slot_off.ensure(sizeof(int) * ((size_t)nq * np + 1), sh.device);
-    {
     RoctxRange rr("hipann.ivf.plan");
-    launch_ivf_plan(sh.coarse_i.get<int64_t>(), nq, np, sh.list_len.get<int>(), nlist, group, sh.cnt.get<int>(),
-                    sh.bucket_off.get<int>(), sh.item_off.get<int>(), cur_cur, sh.bucket.get<int>(),
-                    sh.slot_off.get<int>(), st, exact ? sh.nflag.get<int>() : nullptr, qbound, ccnt_cur,
-                    sh.qtot.get<int>(), hook.done, ccnt_next, cur_next, sh.goff.get<int>());
-    }
+    launch_ivf_plan(sh.coarse_i.get<int64_t>(), nq, np, sh.list_len.get<int>(), nlist, b.m.group, sh.cnt.get<int>(),
+                    sh.bucket_off.get<int>(), sh.item_off.get<int>(), b.cur_cur, sh.bucket.get<int>(),
+                    sh.slot_off.get<int>(), b.st, b.m.exact ? sh.nflag.get<int>() : nullptr, b.qbound, b.ccnt_cur,
+                    sh.qtot.get<int>(), hook.done, b.ccnt_next, b.cur_next, sh.goff.get<int>());
     sh.plan_batch++;
-    ccnt_reset.armed = false;
-    // 3. scan: one k-list per (query, probe, row chunk) slot — every slot is written by exactly one item
-    // (the seeded scan: the pairs' chunk-0 slots, then the queries' candidate slots — one more per query, see below)
-    const size_t parts = ((size_t)np * nq * sh.max_nch + (seeded ? (size_t)np * nq + (size_t)nq : 0)) * kslot;
+}
+
+// the scan's L2 key term ‖q‖² (nullptr: the direct form, or IP)
+const float *ivf_query_norms(IvfBatch &b) {
+    IvfShard &sh = b.sh;
+    if (b.m.form == kFormDirect || b.ix.metric != kL2) return nullptr;
+    if (b.opts.probes_in && b.m.image) return b.qsh.qn.get<float>();  // the query preparation wrote ‖q‖² there
+    // the coarse quantizer's ‖q‖² of the same queries, written by THIS call's coarse step (with probes_in the
+    // quantizer did not run, and a cached pointer match may name a buffer whose contents changed)
+    if (!b.opts.probes_in && b.qsh.qn_of == b.xq && b.qsh.qn_nq == b.nq) return b.qsh.qn.get<float>();
+    sh.qn.ensure(sizeof(float) * (size_t)b.nq, sh.device);
+    launch_row_norms(b.xq, b.nq, b.ix.d, sh.qn.get<float>(), b.st);
+    return sh.qn.get<float>();
+}
+
+// The seeded int8 scan: the chunk-0 items first, every wave's list a sub-list of the pair's slot; then
+// the 64 best of a query's chunk-0 entries, whose 64th key is min'ed into the query's bound (ivf_seed_bound); then the
+// other items under that bound, sub-lists again (so the rerank's bound B — the 64th candidate key or the smallest full
+// sub-list's 16th — is the single launch's).  The chunk-0 slots (one per pair) take the head of part_d / part_i, the
+// queries' candidate slots (common.hpp ivf_seed_run_slot) the rest: a query's run is its seed list, then the rows the
+// second launch's waves append under run_cnt[q] — room for every (pair, chunk >= 1) sub-list in full, so no append can
+// overflow; the rerank reads kSeedK + run_cnt[q] entries.
+void ivf_scan_seeded(IvfBatch &b, IvfImageScanArgs a) {
+    IvfShard &sh = b.sh;
+    const int nlist = b.ix.nlist, np = b.np, kslot = b.m.kslot, group = b.m.group;
+    const int64_t nq = b.nq;
+    HIPANN_REQUIRE((int64_t)np * nq * sh.max_nch + nq < (int64_t)0x7fffffff, "too many candidate slots");
+    HIPANN_REQUIRE((int64_t)np * sh.max_nch * kslot < (int64_t)0x7fffffff, "candidate run too long");
+    sh.run_cnt.ensure(sizeof(int) * (size_t)nq, sh.device);
+    b.cand_d = sh.part_d.get<float>() + (size_t)np * nq * kslot;
+    b.cand_i = sh.part_i.get<int>() + (size_t)np * nq * kslot;
+    IvfPlanView pairs = b.plan();
+    pairs.slot_off = nullptr;
+    a.phase = 1;
+    launch_ivf_scan_mfma_h(a, pairs, ivf_max_items(nq, np, nlist, 1, 0, group), sh.part_d.get<float>(), sh.part_i.get<int>(),
+                           b.st);
+    launch_ivf_seed_bound(sh.part_d.get<float>(), sh.part_i.get<int>(), sh.slot_off.get<int>(), np, nq, kslot, sh.n,
+                          b.qbound, b.cand_d, b.cand_i, sh.run_cnt.get<int>(), b.st);
+    a.phase = 2;
+    a.cursor = sh.run_cnt.get<int>();
+    launch_ivf_scan_mfma_h(a, b.plan(), ivf_max_items(nq, np, nlist, sh.max_nch - 1, sh.n, group), b.cand_d, b.cand_i, b.st);
+    // HIPANN_IVF_RUN_STATS=1 (measurement only: a stream sync and a readback per batch): the appended entries per query
+    static const bool run_stats = [] { const char *e = std::getenv("HIPANN_IVF_RUN_STATS"); return e && std::atoi(e) != 0; }();
+    if (!run_stats) return;
+    std::vector<int> h((size_t)nq);
+    HIPANN_CHECK(hipMemcpyAsync(h.data(), sh.run_cnt.p, sizeof(int) * (size_t)nq, hipMemcpyDeviceToHost, b.st));
+    HIPANN_CHECK(hipStreamSynchronize(b.st));
+    int64_t sum = 0, over = 0;
+    int mx = 0;
+    for (int c : h) { sum += c; mx = std::max(mx, c); over += kSeedK + c > 4096; }
+    std::fprintf(stderr, "HIPANN_IVF_RUN_STATS nq=%lld appended_total=%lld mean=%.1f max=%d runs_over_4096=%lld\n",
+                 (long long)nq, (long long)sum, (double)sum / (double)nq, mx, (long long)over);
+}
+
+// 3. scan: one k-list per (query, probe, row chunk) slot — every slot is written by exactly one item
+// (the seeded scan: the pairs' chunk-0 slots, then the queries' candidate slots — one more per query)
+void ivf_scan(IvfBatch &b) {
+    IvfShard &sh = b.sh;
+    const IvfScanMode &m = b.m;
+    const int nlist = b.ix.nlist, d = b.ix.d, metric = b.ix.metric, np = b.np, k = m.kscan;
+    const int64_t nq = b.nq;
+    const size_t parts = ((size_t)np * nq * sh.max_nch + (m.seeded ? (size_t)np * nq + (size_t)nq : 0)) * m.kslot;
     HIPANN_REQUIRE((int64_t)np * nq * sh.max_nch < (int64_t)0x7fffffff, "too many partial lists");
     sh.part_d.ensure(parts * sizeof(float), sh.device);
     sh.part_i.ensure(parts * sizeof(int), sh.device);
-    const int64_t max_items = ivf_max_items(nq, np, nlist, sh.max_nch, sh.n, group);
-    float *cand_d = nullptr;  // the seeded scan: the queries' candidate runs (inside part_d / part_i)
-    int *cand_i = nullptr;
-    const float *qn = nullptr;
-    if (form != kFormDirect && metric == kL2) {
-        const FlatShard &qs = *sh.quant->shards[0];
-        if (probes_in && img) {
-            qn = qsh0.qn.get<float>();  // the query preparation wrote ‖q‖² there (row_norms_f32's bits)
-        } else if (!probes_in && qs.qn_of == xq && qs.qn_nq == nq) {
-            // the coarse quantizer's ‖q‖² of the same queries, written by THIS call's coarse step (with probes_in
-            // the quantizer did not run, and a cached pointer match may name a buffer whose contents changed)
-            qn = qs.qn.get<float>();
+    const int64_t max_items = ivf_max_items(nq, np, nlist, sh.max_nch, sh.n, m.group);
+    const float *qn = b.qn = ivf_query_norms(b);
+    if (m.tiled && !m.image) ensure_tiled_codes(sh, d, nlist, b.st);
+    if (!m.image && ivf_form_split(m.form))  // (an image's query terms were prepared before the coarse step)
+        sh.qsplit.ensure((size_t)ivf_mfma_bf_qsplit_bytes(nq, d, ivf_form_terms(m.form)), sh.device);
+    float *pd = sh.part_d.get<float>();
+    int *pi = sh.part_i.get<int>();
+    const IvfPlanView plan = b.plan();
+    RoctxRange rr("hipann.ivf.scan");
+    ScopedTiming t(b.ix.timer_main, b.st);
+    if (m.image) {
+        const bool i8 = m.image == 2;
+        IvfImageScanArgs a;
+        a.nq = nq, a.d = d, a.metric = metric, a.k = k, a.sub = m.sub ? 1 : 0, a.qbound = b.qbound;
+        a.tpass_off = sh.tpass_off.get<int64_t>(), a.xn = sh.xnorm.get<float>();
+        if (i8) {  // its query units, scales and residuals; L2: ‖q̂‖² of the dequantised queries as the key's query term
+            a.qsplit = sh.qi8.p, a.its = sh.qs8.get<float>(), a.qres = sh.qres8.get<float>();
+            a.codes = sh.codes_i8.p, a.i8mode = 1, a.xs8 = sh.xs8.get<float>();
+            a.qn = m.cert8 ? sh.qhn2.get<float>() : qn;
+            if (m.cert8) a.xr8 = sh.xr8.get<float>(), a.qhn = sh.qhn.get<float>();
         } else {
-            sh.qn.ensure(sizeof(float) * (size_t)nq, sh.device);
-            launch_row_norms(xq, nq, d, sh.qn.get<float>(), st);
-            qn = sh.qn.get<float>();
+            a.qsplit = sh.hsplit.p, a.its = sh.hits.get<float>(), a.qres = sh.hres.get<float>(), a.qn = qn;
+            a.codes = sh.codes_h.p;
         }
+        if (m.seeded) ivf_scan_seeded(b, a);
+        else launch_ivf_scan_mfma_h(a, plan, max_items, pd, pi, b.st);
+    } else if (m.bigk) {
+        launch_ivf_scan_bigk(b.xq, d, metric, sh.codes, plan, sh.coarse_i.get<int64_t>(), nq * np,
+                             nq * np * std::max(sh.max_nch, 1), k, pd, pi, b.st);
+    } else if (ivf_form_split(m.form)) {
+        launch_ivf_scan_mfma_bf(ivf_form_terms(m.form), b.xq, nq, sh.qsplit.p, qn, d, metric, sh.codes_t.get<float>(),
+                                sh.tpass_off.get<int64_t>(), sh.xnorm.get<float>(), plan, k, max_items, b.qbound, pd, pi,
+                                b.st, m.sub ? 1 : 0);
+    } else if (m.form == kFormDecomposed) {
+        launch_ivf_scan_mfma(b.xq, qn, d, metric, sh.codes_t.get<float>(), sh.tpass_off.get<int64_t>(),
+                             sh.xnorm.get<float>(), plan, k, max_items, b.qbound, pd, pi, b.st);
+    } else {
+        launch_ivf_scan(b.xq, qn, d, metric, m.form, sh.codes, sh.xnorm.get<float>(), plan, nq, k, max_items, b.qbound, pd,
+                        pi, b.st);
     }
-    if (tiled && !img) ensure_tiled_codes(sh, d, nlist, st);
-    if (img) {
-        // query terms prepared before the coarse step
-    } else if (ivf_form_split(form)) {
-        sh.qsplit.ensure((size_t)ivf_mfma_bf_qsplit_bytes(nq, d, ivf_form_terms(form)), sh.device);
-    }
-    {
-        RoctxRange rr("hipann.ivf.scan");
-        ScopedTiming t(ix.timer_main, st);
-        if (img) {
-            // (int8: its query units, scales and residuals in the fp16 form's slots; L2: ‖q̂‖² of the dequantised
-            // queries as the key's query term)
-            auto scan_h = [&](int phase, const int *slots, int64_t items, float *pd, int *pi, int subl,
-                              int *run_cnt = nullptr) {
-                launch_ivf_scan_mfma_h(nq, i8 ? sh.qi8.p : sh.hsplit.p, i8 ? sh.qs8.get<float>() : sh.hits.get<float>(),
-                                       i8 ? sh.qres8.get<float>() : sh.hres.get<float>(), cert8 ? sh.qhn2.get<float>() : qn, d,
-                                       metric, i8 ? sh.codes_i8.p : sh.codes_h.p, sh.tpass_off.get<int64_t>(), sh.xnorm.get<float>(),
-                                       sh.list_off.get<int64_t>(), sh.list_len.get<int>(), sh.cnt.get<int>(), sh.bucket_off.get<int>(),
-                                       sh.item_off.get<int>(), sh.bucket.get<int>(), slots, nlist, np, k,
-                                       items, qbound, pd, pi, st, subl,
-                                       i8 ? 1 : 0, i8 ? sh.xs8.get<float>() : nullptr,
-                                       cert8 ? sh.xr8.get<float>() : nullptr, cert8 ? sh.qhn.get<float>() : nullptr, phase,
-                                       sh.goff.get<int>(), run_cnt);
-            };
-            if (seeded) {
-                // the chunk-0 slots (one per pair) take the head of part_d / part_i, the queries' candidate slots
-                // (common.hpp ivf_seed_run_slot) the rest: a query's run is its seed list, then the rows the second
-                // launch's waves append under run_cnt[q] — room for every (pair, chunk >= 1) sub-list in full, so no
-                // append can overflow; the rerank reads kSeedK + run_cnt[q] entries
-                HIPANN_REQUIRE((int64_t)np * nq * sh.max_nch + nq < (int64_t)0x7fffffff, "too many candidate slots");
-                HIPANN_REQUIRE((int64_t)np * sh.max_nch * kslot < (int64_t)0x7fffffff, "candidate run too long");
-                sh.run_cnt.ensure(sizeof(int) * (size_t)nq, sh.device);
-                cand_d = sh.part_d.get<float>() + (size_t)np * nq * kslot;
-                cand_i = sh.part_i.get<int>() + (size_t)np * nq * kslot;
-                scan_h(1, nullptr, ivf_max_items(nq, np, nlist, 1, 0, group), sh.part_d.get<float>(), sh.part_i.get<int>(), 1);
-                launch_ivf_seed_bound(sh.part_d.get<float>(), sh.part_i.get<int>(), sh.slot_off.get<int>(), np, nq, kslot,
-                                      sh.n, qbound, cand_d, cand_i, sh.run_cnt.get<int>(), st);
-                scan_h(2, sh.slot_off.get<int>(), ivf_max_items(nq, np, nlist, sh.max_nch - 1, sh.n, group), cand_d, cand_i, 1,
-                       sh.run_cnt.get<int>());
-                // HIPANN_IVF_RUN_STATS=1 (measurement only: a stream sync and a readback per batch): the appended
-                // entries per query
-                static const bool run_stats = [] { const char *e = std::getenv("HIPANN_IVF_RUN_STATS"); return e && std::atoi(e) != 0; }();
-                if (run_stats) {
-                    std::vector<int> h((size_t)nq);
-                    HIPANN_CHECK(hipMemcpyAsync(h.data(), sh.run_cnt.p, sizeof(int) * (size_t)nq, hipMemcpyDeviceToHost, st));
-                    HIPANN_CHECK(hipStreamSynchronize(st));
-                    int64_t sum = 0, over = 0;
-                    int mx = 0;
-                    for (int c : h) { sum += c; mx = std::max(mx, c); over += kSeedK + c > 4096; }
-                    std::fprintf(stderr, "HIPANN_IVF_RUN_STATS nq=%lld appended_total=%lld mean=%.1f max=%d runs_over_4096=%lld\n",
-                                 (long long)nq, (long long)sum, (double)sum / (double)nq, mx, (long long)over);
-                }
-            } else {
-                scan_h(0, sh.slot_off.get<int>(), max_items, sh.part_d.get<float>(), sh.part_i.get<int>(), sub ? 1 : 0);
-            }
-        }
-        else if (bigk)
-            launch_ivf_scan_bigk(xq, d, metric, sh.codes, sh.list_off.get<int64_t>(), sh.list_len.get<int>(),
-                                 sh.coarse_i.get<int64_t>(),
-                                 nq * np, np, sh.slot_off.get<int>(), nq * np * std::max(sh.max_nch, 1), k,
-                                 sh.part_d.get<float>(), sh.part_i.get<int>(), st);
-        else if (ivf_form_split(form))
-            launch_ivf_scan_mfma_bf(ivf_form_terms(form), xq, nq, sh.qsplit.p, qn, d, metric, sh.codes_t.get<float>(),
-                                    sh.tpass_off.get<int64_t>(), sh.xnorm.get<float>(), sh.list_off.get<int64_t>(),
-                                    sh.list_len.get<int>(), sh.cnt.get<int>(), sh.bucket_off.get<int>(), sh.item_off.get<int>(),
-                                    sh.bucket.get<int>(), sh.slot_off.get<int>(), nlist, np, k, max_items, qbound,
-                                    sh.part_d.get<float>(), sh.part_i.get<int>(), st, sub ? 1 : 0);
-        else if (form == kFormDecomposed)
-            launch_ivf_scan_mfma(xq, qn, d, metric, sh.codes_t.get<float>(), sh.tpass_off.get<int64_t>(),
-                                 sh.xnorm.get<float>(), sh.list_off.get<int64_t>(), sh.list_len.get<int>(),
-                                 sh.cnt.get<int>(),
-                                 sh.bucket_off.get<int>(), sh.item_off.get<int>(), sh.bucket.get<int>(),
-                                 sh.slot_off.get<int>(), nlist, np, k, max_items, qbound, sh.part_d.get<float>(),
-                                 sh.part_i.get<int>(), st);
-        else
-            launch_ivf_scan(xq, qn, d, metric, form, sh.codes, sh.xnorm.get<float>(), sh.list_off.get<int64_t>(),
-                            sh.list_len.get<int>(), sh.cnt.get<int>(), sh.bucket_off.get<int>(), sh.item_off.get<int>(), sh.bucket.get<int>(),
-                            sh.slot_off.get<int>(), nlist, np, nq, k, max_items, qbound, sh.part_d.get<float>(),
-                            sh.part_i.get<int>(), st);
-    }
-    if (form_override < 0) {  // what the scan saw (hipann_debug_ivf_info / _read)
-        sh.dbg_nq = nq;
-        sh.dbg_np = np;
-        sh.dbg_kslot = kslot;
-        sh.dbg_sub = sub ? 1 : 0;
-        sh.dbg_img = i8 ? 2 : half ? 1 : 0;
-        sh.dbg_seeded = seeded ? 1 : 0;
-        sh.dbg_kfilt = exact ? kfilt : 0;
-        sh.dbg_cand_off = seeded ? (int64_t)np * nq * kslot : -1;
-        sh.dbg_qn = qn;  // (the int8 L2 scan's key term is qhn2 instead; the rerank reads this one)
-    }
-    if (sh.dbg_stop) return;  // a test reads the scan's buffers as they are
-    // 4. merge each query's partial lists (kFormSplit2Exact: merge + exact rerank + bound check)
-    if (!exact) {
-        ScopedTiming t(ix.timer_merge, st);
-        launch_ivf_merge(sh.part_d.get<float>(), sh.part_i.get<int>(), sh.ids, sh.n, sh.slot_off.get<int>(), np, nq, k,
-                         kout, out_sign, D, I, st);
-        return;
-    }
-    // flagged queries re-run on the device in the direct form, each by the rerank wave that flagged it
-    // (ivf_block_fallback inline: no host readback and no launch of its own); HIPANN_IVF_HOST_FALLBACK=1: from the
-    // host on the 3-term path (A/B)
-    const bool inline_fb = !host_fallback() && !sh.count_only;
+}
+
+// what the scan saw (hipann_debug_ivf_info / _read)
+void ivf_record_debug(IvfBatch &b) {
+    IvfShard &sh = b.sh;
+    const IvfScanMode &m = b.m;
+    sh.dbg_nq = b.nq;
+    sh.dbg_np = b.np;
+    sh.dbg_kslot = m.kslot;
+    sh.dbg_sub = m.sub ? 1 : 0;
+    sh.dbg_img = m.image;
+    sh.dbg_seeded = m.seeded ? 1 : 0;
+    sh.dbg_kfilt = m.exact ? m.kfilt : 0;
+    sh.dbg_cand_off = m.seeded ? (int64_t)b.np * b.nq * m.kslot : -1;
+    sh.dbg_qn = b.qn;  // (the int8 L2 scan's key term is qhn2 instead; the rerank reads this one)
+}
+
+// 4. the exact forms: merge + exact rerank + bound check.  Flagged queries re-run on the device in the direct form,
+// each by the rerank wave that flagged it (ivf_block_fallback inline: no host readback and no launch of its own) —
+// inline_fb; else they are left in nflag / flagged (probation's count, or the host's re-run).
+void ivf_rerank(IvfBatch &b, bool inline_fb) {
+    IvfShard &sh = b.sh;
+    const IvfScanMode &m = b.m;
+    const int nlist = b.ix.nlist, d = b.ix.d, metric = b.ix.metric, np = b.np, kout = b.kout;
+    const int64_t nq = b.nq;
     int fb_cap = 0, fb_maxch = 1;
     if (inline_fb) {
         if (!sh.fb_total.p) {
             sh.fb_total.ensure(sizeof(unsigned long long), sh.device);
-            HIPANN_CHECK(hipMemsetAsync(sh.fb_total.p, 0, sizeof(unsigned long long), st));
+            HIPANN_CHECK(hipMemsetAsync(sh.fb_total.p, 0, sizeof(unsigned long long), b.st));
         }
         sh.fpd.ensure(sizeof(float) * (size_t)nq * np * kout, sh.device);
         sh.fpi.ensure(sizeof(long long) * (size_t)nq * np * kout, sh.device);
@@ -723,55 +757,119 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
         sh.fbc_i.ensure(sizeof(long long) * (size_t)fb_cap * np * fb_maxch * kout, sh.device);
         if (sh.fbc_cap < fb_cap || !sh.fbc_done.p) {  // counters start (and are left) at zero
             sh.fbc_done.ensure(sizeof(unsigned) * (size_t)std::max(fb_cap, 64), sh.device);
-            HIPANN_CHECK(hipMemsetAsync(sh.fbc_done.p, 0, sh.fbc_done.bytes, st));
+            HIPANN_CHECK(hipMemsetAsync(sh.fbc_done.p, 0, sh.fbc_done.bytes, b.st));
             sh.fbc_cap = (int)(sh.fbc_done.bytes / sizeof(unsigned));
         }
     }
-    {
-        RoctxRange rr("hipann.ivf.rerank");
-        ScopedTiming t(ix.timer_merge, st);
-        launch_ivf_rerank(seeded ? cand_d : sh.part_d.get<float>(), seeded ? cand_i : sh.part_i.get<int>(),
-                          sh.slot_off.get<int>(), np, nq, kfilt, kout,
-                          metric, xq, sh.codes, d, sh.ids, sh.n, 0, xmax2, D, I, sh.nflag.get<int>(),
-                          sh.flagged.get<int>(), st, kSplit2Eps, i8 ? rxmax8 : half ? sh.half_rxmax : -1.f,
-                          i8 ? sh.qres8.get<float>() : half ? sh.hres.get<float>() : nullptr, sh.coarse_i.get<int64_t>(),
-                          sh.list_off.get<int64_t>(), nlist, qbound, img && metric == kL2 ? qn : nullptr, kslot,
-                          sub ? 1 : 0, inline_fb ? sh.list_len.get<int>() : nullptr,
-                          inline_fb ? sh.fpd.get<float>() : nullptr, inline_fb ? sh.fpi.get<long long>() : nullptr,
-                          inline_fb ? sh.fb_total.get<unsigned long long>() : nullptr, fb_cap, cert8 ? 1 : 0,
-                          seeded ? sh.run_cnt.get<int>() : nullptr);
-        if (fb_cap > 0)
-            launch_ivf_fallback_chunks(sh.nflag.get<int>(), sh.flagged.get<int>(), fb_cap, np, fb_maxch, ivf_chunk_rows(),
-                                       kout, metric, xq, sh.codes, d, sh.ids, 0, sh.coarse_i.get<int64_t>(),
-                                       sh.list_off.get<int64_t>(), sh.list_len.get<int>(), nlist, sh.fbc_d.get<float>(),
-                                       sh.fbc_i.get<long long>(), sh.fbc_done.get<unsigned>(), D, I,
-                                       sh.fb_total.get<unsigned long long>(), st,
-                                       as_half && !probation ? auto8_host_word(sh) : nullptr, (unsigned)++sh.fb_seq);
+    RoctxRange rr("hipann.ivf.rerank");
+    ScopedTiming t(b.ix.timer_merge, b.st);
+    IvfRerankArgs a;
+    a.pd = m.seeded ? b.cand_d : sh.part_d.get<float>(), a.pi = m.seeded ? b.cand_i : sh.part_i.get<int>();
+    a.slot_off = sh.slot_off.get<int>(), a.nprobe = np, a.nq = nq, a.k = m.kfilt, a.kout = kout, a.metric = metric;
+    a.Q = b.xq, a.codes = sh.codes, a.d = d, a.ids = sh.ids, a.nrows = sh.n, a.xmax2 = b.xmax2, a.D = b.D, a.I = b.I;
+    a.nflag = sh.nflag.get<int>(), a.flagged = sh.flagged.get<int>();
+    a.rxmax = m.image == 2 ? b.rxmax8 : m.image == 1 ? sh.half_rxmax : -1.f;
+    a.qres = m.image == 2 ? sh.qres8.get<float>() : m.image == 1 ? sh.hres.get<float>() : nullptr;
+    a.probes = sh.coarse_i.get<int64_t>(), a.list_off = sh.list_off.get<int64_t>(), a.nlist = nlist, a.qbound = b.qbound;
+    a.qnorm = m.image && metric == kL2 ? b.qn : nullptr, a.kslot = m.kslot, a.sub = m.sub ? 1 : 0;
+    if (inline_fb) {
+        a.list_len = sh.list_len.get<int>(), a.fpd = sh.fpd.get<float>(), a.fpi = sh.fpi.get<long long>();
+        a.fb_total = sh.fb_total.get<unsigned long long>();
     }
-    if (sh.count_only) return;  // probation's pass: the flag count stays in nflag, nothing is re-run
-    if (probation) auto8_probation(ix, sh, nq, xq, k_user, kout, st, probes_in);
-    if (inline_fb) return;
+    a.fb_cap = fb_cap, a.i8_l2 = m.cert8 ? 1 : 0, a.seed_cnt = m.seeded ? sh.run_cnt.get<int>() : nullptr;
+    launch_ivf_rerank(a, b.st);
+    if (fb_cap > 0)
+        launch_ivf_fallback_chunks(sh.nflag.get<int>(), sh.flagged.get<int>(), fb_cap, np, fb_maxch, ivf_chunk_rows(),
+                                   kout, metric, b.xq, sh.codes, d, sh.ids, 0, sh.coarse_i.get<int64_t>(),
+                                   sh.list_off.get<int64_t>(), sh.list_len.get<int>(), nlist, sh.fbc_d.get<float>(),
+                                   sh.fbc_i.get<long long>(), sh.fbc_done.get<unsigned>(), b.D, b.I,
+                                   sh.fb_total.get<unsigned long long>(), b.st,
+                                   m.as_half && !b.probation ? auto8_host_word(sh) : nullptr, (unsigned)++sh.fb_seq);
+}
+
+// Probation: the batch has been answered through the fp16 image; the same batch runs once more on the same stream
+// through the int8 image into scratch outputs, counting only (no flagged query is re-run, nothing the caller sees is
+// written).  The flag count is read back — probation's one host synchronisation — and decides by the byte rule.
+void ivf_probation(IvfBatch &b) {
+    IvfIndex &ix = b.ix;
+    IvfShard &sh = b.sh;
+    sh.auto8_live = sh.live;
+    sh.auto8_over = 0;
+    sh.auto8 = -1;
+    if (!ensure_i8_codes(sh, ix.d, ix.nlist, b.st)) return;
+    sh.probe_D.ensure(sizeof(float) * (size_t)b.nq * b.kout, sh.device);
+    sh.probe_I.ensure(sizeof(int64_t) * (size_t)b.nq * b.kout, sh.device);
+    {
+        TimerPause p0(ix.timer_main), p1(ix.timer_merge);
+        IvfSearchOpts o;
+        o.form_override = kFormI8Exact, o.probes_in = b.opts.probes_in, o.count_only = true;
+        ivf_shard_search(ix, sh, b.nq, b.xq, b.k_user, b.kout, sh.probe_D.get<float>(), sh.probe_I.get<int64_t>(), b.st, o);
+    }
     int nf = 0;
-    HIPANN_CHECK(hipMemcpyAsync(&nf, sh.nflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPANN_CHECK(hipStreamSynchronize(st));
+    HIPANN_CHECK(hipMemcpyAsync(&nf, sh.nflag.p, sizeof(int), hipMemcpyDeviceToHost, b.st));
+    HIPANN_CHECK(hipStreamSynchronize(b.st));
+    if (!auto8_over_rule(nf, std::min(ix.nprobe, ix.nlist), ix.nlist, sh.live, ix.d)) sh.auto8 = 1;
+}
+
+// HIPANN_IVF_HOST_FALLBACK=1: the flag count is read back and the flagged queries re-run on the 3-term path (the
+// batch's probe lists are kept for last_probes)
+void ivf_host_rerun(IvfBatch &b) {
+    IvfIndex &ix = b.ix;
+    IvfShard &sh = b.sh;
+    const int d = ix.d, kout = b.kout;
+    int nf = 0;
+    HIPANN_CHECK(hipMemcpyAsync(&nf, sh.nflag.p, sizeof(int), hipMemcpyDeviceToHost, b.st));
+    HIPANN_CHECK(hipStreamSynchronize(b.st));
     if (nf <= 0) return;
-    // flagged queries: re-run on the 3-term path (the batch's probe lists are kept for last_probes)
     ix.rerank_fallbacks += nf;
-    const size_t pbytes = sizeof(int64_t) * (size_t)nq * np;
+    const size_t pbytes = sizeof(int64_t) * (size_t)b.nq * b.np;
     sh.coarse_save.ensure(pbytes, sh.device);
-    HIPANN_CHECK(hipMemcpyAsync(sh.coarse_save.p, sh.coarse_i.p, pbytes, hipMemcpyDeviceToDevice, st));
+    HIPANN_CHECK(hipMemcpyAsync(sh.coarse_save.p, sh.coarse_i.p, pbytes, hipMemcpyDeviceToDevice, b.st));
     sh.fq.ensure(sizeof(float) * (size_t)nf * d, sh.device);
     sh.fD.ensure(sizeof(float) * (size_t)nf * kout, sh.device);
     sh.fI.ensure(sizeof(int64_t) * (size_t)nf * kout, sh.device);
-    launch_ivf_gather_queries(xq, sh.flagged.get<int>(), nf, d, sh.fq.get<float>(), st);
+    launch_ivf_gather_queries(b.xq, sh.flagged.get<int>(), nf, d, sh.fq.get<float>(), b.st);
     {
         TimerPause p0(ix.timer_main), p1(ix.timer_merge);
-        ivf_shard_search(ix, sh, nf, sh.fq.get<float>(), k_user, kout, sh.fD.get<float>(), sh.fI.get<int64_t>(), st,
-                         kFormSplit3);
+        IvfSearchOpts o;
+        o.form_override = kFormSplit3;
+        ivf_shard_search(ix, sh, nf, sh.fq.get<float>(), b.k_user, kout, sh.fD.get<float>(), sh.fI.get<int64_t>(), b.st, o);
     }
-    launch_ivf_scatter_results(sh.fD.get<float>(), sh.fI.get<int64_t>(), sh.flagged.get<int>(), nf, kout, D, I, st);
-    HIPANN_CHECK(hipMemcpyAsync(sh.coarse_i.p, sh.coarse_save.p, pbytes, hipMemcpyDeviceToDevice, st));
+    launch_ivf_scatter_results(sh.fD.get<float>(), sh.fI.get<int64_t>(), sh.flagged.get<int>(), nf, kout, b.D, b.I, b.st);
+    HIPANN_CHECK(hipMemcpyAsync(sh.coarse_i.p, sh.coarse_save.p, pbytes, hipMemcpyDeviceToDevice, b.st));
 }
+
+}  // namespace
+
+// One shard: queries on the shard's device → D/I (nq × kout) on the same device, async on `st`.
+void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, int k, int kout, float *D, int64_t *I,
+                      hipStream_t st, const IvfSearchOpts &opts) {
+    RoctxRange r_all("hipann.ivf.search_shard");
+    DeviceGuard g(sh.device);
+    if (nq <= 0) return;
+    IvfBatch b{ix, sh, nq, xq, k, kout, D, I, st, opts, std::min(ix.nprobe, ix.nlist), {}, false, *sh.quant->shards[0]};
+    ivf_plan_scratch(b);
+    CcntReset ccnt_reset{b.ccnt_cur, ix.nlist, st, true};
+    ivf_pick_mode(b);
+    ivf_prepare_queries(b);
+    ivf_coarse_and_plan(b);
+    ccnt_reset.armed = false;
+    ivf_scan(b);
+    if (opts.record()) ivf_record_debug(b);
+    if (sh.dbg_stop) return;  // a test reads the scan's buffers as they are
+    if (!b.m.exact) {  // 4. merge each query's partial lists
+        ScopedTiming t(ix.timer_merge, st);
+        launch_ivf_merge(sh.part_d.get<float>(), sh.part_i.get<int>(), sh.ids, sh.n, sh.slot_off.get<int>(), b.np, nq,
+                         b.m.kscan, kout, ix.metric == kIP ? -1.f : 1.f, D, I, st);
+        return;
+    }
+    const bool inline_fb = !host_fallback() && !opts.count_only;
+    ivf_rerank(b, inline_fb);
+    if (opts.count_only) return;  // probation's pass: the flag count stays in nflag, nothing is re-run
+    if (b.probation) ivf_probation(b);
+    if (!inline_fb) ivf_host_rerun(b);
+}
+
 
 
 // Grow a shard's CSR so that list l can take add[l] more rows: every list gets capacity max(cap, need + max(need / 4,
@@ -1455,7 +1553,9 @@ int hipann_ivf_search_probes_device(void *h, int64_t nq, const float *xq_dev, co
         vx->last_np = std::min(vx->nprobe, vx->nlist);
         const int keff = (int)std::min<int64_t>(k, std::max<int64_t>(sh.live, 1));
         FenceScope fs(sh.fence, st, sh.device);
-        ivf_shard_search(*vx, sh, nq, xq_dev, keff, (int)k, D_dev, I_dev, st, -1, probes_dev);
+        IvfSearchOpts o;
+        o.probes_in = probes_dev;
+        ivf_shard_search(*vx, sh, nq, xq_dev, keff, (int)k, D_dev, I_dev, st, o);
         return 0;
     });
 }
@@ -1494,14 +1594,20 @@ int64_t hipann_ivf_remove_ids(void *h, const int64_t *labels, int64_t n, char *e
     return -1;
 }
 
+// the handle as an IVFFlat index (nullptr: null, or another kind)
+static IvfIndex *as_ivf(void *h) {
+    auto *ix = static_cast<IndexBase *>(h);
+    return ix && ix->kind == Kind::IVF ? static_cast<IvfIndex *>(ix) : nullptr;
+}
+
 int hipann_ivf_nlist(void *h) {
-    if (!h || static_cast<IndexBase *>(h)->kind != Kind::IVF) return -1;
-    return static_cast<IvfIndex *>(h)->nlist;
+    IvfIndex *vx = as_ivf(h);
+    return vx ? vx->nlist : -1;
 }
 
 int hipann_ivf_get_nprobe(void *h) {
-    if (!h || static_cast<IndexBase *>(h)->kind != Kind::IVF) return -1;
-    auto *vx = static_cast<IvfIndex *>(h);
+    IvfIndex *vx = as_ivf(h);
+    if (!vx) return -1;
     std::lock_guard<std::mutex> lk(vx->mu);
     return vx->nprobe;
 }
@@ -1567,30 +1673,24 @@ int hipann_ivf_last_probes(void *h, int64_t *probes, int64_t cap, char *eb, int 
 }
 
 int hipann_ivf_set_nprobe(void *h, int nprobe) {
-    if (!h || nprobe < 1) return -1;
-    auto *ix = static_cast<IndexBase *>(h);
-    if (ix->kind != Kind::IVF) return -1;
-    auto *vx = static_cast<IvfIndex *>(ix);
+    IvfIndex *vx = as_ivf(h);
+    if (!vx || nprobe < 1) return -1;
     std::lock_guard<std::mutex> lk(vx->mu);
     vx->nprobe = nprobe;
     return 0;
 }
 
 int hipann_ivf_set_form(void *h, int form) {
-    if (!h || form < kFormDecomposed || form > kFormI8Exact) return -1;
-    auto *ix = static_cast<IndexBase *>(h);
-    if (ix->kind != Kind::IVF) return -1;
-    auto *vx = static_cast<IvfIndex *>(ix);
+    IvfIndex *vx = as_ivf(h);
+    if (!vx || form < kFormDecomposed || form > kFormI8Exact) return -1;
     std::lock_guard<std::mutex> lk(vx->mu);
     vx->form = form;
     return 0;
 }
 
 int64_t hipann_ivf_rerank_fallbacks(void *h) {
-    if (!h) return -1;
-    auto *ix = static_cast<IndexBase *>(h);
-    if (ix->kind != Kind::IVF) return -1;
-    auto *vx = static_cast<IvfIndex *>(ix);
+    IvfIndex *vx = as_ivf(h);
+    if (!vx) return -1;
     std::lock_guard<std::mutex> lk(vx->mu);
     int64_t t = vx->rerank_fallbacks;  // host re-runs (HIPANN_IVF_HOST_FALLBACK)
     for (auto &sh : vx->shards) {       // + the device re-runs' running count
@@ -1605,41 +1705,31 @@ int64_t hipann_ivf_rerank_fallbacks(void *h) {
 }
 
 int hipann_ivf_set_filter_image(void *h, int mode) {
-    if (!h || mode < 0 || mode > 2) return -1;
-    auto *ix = static_cast<IndexBase *>(h);
-    if (ix->kind != Kind::IVF) return -1;
-    auto *vx = static_cast<IvfIndex *>(ix);
+    IvfIndex *vx = as_ivf(h);
+    if (!vx || mode < 0 || mode > 2) return -1;
     std::lock_guard<std::mutex> lk(vx->mu);
     vx->filter_image = mode;
     return 0;
 }
 
 int hipann_ivf_get_filter_image(void *h) {
-    if (!h) return -1;
-    auto *ix = static_cast<IndexBase *>(h);
-    if (ix->kind != Kind::IVF) return -1;
-    return static_cast<IvfIndex *>(ix)->filter_image;
+    IvfIndex *vx = as_ivf(h);
+    return vx ? vx->filter_image : -1;
 }
 
 int hipann_ivf_last_filter_image(void *h) {
-    if (!h) return -1;
-    auto *ix = static_cast<IndexBase *>(h);
-    if (ix->kind != Kind::IVF) return -1;
-    return static_cast<IvfIndex *>(ix)->last_filter_image;
+    IvfIndex *vx = as_ivf(h);
+    return vx ? vx->last_filter_image : -1;
 }
 
 int hipann_ivf_last_seeded(void *h) {
-    if (!h) return -1;
-    auto *ix = static_cast<IndexBase *>(h);
-    if (ix->kind != Kind::IVF) return -1;
-    return static_cast<IvfIndex *>(ix)->last_seeded;
+    IvfIndex *vx = as_ivf(h);
+    return vx ? vx->last_seeded : -1;
 }
 
 int64_t hipann_ivf_i8_passes_tiled(void *h) {
-    if (!h) return -1;
-    auto *ix = static_cast<IndexBase *>(h);
-    if (ix->kind != Kind::IVF) return -1;
-    auto *vx = static_cast<IvfIndex *>(ix);
+    IvfIndex *vx = as_ivf(h);
+    if (!vx) return -1;
     std::lock_guard<std::mutex> lk(vx->mu);
     int64_t t = 0;
     for (auto &sh : vx->shards) t += sh->i8_tiled;
@@ -1647,19 +1737,46 @@ int64_t hipann_ivf_i8_passes_tiled(void *h) {
 }
 
 int hipann_ivf_get_form(void *h) {
-    if (!h) return -1;
-    auto *ix = static_cast<IndexBase *>(h);
-    if (ix->kind != Kind::IVF) return -1;
-    return static_cast<IvfIndex *>(ix)->form;
+    IvfIndex *vx = as_ivf(h);
+    return vx ? vx->form : -1;
 }
 
-// ---- test hooks (tests/test_ivf_scan_gpu.py): a single-shard IVF handle's scan stages as the product runs them ------
+// ---- test hooks ------------------------------------------------------------------------------------------------------
+// The scan mode of a batch as ivf_shard_search resolves it, with no device (tests/test_ivf_scan_mode.py).
+// in[0..17): form, is_override, metric, d, k, kout, np, max_nch, alignment (bit 0: queries, bit 1: codes on 16 bytes),
+// host fallback, seed switch, build mask (bit 0: the fp16 image "builds", bit 1: the int8 image), filter-image mode,
+// nq, the shard's rows, i8_state, auto8.  out[0..17): form, last_form, exact, image, sub, kscan, kslot, kfilt, seeded,
+// tiled, cert8, group, bigk, the images asked for (mask as the build mask), filter image eligible, taken, probation.
+// 0, or -1 on short arrays or a value out of range.
+int hipann_debug_ivf_scan_mode(const int *in, int nin, int *out, int nout) {
+    if (!in || !out || nin < 17 || nout < 17 || in[3] < 1 || in[4] < 1 || in[5] < 1 || in[6] < 1 || in[7] < 1) return -1;
+    if (in[0] < kFormDecomposed || in[0] > kFormI8Exact || (in[2] != kL2 && in[2] != kIP) || in[12] < 0 || in[12] > 2) return -1;
+    IvfModeIn mi;
+    mi.form = in[0], mi.is_override = in[1] != 0, mi.metric = in[2], mi.d = in[3], mi.k = in[4], mi.kout = in[5];
+    mi.np = in[6], mi.max_nch = in[7], mi.aligned16 = (in[8] & 3) == 3, mi.host_fb = in[9] != 0, mi.seed_on = in[10] != 0;
+    const int build = in[11];
+    IvfShard sh;  // host fields only
+    sh.n = sh.live = sh.auto8_live = in[14];
+    sh.i8_state = in[15];
+    sh.auto8 = in[16];
+    const bool eligible = ivf_filter_image_eligible(mi, sh.n, sh.i8_state);
+    const IvfImageChoice c = ivf_choose_filter_image(sh, eligible, in[12], in[13], mi.np, /*nlist=*/mi.np, mi.d);
+    mi.use_int8 = c.use_int8;
+    int asked = 0;
+    const IvfScanMode m = ivf_resolve_mode(mi, [&](int image) {
+        asked |= 1 << (image - 1);
+        return (build >> (image - 1) & 1) != 0;
+    });
+    const int o[17] = {m.form, m.last_form, m.exact, m.image, m.sub, m.kscan, m.kslot, m.kfilt, m.seeded,
+                       m.tiled, m.cert8, m.group, m.bigk, asked, eligible, m.as_half, c.probation};
+    std::copy(o, o + 17, out);
+    return 0;
+}
+
+// tests/test_ivf_scan_gpu.py: a single-shard IVF handle's scan stages as the product runs them
 static IvfShard *dbg_shard(void *h) {
-    if (!h) return nullptr;
-    auto *ix = static_cast<IndexBase *>(h);
-    if (ix->kind != Kind::IVF) return nullptr;
-    auto *vx = static_cast<IvfIndex *>(ix);
-    return vx->shards.size() == 1 ? vx->shards[0].get() : nullptr;
+    IvfIndex *vx = as_ivf(h);
+    return vx && vx->shards.size() == 1 ? vx->shards[0].get() : nullptr;
 }
 
 // stop: 1 = ivf_shard_search returns after its scan step (D / I stay unwritten), 0 = the normal search.

@@ -16,7 +16,7 @@
 //
 // HBM traffic per batch ≈ Σ_items |ℓ|·4d  (each list read once per 32 queries probing it) instead
 // of Σ_queries Σ_probes |ℓ|·4d for the query-major reference.
-#include "common.hpp"
+#include "runtime.hpp"
 #include "wave_topk.hpp"
 
 #include <algorithm>
@@ -1141,20 +1141,19 @@ ivf_scan_slot_bigk(const float *__restrict__ Q, int d, const float *__restrict__
     }
 }
 
-void launch_ivf_scan_bigk(const float *Q, int d, int metric, const float *codes, const int64_t *list_off,
-                          const int *list_len, const int64_t *probes, int64_t npairs, int nprobe, const int *slot_off, int64_t nslots,
-                          int k, float *pd, int *pi, hipStream_t st) {
+void launch_ivf_scan_bigk(const float *Q, int d, int metric, const float *codes, const IvfPlanView &plan,
+                          const int64_t *probes, int64_t npairs, int64_t nslots, int k, float *pd, int *pi, hipStream_t st) {
     if (nslots <= 0) return;
     HIPANN_REQUIRE(nslots < (int64_t)0x7fffffff, "too many slots");
     const size_t smem = (size_t)2 * IVF_CH * 4 + (size_t)d * 4;
     HIPANN_REQUIRE(smem <= 64 * 1024, "dimension too large for the k > 64 IVF path");
     dim3 grid((unsigned)nslots), block(256);
     if (metric == kIP)
-        hipLaunchKernelGGL(ivf_scan_slot_bigk<true>, grid, block, smem, st, Q, d, codes, list_off, list_len, probes, npairs,
-                           nprobe, slot_off, k, pd, pi);
+        hipLaunchKernelGGL(ivf_scan_slot_bigk<true>, grid, block, smem, st, Q, d, codes, plan.list_off, plan.list_len,
+                           probes, npairs, plan.nprobe, plan.slot_off, k, pd, pi);
     else
-        hipLaunchKernelGGL(ivf_scan_slot_bigk<false>, grid, block, smem, st, Q, d, codes, list_off, list_len, probes, npairs,
-                           nprobe, slot_off, k, pd, pi);
+        hipLaunchKernelGGL(ivf_scan_slot_bigk<false>, grid, block, smem, st, Q, d, codes, plan.list_off, plan.list_len,
+                           probes, npairs, plan.nprobe, plan.slot_off, k, pd, pi);
     HIPANN_CHECK(hipGetLastError());
 }
 
@@ -1230,15 +1229,14 @@ int ivf_chunk_rows() { return IVF_CH; }
 size_t ivf_scan_smem_bytes() { return (size_t)2 * (IVF_TR + IVF_G) * IVF_LD * sizeof(float); }
 static size_t ivf_scan_dot_smem_bytes() { return (size_t)DT_STAGES * DT_STAGE_F4 * 16; }
 
+bool ivf_dot_supported(int d, bool aligned16) { return (d % 4 == 0) && aligned16; }
 bool ivf_dot_supported(const float *Q, int d, const float *codes) {
-    return (d % 4 == 0) && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)codes % 16 == 0);
+    return ivf_dot_supported(d, ((uintptr_t)Q % 16 == 0) && ((uintptr_t)codes % 16 == 0));
 }
 
-void launch_ivf_scan(const float *Q, const float *qn, int d, int metric, int form, const float *codes,
-                     const float *xn, const int64_t *list_off, const int *list_len, const int *cnt,
-                     const int *bucket_off, const int *item_off, const int *bucket, const int *slot_off, int nlist,
-                     int nprobe, int64_t nq,
-                     int k, int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st) {
+void launch_ivf_scan(const float *Q, const float *qn, int d, int metric, int form, const float *codes, const float *xn,
+                     const IvfPlanView &plan, int64_t nq, int k, int64_t max_items, unsigned *qbound, float *pd, int *pi,
+                     hipStream_t st) {
     if (max_items <= 0) return;
     HIPANN_REQUIRE(max_items < (int64_t)0x7fffffff, "too many IVF work items");
     HIPANN_REQUIRE(form != kFormDecomposed, "the MFMA scan is launched with its tiled codes (launch_ivf_scan_mfma)");
@@ -1247,7 +1245,7 @@ void launch_ivf_scan(const float *Q, const float *qn, int d, int metric, int for
         HIPANN_REQUIRE(metric == kIP || (qn && xn), "decomposed L2 scan needs query and row norms");
         dim3 grid((unsigned)max_items), block(DT_THREADS);
         const size_t smem = ivf_scan_dot_smem_bytes();
-#define HIPANN_DOT_ARGS Q, qn, d, codes, xn, list_off, list_len, cnt, bucket_off, item_off, bucket, slot_off, nlist, nprobe, k, pd, pi
+#define HIPANN_DOT_ARGS Q, qn, d, codes, xn, HIPANN_PLAN_ARGS(plan), k, pd, pi
         if (metric == kIP) hipLaunchKernelGGL((ivf_scan_dot<true>), grid, block, smem, st, HIPANN_DOT_ARGS);
         else hipLaunchKernelGGL((ivf_scan_dot<false>), grid, block, smem, st, HIPANN_DOT_ARGS);
 #undef HIPANN_DOT_ARGS
@@ -1255,7 +1253,7 @@ void launch_ivf_scan(const float *Q, const float *qn, int d, int metric, int for
         const bool vec4 = ivf_dot_supported(Q, d, codes);
         dim3 grid((unsigned)max_items), block(IVF_THREADS);
         const size_t smem = ivf_scan_smem_bytes();
-#define HIPANN_IVF_ARGS Q, d, codes, list_off, list_len, cnt, bucket_off, item_off, bucket, slot_off, nlist, nprobe, nq, k, pd, pi
+#define HIPANN_IVF_ARGS Q, d, codes, HIPANN_PLAN_ARGS(plan), nq, k, pd, pi
         if (vec4) {
             if (metric == kIP) hipLaunchKernelGGL((ivf_scan_topk<true, true>), grid, block, smem, st, HIPANN_IVF_ARGS);
             else hipLaunchKernelGGL((ivf_scan_topk<true, false>), grid, block, smem, st, HIPANN_IVF_ARGS);
@@ -2627,28 +2625,22 @@ void launch_ivf_seed_bound(const float *pa_d, const int *pa_i, const int *slot_o
 #define HIPANN_RR_WIDE (1 << 30)  // below this many queries: one 4-wave block per query (nq 1024: 80 -> 65 us)
 #endif
 
-void launch_ivf_rerank(const float *pd, const int *pi, const int *slot_off, int nprobe, int64_t nq, int k, int kout,
-                       int metric, const float *Q, const float *codes, int d, const int64_t *ids, int64_t nrows,
-                       int64_t label_offset, float xmax2, float *D, int64_t *I, int *nflag, int *flagged,
-                       hipStream_t st, float eps, float rxmax, const float *qres, const int64_t *probes,
-                       const int64_t *list_off, int nlist, const unsigned *qbound, const float *qnorm, int kslot,
-                       int sub, const int *list_len, float *fpd, long long *fpi, unsigned long long *fb_total,
-                       int fb_cap, int i8_l2, const int *seed_cnt) {
-    if (nq <= 0) return;
-    if (kslot <= 0) kslot = k;
-    HIPANN_REQUIRE(!seed_cnt || (slot_off && sub && qbound), "ivf rerank: candidate runs need the slot table and the bound");
-    HIPANN_REQUIRE(!i8_l2 || (metric == kL2 && qres && qnorm), "ivf rerank: the int8 L2 certificate needs ‖q − q̂‖ and ‖q‖²");
+void launch_ivf_rerank(const IvfRerankArgs &a, hipStream_t st) {
+    if (a.nq <= 0) return;
+    const int kslot = a.kslot <= 0 ? a.k : a.kslot;
+    HIPANN_REQUIRE(!a.seed_cnt || (a.slot_off && a.sub && a.qbound), "ivf rerank: candidate runs need the slot table and the bound");
+    HIPANN_REQUIRE(!a.i8_l2 || (a.metric == kL2 && a.qres && a.qnorm), "ivf rerank: the int8 L2 certificate needs ‖q − q̂‖ and ‖q‖²");
     // the filter depth k bounds kout (kout = k leaves no margin: those queries are flagged and re-run exactly)
-    HIPANN_REQUIRE(k >= kRerankK && k <= 64 && kout >= 1 && kout <= k && kslot >= 1 && (!sub || qbound),
+    HIPANN_REQUIRE(a.k >= kRerankK && a.k <= 64 && a.kout >= 1 && a.kout <= a.k && kslot >= 1 && (!a.sub || a.qbound),
                    "ivf rerank: k / kout out of range");
-    HIPANN_REQUIRE(!fpd || (fpi && list_len && probes && list_off && fb_total), "ivf rerank: inline re-run buffers");
+    HIPANN_REQUIRE(!a.fpd || (a.fpi && a.list_len && a.probes && a.list_off && a.fb_total), "ivf rerank: inline re-run buffers");
     // small batches: one 4-wave block per query (fills more of the chip, shorter per-query chain)
-    const bool wide = nq < HIPANN_RR_WIDE;
-    dim3 grid((unsigned)(wide ? nq : ceil_div(nq, 4))), block(256);
-#define RR_ARGS pd, pi, slot_off, nprobe, nq, k, kout, Q, codes, d, ids, nrows, label_offset, xmax2, D, I, nflag, flagged, \
-                eps, rxmax, qres, probes, list_off, nlist, qbound, qnorm, kslot, sub, list_len, fpd, fpi, fb_total, \
-                fpd ? fb_cap : 0, i8_l2, seed_cnt
-    if (metric == kIP) {
+    const bool wide = a.nq < HIPANN_RR_WIDE;
+    dim3 grid((unsigned)(wide ? a.nq : ceil_div(a.nq, 4))), block(256);
+#define RR_ARGS a.pd, a.pi, a.slot_off, a.nprobe, a.nq, a.k, a.kout, a.Q, a.codes, a.d, a.ids, a.nrows, a.label_offset, \
+                a.xmax2, a.D, a.I, a.nflag, a.flagged, a.eps, a.rxmax, a.qres, a.probes, a.list_off, a.nlist, a.qbound, \
+                a.qnorm, kslot, a.sub, a.list_len, a.fpd, a.fpi, a.fb_total, a.fpd ? a.fb_cap : 0, a.i8_l2, a.seed_cnt
+    if (a.metric == kIP) {
         if (wide) hipLaunchKernelGGL((ivf_rerank_topk<true, 4>), grid, block, 0, st, RR_ARGS);
         else hipLaunchKernelGGL((ivf_rerank_topk<true, 1>), grid, block, 0, st, RR_ARGS);
     } else {
@@ -2676,9 +2668,13 @@ extern "C" int hipann_debug_ivf_rerank(const float *pd, const int *pi, const int
     if ((metric != kL2 && metric != kIP) || (probes && (!list_off || nlist < 1))) return -1;
     try {
         HIPANN_CHECK(hipMemsetAsync(nflag, 0, sizeof(int), 0));
-        launch_ivf_rerank(pd, pi, slot_off, nprobe, nq, k, kout, metric, Q, codes, d, ids, nrows, label_offset, xmax2, D,
-                          I, nflag, flagged, 0, eps, rxmax, qres, probes, list_off, nlist, qbound, qnorm, kslot, sub,
-                          nullptr, nullptr, nullptr, nullptr, 0, i8_l2, seed_cnt);
+        IvfRerankArgs a;  // (no re-run buffers: list_len, fpd, fpi, fb_total and fb_cap stay unset)
+        a.pd = pd, a.pi = pi, a.slot_off = slot_off, a.nprobe = nprobe, a.nq = nq, a.k = k, a.kout = kout, a.metric = metric;
+        a.Q = Q, a.codes = codes, a.d = d, a.ids = ids, a.nrows = nrows, a.label_offset = label_offset, a.xmax2 = xmax2;
+        a.D = D, a.I = I, a.nflag = nflag, a.flagged = flagged, a.eps = eps, a.rxmax = rxmax, a.qres = qres;
+        a.probes = probes, a.list_off = list_off, a.nlist = nlist, a.qbound = qbound, a.qnorm = qnorm, a.kslot = kslot;
+        a.sub = sub, a.i8_l2 = i8_l2, a.seed_cnt = seed_cnt;
+        launch_ivf_rerank(a, 0);
         if (hipGetLastError() != hipSuccess) return -1;
         return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
     } catch (...) {

@@ -30,7 +30,7 @@
 // lane's cached k-th, the batch is bitonic-sorted inside the rows and merged (reverse + min + 4
 // half-cleaner stages), four queries at a time, every exchange a DPP operand.  At the end of the item
 // the 8 waves' lists are merged pairwise through LDS (3 rounds) and wave 0 writes the k-lists.
-#include "common.hpp"
+#include "runtime.hpp"
 #include "wave_topk.hpp"
 
 #include <algorithm>
@@ -555,18 +555,18 @@ void launch_ivf_tile_codes(const float *codes, const int64_t *list_off, const in
     HIPANN_CHECK(hipGetLastError());
 }
 
+bool ivf_mfma_supported(int d, bool aligned16, int k) {
+    return (d % 4 == 0) && aligned16 && k >= 1 && k <= MF_KMAX && mf_group(d) >= 16;
+}
 bool ivf_mfma_supported(const float *Q, int d, const float *codes, int k) {
-    return (d % 4 == 0) && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)codes % 16 == 0) && k >= 1 && k <= MF_KMAX &&
-           mf_group(d) >= 16;
+    return ivf_mfma_supported(d, ((uintptr_t)Q % 16 == 0) && ((uintptr_t)codes % 16 == 0), k);
 }
 
 int ivf_mfma_group(int d) { return mf_group(d); }
 
 void launch_ivf_scan_mfma(const float *Q, const float *qn, int d, int metric, const float *codes_t,
-                          const int64_t *tpass_off, const float *xn,
-                          const int64_t *list_off, const int *list_len, const int *cnt, const int *bucket_off,
-                          const int *item_off, const int *bucket, const int *slot_off, int nlist, int nprobe, int k,
-                          int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub) {
+                          const int64_t *tpass_off, const float *xn, const IvfPlanView &plan, int k, int64_t max_items,
+                          unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub) {
     if (max_items <= 0) return;
     HIPANN_REQUIRE(max_items < (int64_t)0x7fffffff, "too many IVF work items");
     HIPANN_REQUIRE(ivf_mfma_supported(Q, d, codes_t, k), "MFMA IVF scan needs d % 4 == 0, 16-B aligned data, k <= 16");
@@ -575,8 +575,7 @@ void launch_ivf_scan_mfma(const float *Q, const float *qn, int d, int metric, co
     const size_t merge = (size_t)(MF_WAVES / 2) * MF_QTMAX * 4 * 64 * sizeof(float2);  // end-of-item scratch
     const size_t smem = std::max((size_t)group * mf_stride(d) * 4, merge);
     dim3 grid((unsigned)max_items), block(MF_THREADS);
-#define MF_LAUNCH_ARGS Q, qn, d, codes_t, tpass_off, xn, list_off, list_len, cnt, bucket_off, item_off, bucket, slot_off, nlist, nprobe, group, k, \
-                       sub, qbound, pd, pi
+#define MF_LAUNCH_ARGS Q, qn, d, codes_t, tpass_off, xn, HIPANN_PLAN_ARGS(plan), group, k, sub, qbound, pd, pi
     if (metric == kIP) hipLaunchKernelGGL((ivf_scan_mfma<true>), grid, block, smem, st, MF_LAUNCH_ARGS);
     else hipLaunchKernelGGL((ivf_scan_mfma<false>), grid, block, smem, st, MF_LAUNCH_ARGS);
 #undef MF_LAUNCH_ARGS
@@ -920,15 +919,16 @@ int ivf_mfma_bf_group(int d, int np) { return mb_group(d, np); }
 
 int64_t ivf_mfma_bf_qsplit_bytes(int64_t nq, int d, int np) { return nq * np * mb_nsuper(d) * 64; }
 
+bool ivf_mfma_bf_supported(int d, bool aligned16, int k, int np) {
+    return ivf_mfma_supported(d, aligned16, k) && mb_group(d, np) >= 16;
+}
 bool ivf_mfma_bf_supported(const float *Q, int d, const float *codes, int k, int np) {
     return ivf_mfma_supported(Q, d, codes, k) && mb_group(d, np) >= 16;
 }
 
 void launch_ivf_scan_mfma_bf(int np, const float *Q, int64_t nq, void *qsplit, const float *qn, int d, int metric,
-                             const float *codes_t, const int64_t *tpass_off, const float *xn, const int64_t *list_off,
-                             const int *list_len, const int *cnt, const int *bucket_off, const int *item_off, const int *bucket,
-                             const int *slot_off, int nlist, int nprobe, int k, int64_t max_items, unsigned *qbound,
-                             float *pd, int *pi, hipStream_t st, int sub) {
+                             const float *codes_t, const int64_t *tpass_off, const float *xn, const IvfPlanView &plan,
+                             int k, int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub) {
     if (max_items <= 0 || nq <= 0) return;
     HIPANN_REQUIRE(np == 2 || np == 3, "split-bf16 scan: 2 or 3 terms");
     HIPANN_REQUIRE(max_items < (int64_t)0x7fffffff, "too many IVF work items");
@@ -945,8 +945,7 @@ void launch_ivf_scan_mfma_bf(int np, const float *Q, int64_t nq, void *qsplit, c
     const size_t merge = (size_t)(MF_WAVES / 2) * MF_QTMAX * 4 * 64 * sizeof(float2);
     const size_t smem = std::max((size_t)group * mb_stride(d, np, nh) * 4, merge);
     dim3 grid((unsigned)max_items), block(MF_THREADS);
-#define MB_LAUNCH_ARGS qs, qn, d, codes_t, tpass_off, xn, list_off, list_len, cnt, bucket_off, item_off, bucket, slot_off, nlist, nprobe, \
-                       group, k, sub, qbound, pd, pi
+#define MB_LAUNCH_ARGS qs, qn, d, codes_t, tpass_off, xn, HIPANN_PLAN_ARGS(plan), group, k, sub, qbound, pd, pi
 #define MB_LAUNCH(NP_, NH_)                                                                                         \
     do {                                                                                                            \
         if (metric == kIP) hipLaunchKernelGGL((ivf_scan_mfma_bf<true, NP_, NH_>), grid, block, smem, st, MB_LAUNCH_ARGS); \
@@ -1858,39 +1857,35 @@ void launch_ivf_split_queries_h(const float *Q, int64_t nq, int d, int es, void 
 }
 
 // The batch's queries are already prepared (launch_ivf_split_queries_h / launch_ivf_split_queries_i8).
-void launch_ivf_scan_mfma_h(int64_t nq, const void *qsplit, const float *its, float *qres, const float *qn, int d,
-                            int metric, const void *codes_h, const int64_t *tpass_off, const float *xn,
-                            const int64_t *list_off, const int *list_len, const int *cnt, const int *bucket_off,
-                            const int *item_off, const int *bucket, const int *slot_off, int nlist, int nprobe, int k,
-                            int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub, int i8mode,
-                            const float *xs8, const float *xr8, const float *qhn, int phase, const int *goff,
-                            int *cursor) {
-    if (max_items <= 0 || nq <= 0) return;
-    HIPANN_REQUIRE(phase == 0 ? slot_off != nullptr : goff && (phase == 1) == (slot_off == nullptr),
+void launch_ivf_scan_mfma_h(const IvfImageScanArgs &a, const IvfPlanView &plan, int64_t max_items, float *pd, int *pi,
+                            hipStream_t st) {
+    const int d = a.d, metric = a.metric, i8mode = a.i8mode, phase = a.phase;
+    if (max_items <= 0 || a.nq <= 0) return;
+    HIPANN_REQUIRE(phase == 0 ? plan.slot_off != nullptr : plan.goff && (phase == 1) == (plan.slot_off == nullptr),
                    "fp16 / int8 IVF scan: phase 1 writes pair slots, phase 2 needs the plan's slot prefixes");
-    HIPANN_REQUIRE((phase == 2) == (cursor != nullptr) && (!cursor || (i8mode && metric == kL2 && sub)),
+    HIPANN_REQUIRE((phase == 2) == (a.cursor != nullptr) && (!a.cursor || (i8mode && metric == kL2 && a.sub)),
                    "int8 IVF scan: phase 2 (int8 image, L2, sub-lists) appends through the queries' cursors");
     HIPANN_REQUIRE(max_items < (int64_t)0x7fffffff, "too many IVF work items");
-    HIPANN_REQUIRE(qsplit && its && qres && codes_h, "fp16 IVF scan: missing buffers");
-    HIPANN_REQUIRE(i8mode ? ivf_mfma_i8_supported(d, k) && xs8 : ivf_mfma_h_supported(d, k),
+    HIPANN_REQUIRE(a.qsplit && a.its && a.qres && a.codes, "fp16 IVF scan: missing buffers");
+    HIPANN_REQUIRE(i8mode ? ivf_mfma_i8_supported(d, a.k) && a.xs8 : ivf_mfma_h_supported(d, a.k),
                    "fp16 / int8 IVF scan needs k <= 16 (int8: scales and prepared queries)");
-    HIPANN_REQUIRE(metric == kIP || (qn && xn), "decomposed L2 scan needs query and row norms");
-    HIPANN_REQUIRE(!i8mode || metric == kIP || (xr8 && qhn), "int8 L2 scan needs the rows' residuals and the queries' norms");
-    const uint4 *qs = static_cast<const uint4 *>(qsplit);
+    HIPANN_REQUIRE(metric == kIP || (a.qn && a.xn), "decomposed L2 scan needs query and row norms");
+    HIPANN_REQUIRE(!i8mode || metric == kIP || (a.xr8 && a.qhn), "int8 L2 scan needs the rows' residuals and the queries' norms");
+    const uint4 *qs = static_cast<const uint4 *>(a.qsplit);
     const int group = i8mode ? ivf_mfma_i8_group(d) : mh_group_packed(d);
     // LDS: the group's query image and parameters, or the end-of-item merge scratch
     const size_t merge = (size_t)(MF_WAVES / 2) * MH_QTW * 4 * 64 * sizeof(float2);
     const size_t per_q = i8mode ? (size_t)(mi_nsup(d) * 16 + 8) * 4 + 16 : (size_t)mh_stride(d) * 4 + 8;
     const size_t smem = std::max((size_t)ivf_group_wide(group) * per_q, merge);
     HIPANN_REQUIRE(smem <= MF_LDS_MAX, "fp16 IVF scan: LDS image too large");
-    HIPANN_REQUIRE(nq < (int64_t)0x7fffffff, "fp16 IVF scan: batch too large");
+    HIPANN_REQUIRE(a.nq < (int64_t)0x7fffffff, "fp16 IVF scan: batch too large");
     dim3 grid((unsigned)max_items), block(MF_THREADS);
-    const uint4 *ch = static_cast<const uint4 *>(codes_h);
+    const uint4 *ch = static_cast<const uint4 *>(a.codes);
     // HIPANN_IVF_REMAP=0 (A/B): consecutive items (a chunk's query groups) dealt round-robin over the XCDs instead of
     // contiguous runs per XCD
     static const int remap = [] { const char *e = std::getenv("HIPANN_IVF_REMAP"); return !e || std::atoi(e) ? 1 : 0; }();
-#define MH_LAUNCH_ARGS qs, qn, its, d, ch, tpass_off, xn, list_off, list_len, cnt, bucket_off, item_off, bucket, slot_off, nlist, nprobe, \
-                       group, k, sub, qbound, pd, pi, qres, (int)nq, remap, xs8, xr8, qhn, phase, goff, cursor
+#define MH_LAUNCH_ARGS qs, a.qn, a.its, d, ch, a.tpass_off, a.xn, HIPANN_PLAN_ARGS(plan), group, a.k, a.sub, a.qbound, pd, pi, \
+                       a.qres, (int)a.nq, remap, a.xs8, a.xr8, a.qhn, phase, plan.goff, a.cursor
     if (i8mode) {
         if (metric == kIP) hipLaunchKernelGGL((ivf_scan_mfma_h<true, true>), grid, block, smem, st, MH_LAUNCH_ARGS);
         else hipLaunchKernelGGL((ivf_scan_mfma_h<false, true>), grid, block, smem, st, MH_LAUNCH_ARGS);

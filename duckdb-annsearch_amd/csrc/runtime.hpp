@@ -434,13 +434,12 @@ struct IvfShard {
     // −1 fp16; auto8_live: the live rows at the last probation (a quarter more rows: probation again); auto8_over:
     // consecutive int8 batches whose flag count broke the byte rule.  fb_host (pinned, host-mapped): batch number
     // << 32 | flag count of the latest int8 batch, written by its fallback launch and read by the next call — no
-    // host synchronisation and no stream marker in the steady state.  count_only: probation's int8 pass (scratch
-    // outputs probe_D / probe_I, no re-run of flagged queries, the flag count left in nflag).
+    // host synchronisation and no stream marker in the steady state.  probe_D / probe_I: the scratch outputs of
+    // probation's int8 pass (IvfSearchOpts::count_only).
     int auto8 = 0, auto8_over = 0;
     int64_t auto8_live = 0;
     HostBuf fb_host;
     uint64_t fb_seq = 0, fb_seen = 0;
-    bool count_only = false;
     DevBuf probe_D, probe_I;
     // test hooks (hipann_debug_ivf_*, tests/test_ivf_scan_gpu.py).  dbg_stop: ivf_shard_search returns after its scan
     // step (no merge, no rerank; D / I stay unwritten).  dbg_seed: the seeded int8 scan by HIPANN_IVF_SEED (-1), off
@@ -532,6 +531,15 @@ void launch_merge_raw(const float *pd, const int *pi, int nparts, int64_t nq, in
                       hipStream_t st);
 void launch_flat_scan_topk(const float *Q, int nq, const float *X, int64_t N, int d, int metric, int k, int nwaves,
                            int64_t rows_per_wave, float *pd, int *pi, hipStream_t st);
+// What launch_ivf_plan leaves for the scans (device arrays; goff: the group prefix, read by the seeded image scan only).
+struct IvfPlanView {
+    const int64_t *list_off;
+    const int *list_len, *cnt, *bucket_off, *item_off, *bucket, *slot_off, *goff;
+    int nlist, nprobe;
+};
+// the nine leading plan parameters of every item scan kernel, in their order
+#define HIPANN_PLAN_ARGS(p) \
+    (p).list_off, (p).list_len, (p).cnt, (p).bucket_off, (p).item_off, (p).bucket, (p).slot_off, (p).nlist, (p).nprobe
 void launch_ivf_plan(const int64_t *probes, int64_t nq, int nprobe, const int *list_len, int nlist, int group,
                      int *cnt, int *bucket_off, int *item_off, int *cursor, int *bucket, int *slot_off,
                      hipStream_t st, int *nflag_reset = nullptr, unsigned *qbound = nullptr, int *ccnt = nullptr,
@@ -540,6 +548,7 @@ void launch_ivf_plan(const int64_t *probes, int64_t nq, int nprobe, const int *l
                      int *goff = nullptr);
 int64_t ivf_max_items(int64_t nq, int nprobe, int nlist, int max_nch, int64_t nrows, int group);
 int ivf_mfma_bf_group(int d, int np);
+bool ivf_mfma_bf_supported(int d, bool aligned16, int k, int np);
 bool ivf_mfma_bf_supported(const float *Q, int d, const float *codes, int k, int np);
 int64_t ivf_mfma_bf_qsplit_bytes(int64_t nq, int d, int np);
 // Form 4 (bounded passes): the flagged queries' exact top-kout over ALL their buffered candidates, certified
@@ -551,19 +560,41 @@ void launch_flat_cand_rerank(const int *flagged, int nf, const float *cand_d, co
                              float *part_d, long long *part_i, int *ovf, float *D, int64_t *I, int *nflag2,
                              int *flagged2, hipStream_t st, float *dbg = nullptr, const float *qres = nullptr);
 int flat_cand_rerank_parts(int nsplit);
-void launch_ivf_rerank(const float *pd, const int *pi, const int *slot_off, int nprobe, int64_t nq, int k, int kout,
-                       int metric, const float *Q, const float *codes, int d, const int64_t *ids, int64_t nrows,
-                       int64_t label_offset, float xmax2, float *D, int64_t *I, int *nflag, int *flagged,
-                       hipStream_t st, float eps = kSplit2Eps, float rxmax = -1.f, const float *qres = nullptr,
-                       const int64_t *probes = nullptr, const int64_t *list_off = nullptr, int nlist = 0,
-                       const unsigned *qbound = nullptr, const float *qnorm = nullptr, int kslot = 0, int sub = 0,
-                       const int *list_len = nullptr, float *fpd = nullptr, long long *fpi = nullptr,
-                       unsigned long long *fb_total = nullptr,  // fpd != nullptr: flagged IVF queries re-run inline
-                       int fb_cap = 0,  // ... except the first fb_cap, left to launch_ivf_fallback_chunks
-                       int i8_l2 = 0,  // the int8 image's L2 certificate (qres = ‖q − q̂‖, lower-bound scan keys)
-                       // the seeded int8 scan: pd / pi hold every query's candidate run (common.hpp
-                       // ivf_seed_run_slot), query q's of kSeedK + seed_cnt[q] entries; slot_off only places the runs
-                       const int *seed_cnt = nullptr);
+// launch_ivf_rerank's arguments: the scan's lists (pd / pi: nprobe slots of kslot entries per query, or slot_off's
+// slots), the filter depth k, the rows and the outputs; then what only some callers set.
+struct IvfRerankArgs {
+    const float *pd = nullptr;
+    const int *pi = nullptr, *slot_off = nullptr;
+    int nprobe = 0;
+    int64_t nq = 0;
+    int k = 0, kout = 0, metric = kL2;
+    const float *Q = nullptr, *codes = nullptr;
+    int d = 0;
+    const int64_t *ids = nullptr;
+    int64_t nrows = 0, label_offset = 0;
+    float xmax2 = 0.f;
+    float *D = nullptr;
+    int64_t *I = nullptr;
+    int *nflag = nullptr, *flagged = nullptr;
+    float eps = kSplit2Eps, rxmax = -1.f;
+    const float *qres = nullptr;
+    const int64_t *probes = nullptr, *list_off = nullptr;
+    int nlist = 0;
+    const unsigned *qbound = nullptr;
+    const float *qnorm = nullptr;
+    int kslot = 0, sub = 0;
+    // fpd != nullptr: flagged IVF queries re-run inline, except the first fb_cap, left to launch_ivf_fallback_chunks
+    const int *list_len = nullptr;
+    float *fpd = nullptr;
+    long long *fpi = nullptr;
+    unsigned long long *fb_total = nullptr;
+    int fb_cap = 0;
+    int i8_l2 = 0;  // the int8 image's L2 certificate (qres = ‖q − q̂‖, lower-bound scan keys)
+    // the seeded int8 scan: pd / pi hold every query's candidate run (common.hpp ivf_seed_run_slot), query q's of
+    // kSeedK + seed_cnt[q] entries; slot_off only places the runs
+    const int *seed_cnt = nullptr;
+};
+void launch_ivf_rerank(const IvfRerankArgs &a, hipStream_t st);
 // the rerank's first fb_cap flagged queries re-run in parallel (one wave per (query, probe, chunk) item); cpd/cpi:
 // fb_cap·nprobe·maxch·kout entries, done: fb_cap counters (zero on entry; left zero)
 void launch_ivf_fallback_chunks(const int *nflag, const int *flagged, int fb_cap, int nprobe, int maxch, int chunk_rows,
@@ -585,19 +616,30 @@ void launch_ivf_tile_half(const float *codes, const int64_t *list_off, const int
                           int nlist, int64_t total_pass, int d, float scale, void *dst, hipStream_t st,
                           const int64_t *pass_ids = nullptr);
 void launch_ivf_half_residual(const float *codes, int64_t n, int d, float scale, unsigned *out, hipStream_t st);
-// (the batch's queries already prepared: launch_ivf_split_queries_h, or launch_ivf_split_queries_i8 with i8mode)
-void launch_ivf_scan_mfma_h(int64_t nq, const void *qsplit, const float *its, float *qres, const float *qn, int d,
-                            int metric, const void *codes_h, const int64_t *tpass_off, const float *xn,
-                            const int64_t *list_off, const int *list_len, const int *cnt, const int *bucket_off,
-                            const int *item_off, const int *bucket, const int *slot_off, int nlist, int nprobe, int k,
-                            int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub = 0,
-                            int i8mode = 0, const float *xs8 = nullptr, const float *xr8 = nullptr,
-                            const float *qhn = nullptr,
-                            // the seeded scan's two launches (ivf_scan_mfma_h): 1 = the chunk-0 items (slot_off ==
-                            // nullptr: one slot per pair), 2 = the others (slot_off = the plan's slot prefixes; the
-                            // waves append their rows to the queries' candidate runs through cursor, one int per
-                            // query, zeroed by launch_ivf_seed_bound); goff = the plan's group prefix
-                            int phase = 0, const int *goff = nullptr, int *cursor = nullptr);
+// The image scan's arguments (the batch's queries already prepared: launch_ivf_split_queries_h, or
+// launch_ivf_split_queries_i8 with i8mode).
+struct IvfImageScanArgs {
+    // the prepared queries: image, 1/(t·s) or scales, residuals, the L2 key's query term; int8 L2: ‖q̂‖
+    int64_t nq = 0;
+    const void *qsplit = nullptr;
+    const float *its = nullptr;
+    float *qres = nullptr;
+    const float *qn = nullptr, *qhn = nullptr;
+    // the rows' image: fp16 or (i8mode) int8 with its per-row scales and, for L2, residuals
+    const void *codes = nullptr;
+    const int64_t *tpass_off = nullptr;
+    const float *xn = nullptr, *xs8 = nullptr, *xr8 = nullptr;
+    int i8mode = 0;
+    int d = 0, metric = kL2, k = 0, sub = 0;
+    unsigned *qbound = nullptr;
+    // the seeded scan's two launches (ivf_scan_mfma_h): 1 = the chunk-0 items (plan.slot_off == nullptr: one slot per
+    // pair), 2 = the others (plan.slot_off = the plan's slot prefixes; the waves append their rows to the queries'
+    // candidate runs through cursor, one int per query, zeroed by launch_ivf_seed_bound); both read plan.goff
+    int phase = 0;
+    int *cursor = nullptr;
+};
+void launch_ivf_scan_mfma_h(const IvfImageScanArgs &a, const IvfPlanView &plan, int64_t max_items, float *pd, int *pi,
+                            hipStream_t st);
 // The seeded int8 scan's step between its two launches, one block per query: the kSeedK best of the query's nprobe·kslot
 // chunk-0 entries (pa_d / pa_i, one kslot-entry slot per pair; pairs without rows skipped) into the tail of the query's
 // first candidate slot (cd / ci), the kSeedK-th key min'ed into qbound[q] when all kSeedK are real; cursor[q] = 0, the
@@ -688,23 +730,21 @@ void launch_ivf_remove_rows(const int64_t *labels, int64_t m, const int64_t *lis
 void launch_ivf_scatter_results(const float *Df, const int64_t *If, const int *idx, int nf, int kout, float *D,
                                 int64_t *I, hipStream_t st);
 void launch_ivf_scan_mfma_bf(int np, const float *Q, int64_t nq, void *qsplit, const float *qn, int d, int metric,
-                             const float *codes_t, const int64_t *tpass_off, const float *xn, const int64_t *list_off,
-                             const int *list_len, const int *cnt, const int *bucket_off, const int *item_off, const int *bucket,
-                             const int *slot_off, int nlist, int nprobe, int k, int64_t max_items, unsigned *qbound,
-                             float *pd, int *pi, hipStream_t st, int sub = 0);
+                             const float *codes_t, const int64_t *tpass_off, const float *xn, const IvfPlanView &plan,
+                             int k, int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub = 0);
 int ivf_group_size(int form, int d);  // queries per work item of the form's scan kernel
 int ivf_chunk_rows();
 bool ivf_plan_query_major();
-void launch_ivf_scan_bigk(const float *Q, int d, int metric, const float *codes, const int64_t *list_off,
-                          const int *list_len, const int64_t *probes, int64_t npairs, int nprobe, const int *slot_off, int64_t nslots,
-                          int k, float *pd, int *pi, hipStream_t st);
+void launch_ivf_scan_bigk(const float *Q, int d, int metric, const float *codes, const IvfPlanView &plan,
+                          const int64_t *probes, int64_t npairs, int64_t nslots, int k, float *pd, int *pi, hipStream_t st);
 size_t ivf_scan_smem_bytes();
+// (aligned16: the queries and the codes both start on 16 bytes)
+bool ivf_dot_supported(int d, bool aligned16);
 bool ivf_dot_supported(const float *Q, int d, const float *codes);
-void launch_ivf_scan(const float *Q, const float *qn, int d, int metric, int form, const float *codes,
-                     const float *xn, const int64_t *list_off, const int *list_len, const int *cnt,
-                     const int *bucket_off, const int *item_off, const int *bucket, const int *slot_off, int nlist,
-                     int nprobe, int64_t nq,
-                     int k, int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st);
+void launch_ivf_scan(const float *Q, const float *qn, int d, int metric, int form, const float *codes, const float *xn,
+                     const IvfPlanView &plan, int64_t nq, int k, int64_t max_items, unsigned *qbound, float *pd, int *pi,
+                     hipStream_t st);
+bool ivf_mfma_supported(int d, bool aligned16, int k);
 bool ivf_mfma_supported(const float *Q, int d, const float *codes, int k);
 int ivf_mfma_group(int d);
 int64_t ivf_mfma_pass_floats(int d);  // floats per 32-row pass of the tiled codes
@@ -712,9 +752,7 @@ void launch_ivf_tile_codes(const float *codes, const int64_t *list_off, const in
                            int nlist, int64_t total_pass, int d, float *dst, hipStream_t st,
                            const int64_t *pass_ids = nullptr);
 void launch_ivf_scan_mfma(const float *Q, const float *qn, int d, int metric, const float *codes_t,
-                          const int64_t *tpass_off, const float *xn,
-                          const int64_t *list_off, const int *list_len, const int *cnt, const int *bucket_off, const int *item_off,
-                          const int *bucket, const int *slot_off, int nlist, int nprobe, int k, int64_t max_items,
+                          const int64_t *tpass_off, const float *xn, const IvfPlanView &plan, int k, int64_t max_items,
                           unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub = 0);
 void launch_ivf_merge(const float *pd, const int *pi, const int64_t *ids, int64_t nrows, const int *slot_off, int nprobe, int64_t nq,
                       int k, int kout, float out_sign, float *D, int64_t *I, hipStream_t st);
