@@ -1312,11 +1312,11 @@ void launch_flat_i8_group_merge(const float *pd, const int *pi, int nw, int nq, 
 }
 
 
-void launch_flat_bf16_k64(const void *qimg, const float *qn, int64_t nq, const void *ximg, const float *xn, int64_t N,
-                          int nk, int metric, int nqt, int nsplit, int64_t tiles_per_split, int64_t tile_begin,
-                          int64_t tile_end, const float *bound, float *cand_d, int *cand_i, int *cand_n, int cap,
-                          bool resume, bool keys, hipStream_t st, const float *qscale, const float *xscale) {
-    HIPANN_REQUIRE(nk % 2 == 0 && cand_d && (keys || (bound && cand_i && cand_n && cap > 0)),
+void launch_flat_bf16_k64(const FlatK64Args &a, hipStream_t st) {
+    const int nk = a.nk, metric = a.metric, nqt = a.nqt, nsplit = a.nsplit;
+    const bool keys = a.keys;
+    const float *const qscale = a.qscale, *const xscale = a.xscale;
+    HIPANN_REQUIRE(nk % 2 == 0 && a.cand_d && (keys || (a.bound && a.cand_i && a.cand_n && a.cap > 0)),
                    "flat_bf16_k64: bad arguments");
     HIPANN_REQUIRE(!qscale == !xscale, "flat_bf16_k64: int8 needs both scales");
     HIPANN_REQUIRE((int64_t)nqt * nsplit < 0x7fffffff, "grid too large");
@@ -1324,11 +1324,12 @@ void launch_flat_bf16_k64(const void *qimg, const float *qn, int64_t nq, const v
     // 9.93 vs 8.22 ms at 10M, its accumulators shuffled between AGPRs and VGPRs; a tile loop whose first K-step starts
     // from a zero C operand instead of resetting the accumulators — 43 spills, 10.75 vs 7.71 ms)
     dim3 grid((unsigned)(nqt * nsplit)), block(64 * K64Geom<2>::W);
-    const k64_u32x4 *qa = static_cast<const k64_u32x4 *>(qimg);
-    const k64_u32x4 *xa = static_cast<const k64_u32x4 *>(ximg);
+    const k64_u32x4 *qa = static_cast<const k64_u32x4 *>(a.qimg);
+    const k64_u32x4 *xa = static_cast<const k64_u32x4 *>(a.ximg);
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid, block, K64_LDS, st, qa, qn, nq, xa, xn, N, nk, nqt, nsplit, tiles_per_split,
-                           tile_begin, tile_end, bound, cand_d, cand_i, cand_n, cap, resume ? 1 : 0, qscale, xscale);
+        hipLaunchKernelGGL(kern, grid, block, K64_LDS, st, qa, a.qn, a.nq, xa, a.xn, a.N, nk, nqt, nsplit,
+                           a.tiles_per_split, a.tile_begin, a.tile_end, a.bound, a.cand_d, a.cand_i, a.cand_n, a.cap,
+                           a.resume ? 1 : 0, qscale, xscale);
     };
     // HIPANN_K64_STAGGER=1 (A/B, measured and rejected in r06): the staggered schedule (STAG above).  Same-box A/B,
     // alternating: 10M x 768 kernel 7.86-7.92 → 9.08-9.10 ms, C2 1.00 → 1.23, C5 9.69 → 11.12 (with the epilogue at
@@ -1488,9 +1489,13 @@ extern "C" int hipann_debug_flat_pass(const float *Q, int64_t nq, const float *X
             launch_b16_tile_rows(Q, nq, d, K64_QM, qimg.p, 0);
             if (metric == kL2) launch_row_norms(Q, nq, d, qn.get<float>(), 0);
         }
-        launch_flat_bf16_k64(qimg.p, qnp, nq, ximg.p, xnp, N, nk, metric, (int)ceil_div(nq, (int64_t)K64_QM), nsplit,
-                             tiles_per_split, tile_begin, tile_end, bound, cand_d, cand_i, cand_n, cap, resume != 0,
-                             keys != 0, 0, qscp, xscp);
+        FlatK64Args a;
+        a.qimg = qimg.p, a.qn = qnp, a.nq = nq, a.ximg = ximg.p, a.xn = xnp, a.N = N, a.nk = nk, a.metric = metric;
+        a.nqt = (int)ceil_div(nq, (int64_t)K64_QM), a.nsplit = nsplit, a.tiles_per_split = tiles_per_split;
+        a.tile_begin = tile_begin, a.tile_end = tile_end, a.bound = bound;
+        a.cand_d = cand_d, a.cand_i = cand_i, a.cand_n = cand_n, a.cap = cap, a.resume = resume != 0, a.keys = keys != 0;
+        a.qscale = qscp, a.xscale = xscp;
+        launch_flat_bf16_k64(a, 0);
         return dbg_sync();  // (before the scratch buffers go)
     });
 }

@@ -404,11 +404,10 @@ void launch_flat_bf16_seed(const float *pd, int nsplit, int64_t nq, int k, float
     HIPANN_CHECK(hipGetLastError());
 }
 
-// the bounded passes of flat_b16k64.hip apply to 256-query blocks over an even chunk count (HIPANN_B16_K64=0:
-// one pass of the 32-dim list kernel below, A/B)
-bool flat_bf16_resumable(int64_t nq, int d, int k) {
-    static const bool k64 = [] { const char *e = std::getenv("HIPANN_B16_K64"); return !e || std::atoi(e); }();
-    return k64 && flat_bf16_waves(nq) == 8 && flat_bf16_k64_supported(b16_nk(d), k);
+// the bounded passes of flat_b16k64.hip apply to 256-query blocks over an even chunk count (k64_on = false,
+// HIPANN_B16_K64=0 in the caller's switches: one pass of the 32-dim list kernel below, A/B)
+bool flat_bf16_resumable(int64_t nq, int d, int k, bool k64_on) {
+    return k64_on && flat_bf16_waves(nq) == 8 && flat_bf16_k64_supported(b16_nk(d), k);
 }
 
 void launch_flat_bf16_topk(const float *Q, const float *qn, int64_t nq, void *qimg, const void *ximg, const float *xn,

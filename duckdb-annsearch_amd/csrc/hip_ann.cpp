@@ -408,6 +408,185 @@ static void flat_shard_search_bigk(FlatIndex &ix, FlatShard &sh, int64_t nq, con
                             D, I, st);
 }
 
+// ---- the Flat shard search: its switches, the mode a call resolves to ("Flat scan modes", has the
+// table), then the stages of flat_shard_launch in their order on the stream ----
+
+// The A/B switches of the shard search, read from the environment once (flat_tuning) and passed by value into the
+// resolver and the planner.  The defaults are the product's paths.
+struct FlatTuning {
+    int passes = 0;             // HIPANN_FLAT_PASSES: pins the bounded passes' count P (0: flat_pass_plan's choice)
+    bool i8_small = true;       // HIPANN_FLAT_I8_SMALL=0: every nq < 20 call stays on the fp32 scan
+    bool seed = true;           // HIPANN_FLAT_BF16_SEED=0: no seed bound on large tables, so no bounded passes
+    bool i8_prep_fused = true;  // HIPANN_I8_PREP_FUSED=0: the int8 queries by row_norms + i8_row_scale + i8_tile_rows
+    int64_t blocks = 0;         // HIPANN_FLAT_BF16_BLOCKS: target grid size of the image scans (0: one resident round)
+    int64_t pass_a = -1;        // HIPANN_FLAT_PASS_A: two passes, 1/x of each split in pass A (< 0: flat_pass_plan)
+    int64_t sample = 16384;     // HIPANN_FLAT_SAMPLE: rows of the seed sample (multiple of 256)
+    bool cand_debug = false;    // HIPANN_FLAT_CAND_DEBUG (set): the candidate buffers' fill and the flagged queries to stderr
+    bool b16_k64 = true;        // HIPANN_B16_K64=0: one pass of the 32-dim list kernel in place of the bounded passes
+};
+
+static const FlatTuning &flat_tuning() {
+    static const FlatTuning t = [] {
+        auto num = [](const char *name, long long dflt) {
+            const char *e = std::getenv(name);
+            return e ? std::atoll(e) : dflt;
+        };
+        FlatTuning v;
+        v.passes = (int)num("HIPANN_FLAT_PASSES", 0);
+        v.i8_small = num("HIPANN_FLAT_I8_SMALL", 1) != 0;
+        v.seed = num("HIPANN_FLAT_BF16_SEED", 1) != 0;
+        v.i8_prep_fused = num("HIPANN_I8_PREP_FUSED", 1) != 0;
+        v.blocks = num("HIPANN_FLAT_BF16_BLOCKS", 0);
+        v.pass_a = num("HIPANN_FLAT_PASS_A", -1);
+        v.sample = num("HIPANN_FLAT_SAMPLE", 16384);
+        v.cand_debug = std::getenv("HIPANN_FLAT_CAND_DEBUG") != nullptr;
+        v.b16_k64 = num("HIPANN_B16_K64", 1) != 0;
+        return v;
+    }();
+    return t;
+}
+
+enum FlatPath : int {
+    kFlatPathNone = 0,     // no queries: nothing is written
+    kFlatPathPads = 1,     // no rows: pads only
+    kFlatPathKeys = 2,     // the key matrix + per-row selection (flat_shard_search_bigk)
+    kFlatPathSmallI8 = 3,  // nq <= 16 on a large table: the int8 image's scan, 64 candidates, exact rerank
+    kFlatPathDirect = 4,   // nq < 20: the fp32 direct scan
+    kFlatPathLists = 5,    // per-split lists: the fp32 / 2-term / 3-term GEMM lists or (form 4) the bf16 list kernel
+    kFlatPathBounded = 6   // the bounded passes over the bf16 or int8 image
+};
+
+// Everything flat_resolve_mode reads; no pointer, no shard, no environment.
+struct FlatModeIn {
+    int64_t nq = 0, n = 0;
+    int d = 0, metric = kL2, k = 0, kout = 0;
+    int form = kFlatI8Exact;   // the requested form (FlatForm)
+    bool is_override = false;  // ... from the caller (a flagged query's re-run), not the index
+    FlatTuning tune;
+};
+
+// What a call resolves to.  Every field is set once, here; a stage that needs one reads it.
+struct FlatScanMode {
+    int path = kFlatPathNone;
+    int form = kFlatFp32;            // the scan that runs (paths Lists and Bounded; SmallI8: kFlatI8Exact)
+    bool record = false;             // the index's last_* is written (never by an override call or the Keys path) ...
+    int last_form = kFlatFp32, last_kfilt = 0;  // ... with these
+    bool exact = false;              // a filter of kscan candidates + the exact direct-form rerank
+    bool bounded = false, seeded = false;  // the bounded passes; a seed bound from a sample of the first rows
+    bool i8 = false, i8_prep = false;      // the int8 image filters; its queries by the fused preparation
+    int kscan = 0, k_user = 0;       // the scan's depth (kf on the exact forms), the caller's k (the re-run's)
+    int pend_kind = FlatPending::kNone, rerun_form = kFlatSplit3;  // what flat_shard_finish has left to do, on which form
+    bool need_qn = false;            // the path reads ‖q‖² ...
+    bool prep_qn = false;            // ... and the int8 query preparation writes it (no row_norms launch)
+    bool image() const { return form == kFlatBf16Exact || form == kFlatI8Exact; }
+};
+
+constexpr int64_t kFlatSeedMinRows = 8 * 65536;  // tables from here on get a seed bound (and may run bounded)
+constexpr int64_t kFlatI8SmallMinRows = 65536;
+
+// The exact forms' filter depth kf (0: not an exact form) and whether the form runs as the bounded passes.
+// kout ≤ kRerankMaxK: kf = 32 (the bf16 image: at 10M × 768 the 10th and 16th distances are ≈2 apart, inside its
+// rounding bound ≈1.3, the 10th and 32nd ≈5; the split scan: IP 32, L2 16).  Larger kout (request_k = k +
+// |tombstones|, faiss_index.cpp:713-715): kf = min(64, max(base, 2·kout)).  The list kernels hold kf in LDS (capped
+// by their launchers' LDS budget); the bounded passes take any kf ≤ 64.  The int8 rounding bound is ≈3× the bf16 one
+// (E ≈ 4.4 against 1.3-1.7 at 768 dims on U(-1, 1)): a 64-deep filter keeps the 10th distance clear of it (the
+// 10th-to-32nd gap is ≈5, the 10th-to-64th ≈8).
+static int flat_filter_depth(const FlatModeIn &in, int form, bool sampled, bool *bounded) {
+    *bounded = form == kFlatI8Exact;
+    if (form == kFlatI8Exact) return 64;
+    if (form != kFlatSplit2Exact && form != kFlatBf16Exact) return 0;
+    const int base = in.metric == kIP || form == kFlatBf16Exact ? kFlatRerankKIP : kRerankK;
+    const int kf = in.kout <= kRerankMaxK ? base : std::min(64, std::max(base, 2 * in.kout));
+    if (form == kFlatSplit2Exact) return std::min(kf, flat_gemm_topk_bf_kmax(2));
+    *bounded = flat_bf16_resumable(in.nq, in.d, kf, in.tune.b16_k64) && sampled;
+    return *bounded ? kf : std::min(kf, flat_bf16_topk_kmax(in.nq));
+}
+
+FlatScanMode flat_resolve_mode(const FlatModeIn &in) {
+    FlatScanMode m;
+    const int64_t nq = in.nq, n = in.n;
+    const int d = in.d, k = in.k, kout = in.kout;
+    m.kscan = m.k_user = k;
+    if (nq <= 0) return m;
+    if (n == 0) {
+        m.path = kFlatPathPads;
+        return m;
+    }
+    // Large k, or a small table (an IVF coarse quantizer: nq x nlist keys are a few MB): the GEMM writes the key
+    // matrix and one wave per query selects — the fused epilogue would spend its time filling empty lists, one query
+    // tile per CU.  nq < 20 on a table of ≤ 1024 rows (the coarse quantizer of the extension's nq = 1 call):
+    // direct-form keys over ≥ 16-row waves + one bitwise select per query row (the fused scan's nparts × k partial
+    // lists took one wave 47 µs to merge at nlist 1024).  This path leaves last_* as it was.
+    if (k > kFusedMaxK || (nq >= kBlasThreshold && n <= kSmallTable) ||
+        (nq < kBlasThreshold && n <= 1024 && kout <= 64 && scan_smem_bytes((int)nq, d) <= 64 * 1024)) {
+        m.path = kFlatPathKeys;
+        m.need_qn = nq >= kBlasThreshold && in.metric == kL2;
+        return m;
+    }
+    m.record = !in.is_override;
+    // nq < 20 on a large table (the extension's per-query calls, faiss_index.cpp:737): form 5's int8 image as the
+    // filter — flat_i8_scan (a quarter of the fp32 rows' bytes), 64 candidates per query, the exact direct-form
+    // rerank with the int8 residual bound; queries it cannot certify re-run on the fp32 direct scan.
+    if (nq <= flat_i8_scan_max_nq() && in.form == kFlatI8Exact && in.tune.i8_small && n >= kFlatI8SmallMinRows &&
+        d <= 1024 && kout <= flat_i8_scan_k() && k <= flat_i8_scan_k()) {
+        m.path = kFlatPathSmallI8;
+        m.form = m.last_form = kFlatI8Exact;
+        m.exact = m.i8 = true;
+        m.kscan = m.last_kfilt = flat_i8_scan_k();
+        m.pend_kind = FlatPending::kSmallI8;
+        m.rerun_form = kFlatFp32;
+        m.need_qn = in.metric == kL2;
+        return m;
+    }
+    if (nq < kBlasThreshold) {  // the direct form (fvec_L2sqr / fvec_inner_product)
+        m.path = kFlatPathDirect;
+        return m;
+    }
+    // BLAS form: ‖q‖² + ‖x‖² − 2 q·x on the matrix cores.  kFlatI8Exact runs only as the bounded passes (256-query
+    // blocks, >= 512K rows, d <= 1024 so the int32 sums convert to fp32 exactly); elsewhere the bf16 image's paths.
+    const bool sampled = in.tune.seed && n >= kFlatSeedMinRows;
+    const int want = in.form == kFlatI8Exact &&
+                             !(flat_bf16_resumable(nq, d, 64, in.tune.b16_k64) && sampled && d <= 1024)
+                         ? kFlatBf16Exact : in.form;
+    bool bounded = false;
+    const int kf = flat_filter_depth(in, want, sampled, &bounded);
+    // the list kernels need kf ≥ kout + 4 of margin; the bounded passes take any kout ≤ kf — a query whose kout-th
+    // distance is within the bound of the kf-th key goes to the all-candidate rerank, certified against the pass
+    // bound.  Otherwise: the 3-term split (fp32-level).
+    m.exact = kf > 0 && (kout <= kRerankMaxK || (bounded ? kout <= kf : kout + 4 <= kf));
+    m.kscan = m.exact ? kf : k;
+    const int lists = kf > 0 && !m.exact ? kFlatSplit3 : want;
+    // the split scans' LDS lists hold fewer rows at 3 terms (k <= 56 at 8 waves): a longer list takes the fp32
+    // matrix cores (exact fp32 products, lists up to 64)
+    const bool too_deep = (lists == kFlatSplit3 || lists == kFlatSplit2) &&
+                          m.kscan > flat_gemm_topk_bf_kmax(lists == kFlatSplit3 ? 3 : 2);
+    m.form = m.last_form = too_deep ? kFlatFp32 : lists;
+    m.last_kfilt = m.exact ? kf : 0;
+    m.bounded = m.exact && bounded;
+    m.seeded = m.image() && sampled;
+    m.i8 = m.form == kFlatI8Exact;
+    m.i8_prep = m.i8 && in.tune.i8_prep_fused;
+    m.path = m.bounded ? kFlatPathBounded : kFlatPathLists;
+    if (m.exact) m.pend_kind = FlatPending::kExact;  // flagged queries re-run on the 3-term split
+    m.need_qn = in.metric == kL2;
+    m.prep_qn = m.need_qn && m.i8_prep;
+    return m;
+}
+
+// max over n non-negative floats on the device, on the host (their bit patterns order as the values): one launch into
+// the scratch word sh.nflag (so before any flags), a 4-byte readback and a host synchronisation, counted — later
+// searches may run on other streams.  sh.tmpnorm, where the callers put the values, is released.
+static float device_max_to_host(FlatIndex &ix, FlatShard &sh, const float *v, int64_t n, hipStream_t st) {
+    sh.nflag.ensure(sizeof(int), sh.device);
+    launch_ivf_max_norm(v, n, sh.nflag.get<unsigned>(), st);
+    unsigned bits = 0;
+    HIPANN_CHECK(hipMemcpyAsync(&bits, sh.nflag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPANN_CHECK(hipStreamSynchronize(st));
+    ++ix.host_syncs;
+    sh.tmpnorm.release();
+    return bits_to_float(bits);
+}
+
 // The shard's tiled int8 image (form kFlatI8Exact): per-row scales max|x|/127, the rows' int8 units in the bf16
 // image's tile geometry, and the largest row residual ‖x − s·x̂‖ (the rerank bound's row term).  Built once.
 static void ensure_i8_image(FlatIndex &ix, FlatShard &sh, int d, hipStream_t st) {
@@ -417,19 +596,22 @@ static void ensure_i8_image(FlatIndex &ix, FlatShard &sh, int d, hipStream_t st)
     sh.tmpnorm.ensure(sizeof(float) * (size_t)sh.n, sh.device);
     launch_i8_row_scale(sh.xb, sh.n, d, sh.xscale.get<float>(), sh.tmpnorm.get<float>(), st);
     launch_i8_tile_rows(sh.xb, sh.xscale.get<float>(), sh.n, d, flat_bf16_tile_rows(), sh.xi8.p, st);
-    sh.nflag.ensure(sizeof(int), sh.device);
-    launch_ivf_max_norm(sh.tmpnorm.get<float>(), sh.n, sh.nflag.get<unsigned>(), st);  // max of non-negative
-    unsigned bits = 0;
-    HIPANN_CHECK(hipMemcpyAsync(&bits, sh.nflag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIPANN_CHECK(hipStreamSynchronize(st));
-    ++ix.host_syncs;
-    sh.tmpnorm.release();
-    std::memcpy(&sh.i8_rxmax, &bits, sizeof(float));
+    sh.i8_rxmax = device_max_to_host(ix, sh, sh.tmpnorm.get<float>(), sh.n, st);
     sh.xi8_ok = true;
 }
 
-// Search one shard: queries already on the shard's device.  Writes D (nq×kout fp32: raw distances,
-// ±inf pads) and I (nq×kout int64 labels, −1 pads) on the same device, asynchronously on `st`.
+// The shard's tiled bf16 image (flat_bf16.hip: one plain bf16 product per element) and the rows' largest bf16
+// rounding residual ‖x̂ − x‖ (the rerank's bound).  Built once.
+static void ensure_b16_image(FlatIndex &ix, FlatShard &sh, int d, hipStream_t st) {
+    if (sh.xb16_ok) return;
+    sh.xb16.ensure(flat_bf16_img_bytes(sh.n, d, flat_bf16_tile_rows()), sh.device);
+    launch_b16_tile_rows(sh.xb, sh.n, d, flat_bf16_tile_rows(), sh.xb16.p, st);
+    sh.tmpnorm.ensure(sizeof(float) * (size_t)sh.n, sh.device);
+    launch_b16_row_residual2(sh.xb, sh.n, d, sh.tmpnorm.get<float>(), st);
+    sh.bf16_rxmax = std::sqrt(device_max_to_host(ix, sh, sh.tmpnorm.get<float>(), sh.n, st)) * 1.0001f;
+    sh.xb16_ok = true;
+}
+
 // max‖x‖² of the shard (once per row set): the exact form's error bound
 static float flat_xmax2(FlatIndex &ix, FlatShard &sh, int d, hipStream_t st) {
     if (sh.xmax2 >= 0.f) return sh.xmax2;
@@ -439,17 +621,22 @@ static float flat_xmax2(FlatIndex &ix, FlatShard &sh, int d, hipStream_t st) {
         launch_row_norms(sh.xb, sh.n, d, sh.tmpnorm.get<float>(), st);
         xn = sh.tmpnorm.get<float>();
     }
-    sh.nflag.ensure(sizeof(int), sh.device);
-    launch_ivf_max_norm(xn, sh.n, sh.nflag.get<unsigned>(), st);
-    unsigned bits = 0;
-    HIPANN_CHECK(hipMemcpyAsync(&bits, sh.nflag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIPANN_CHECK(hipStreamSynchronize(st));
-    ++ix.host_syncs;
-    sh.tmpnorm.release();
-    float v;
-    std::memcpy(&v, &bits, sizeof(v));
-    sh.xmax2 = v;
-    return v;
+    sh.xmax2 = device_max_to_host(ix, sh, xn, sh.n, st);
+    return sh.xmax2;
+}
+
+// ‖q‖² of the batch in sh.qn, and the shard's note of whose they are (qn_of / qn_nq: the IVF scan reads them
+// afterwards).  The caller may have prepared them (qn_given: nothing to launch).  With `owed` the launch is left to
+// the int8 query preparation, which writes *owed (nullptr: nothing owed).
+static const float *flat_query_norms(FlatShard &sh, int64_t nq, const float *xq, int d, hipStream_t st,
+                                     float **owed = nullptr) {
+    const bool given = sh.qn_given == xq && sh.qn_given_nq == nq;
+    if (!given) sh.qn.ensure((size_t)nq * sizeof(float), sh.device);
+    if (owed) *owed = given ? nullptr : sh.qn.get<float>();
+    else if (!given) launch_row_norms(xq, nq, d, sh.qn.get<float>(), st);
+    sh.qn_of = xq;
+    sh.qn_nq = nq;
+    return sh.qn.get<float>();
 }
 
 // The bounded passes' plan: tile boundaries 0 = b₀ < b₁ < … < b_P = tps within every split.  Pass 0 admits the
@@ -458,10 +645,9 @@ static float flat_xmax2(FlatIndex &ix, FlatShard &sh, int d, hipStream_t st) {
 // the epilogue's slow path (measured ≈ 0.54 µs per candidate per query per 1024-query batch: C2 and 10M pass-A
 // sweeps, profiles/r04/passa_sweep_r04.txt), every pass ≈ 55 µs (its pipeline fill + the bound kernel), so P and
 // geometric boundaries b_p ≈ (S/(nsplit·rows))·g^p, g = (N/S)^{1/P}, minimise candidates·nq·0.54 ns + P·55 µs.
-// HIPANN_FLAT_PASSES pins P (A/B).
+// forced > 0 pins P (FlatTuning::passes, A/B).
 static std::vector<int64_t> flat_pass_plan(int64_t tps, int64_t nsplit, int64_t tile_rows, int64_t sample, int k,
-                                           int64_t nq) {
-    static const int forced = [] { const char *e = std::getenv("HIPANN_FLAT_PASSES"); return e ? std::atoi(e) : 0; }();
+                                           int64_t nq, int forced) {
     const double unit = (double)sample / ((double)nsplit * (double)tile_rows);  // the sample in tiles per split
     std::vector<int64_t> best{0, tps};
     double best_cost = 1e300;
@@ -501,511 +687,443 @@ static void flag_readback(FlatShard &sh, hipStream_t st) {
     launch_post_words(sh.nflag.p, sh.h_nflag.p, 1, ++sh.flag_seq, st);
 }
 
+// One call of flat_shard_launch: its arguments, the resolved mode and what the stages hand on.
+struct FlatCall {
+    FlatIndex &ix;
+    FlatShard &sh;
+    const int64_t nq;
+    const float *const xq;
+    const int kout;
+    float *const D;
+    int64_t *const I;
+    const hipStream_t st;
+    const FlatTuning tune;
+    const FlatScanMode m;
+    const int d, metric;
+    const float out_sign;
+    const float *qn = nullptr;  // ‖q‖² (L2), or nullptr
+    float *qn_owed = nullptr;   // ... still to be written, by the int8 query preparation
+    float xmax2 = 0.f;          // the exact forms' max ‖x‖²
+    float rxmax = -1.f;         // the rerank bound's row term of the image that filtered (−1: the 2-term split's eps)
+    int W = 0;                  // the image scans' waves per block (32 queries each)
+    int64_t nqt = 0, nsplit = 0, tps = 0;  // query tiles, column splits, row tiles per split
+};
+
+// What the scan stage leaves in part_d / part_i for the merge or the rerank, and, from the bounded passes, the
+// candidate buffers and pass bound for the flagged queries' second rerank (flat_shard_finish).
+struct FlatCandRun {
+    int lists = 0;             // lists per query, m.kscan entries each
+    bool flags_reset = false;  // nflag is zeroed and the overflowed queries are flagged already
+    const float *cd = nullptr, *bound = nullptr;
+    const int *ci = nullptr, *cn = nullptr;
+    int nsplit = 0, cap = 0;
+};
+
 // The exact Flat forms' rerank over the shard's rows (ivf_rerank_topk, slot lists query-major): the caller adds the
-// lists (pd, pi, nprobe = lists per query), the filter depth k and the image's residual terms.
-static IvfRerankArgs flat_rerank_args(FlatShard &sh, int64_t nq, int kout, int metric, const float *xq, int d,
-                                      float xmax2, float *D, int64_t *I) {
+// lists (pd, pi, nprobe = lists per query) and the filter depth k.
+static IvfRerankArgs flat_rerank_args(const FlatCall &c) {
+    FlatShard &sh = c.sh;
     IvfRerankArgs a;
-    a.nq = nq, a.kout = kout, a.metric = metric, a.Q = xq, a.codes = sh.xb, a.d = d, a.nrows = sh.n;
-    a.label_offset = sh.label_offset, a.xmax2 = xmax2, a.D = D, a.I = I;
+    a.nq = c.nq, a.kout = c.kout, a.metric = c.metric, a.Q = c.xq, a.codes = sh.xb, a.d = c.d, a.nrows = sh.n;
+    a.label_offset = sh.label_offset, a.xmax2 = c.xmax2, a.D = c.D, a.I = c.I;
     a.nflag = sh.nflag.get<int>(), a.flagged = sh.flagged.get<int>();
+    // (int8: the row term and each query's own residual from the int8 images; qres makes the rerank read them)
+    a.rxmax = c.rxmax, a.qres = c.m.i8 ? sh.qres.get<float>() : nullptr;
     return a;
 }
 
+static void flat_reset_flags(FlatCall &c) {
+    c.sh.nflag.ensure(sizeof(int), c.sh.device);
+    c.sh.flagged.ensure(sizeof(int) * (size_t)c.nq, c.sh.device);
+    HIPANN_CHECK(hipMemsetAsync(c.sh.nflag.p, 0, sizeof(int), c.st));
+}
+
+// Path SmallI8: the int8 image and max ‖x‖² (built once), ‖q‖², flat_i8_scan's per-wave lists merged to G groups of
+// 64 per query, the rerank.
+static void flat_small_i8(FlatCall &c) {
+    FlatShard &sh = c.sh;
+    const int64_t nq = c.nq;
+    const int kf = c.m.kscan;
+    ensure_i8_image(c.ix, sh, c.d, c.st);
+    c.xmax2 = flat_xmax2(c.ix, sh, c.d, c.st);
+    c.rxmax = sh.i8_rxmax;
+    if (c.m.need_qn) c.qn = flat_query_norms(sh, nq, c.xq, c.d, c.st);
+    const int64_t nw = flat_i8_scan_waves(sh.n);
+    const int G = (int)std::min<int64_t>(64, nw);
+    sh.qscale.ensure(sizeof(float) * (size_t)nq, sh.device);
+    sh.qres.ensure(sizeof(float) * (size_t)nq, sh.device);
+    sh.qimg.ensure((size_t)nq * flat_i8_nk(c.d) * 4 * 16, sh.device);
+    sh.part_d.ensure((size_t)nw * nq * kf * sizeof(float), sh.device);
+    sh.part_i.ensure((size_t)nw * nq * kf * sizeof(int), sh.device);
+    sh.mid_d.ensure((size_t)G * nq * kf * sizeof(float), sh.device);
+    sh.mid_i.ensure((size_t)G * nq * kf * sizeof(long long), sh.device);
+    {
+        ScopedTiming t(c.ix.timer_main, c.st);
+        launch_flat_i8_scan(c.xq, nq, c.d, c.metric, sh.xi8.p, sh.xscale.get<float>(), sh.xn.get<float>(), sh.n,
+                            sh.qscale.get<float>(), sh.qres.get<float>(), c.qn, sh.qimg.p, sh.part_d.get<float>(),
+                            sh.part_i.get<int>(), nw, c.st);
+    }
+    flat_reset_flags(c);
+    ScopedTiming t(c.ix.timer_merge, c.st);
+    float *md = sh.mid_d.get<float>();
+    int *mi = reinterpret_cast<int *>(sh.mid_i.p);
+    launch_flat_i8_group_merge(sh.part_d.get<float>(), sh.part_i.get<int>(), (int)nw, (int)nq, G, md, mi, c.st);
+    IvfRerankArgs a = flat_rerank_args(c);
+    a.pd = md, a.pi = mi, a.nprobe = G, a.k = kf;
+    launch_ivf_rerank(a, c.st);
+}
+
+// Path Direct (fvec_L2sqr / fvec_inner_product): per-wave lists, merged per query.
+static void flat_direct_scan(FlatCall &c) {
+    FlatShard &sh = c.sh;
+    const int64_t nq = c.nq;
+    const int d = c.d, k = c.m.kscan, kout = c.kout;
+    // ≥ 512 rows per wave on large tables; small ones (the IVF coarse quantizer's 1024 centroids at
+    // nq = 1) are spread over waves of ≥ 16 rows (2 waves of 512 rows took 234 us for 1024 × 768)
+    const int64_t want = std::min<int64_t>(8192, std::max<int64_t>(std::min<int64_t>(256, ceil_div(sh.n, 16)),
+                                                                     ceil_div(sh.n, 512)));
+    const int64_t rpw = ceil_div(sh.n, want);
+    const int64_t nw_alloc = ceil_div(ceil_div(sh.n, rpw), 4) * 4;
+    // the scan holds its queries in ≤ 64 KiB of LDS: larger d·nq runs as several query chunks (d = 1536 fits 10
+    // queries; one query up to d = 16384)
+    int qc = (int)nq;
+    while (qc > 1 && scan_smem_bytes(qc, d) > 64 * 1024) --qc;
+    HIPANN_REQUIRE(scan_smem_bytes(qc, d) <= 64 * 1024, "dimension too large for the scan path");
+    sh.part_d.ensure((size_t)nw_alloc * qc * k * sizeof(float), sh.device);
+    sh.part_i.ensure((size_t)nw_alloc * qc * k * sizeof(int), sh.device);
+    const int groups = (int)std::min<int64_t>(256, ceil_div(nw_alloc, 32));
+    if (nw_alloc > 256) {
+        sh.mid_d.ensure(sizeof(float) * (size_t)groups * qc * kout, sh.device);
+        sh.mid_i.ensure(sizeof(long long) * (size_t)groups * qc * kout, sh.device);
+    }
+    for (int64_t q0 = 0; q0 < nq; q0 += qc) {
+        const int64_t nc = std::min<int64_t>(qc, nq - q0);
+        {
+            ScopedTiming t(c.ix.timer_main, c.st);
+            launch_flat_scan_topk(c.xq + q0 * d, (int)nc, sh.xb, sh.n, d, c.metric, k, (int)nw_alloc, rpw,
+                                  sh.part_d.get<float>(), sh.part_i.get<int>(), c.st);
+        }
+        ScopedTiming t(c.ix.timer_merge, c.st);
+        if (nw_alloc > 256) {
+            // thousands of per-wave lists: groups of ~32 merged by one wave each, then the group lists by one
+            // 4-wave block per query (one wave per query took ~1 ms for 8192 lists at 10M rows, nq = 1)
+            launch_merge_parts_2level<int>(sh.part_d.get<float>(), sh.part_i.get<int>(), (int)nw_alloc, nc, k, kout,
+                                           sh.label_offset, 1.f, c.out_sign, c.D + q0 * kout, c.I + q0 * kout,
+                                           sh.mid_d.get<float>(), sh.mid_i.get<long long>(), groups, c.st);
+        } else {
+            launch_merge_parts<int>(sh.part_d.get<float>(), sh.part_i.get<int>(), (int)nw_alloc, nc, k, kout,
+                                    sh.label_offset, 1.f, c.out_sign, c.D + q0 * kout, c.I + q0 * kout, c.st);
+        }
+    }
+}
+
+// The exact forms' bound terms: max ‖x‖² (cached; its first computation uses sh.nflag as scratch, so before any
+// flags), the int8 image (one int8 product per element, int32 sums, per-row scales; built once) and the row residual
+// of the image that filters.  The bf16 term is read here, ahead of the image's first build, as it always was: the
+// first bf16 search of a row set reranks with the value from before the build.
+static void flat_bound_terms(FlatCall &c) {
+    if (!c.m.exact) return;
+    c.xmax2 = flat_xmax2(c.ix, c.sh, c.d, c.st);
+    if (c.m.i8) ensure_i8_image(c.ix, c.sh, c.d, c.st);
+    c.rxmax = c.m.i8 ? c.sh.i8_rxmax : c.m.form == kFlatBf16Exact ? c.sh.bf16_rxmax : -1.f;
+}
+
+// Column splits of a table of n rows in tiles of tile_rows for about `blocks` blocks over nqt query tiles: whole
+// tiles per split, no empty split.  round8 (the GEMM lists): a multiple of 8 splits before the tiles are dealt out.
+struct FlatSplit {
+    int64_t nsplit, tps;
+};
+static FlatSplit flat_split_geometry(int64_t blocks, int64_t nqt, int64_t n, int64_t tile_rows, bool round8) {
+    const int64_t ntiles = ceil_div(n, tile_rows);
+    const int64_t fit = std::min<int64_t>(std::max<int64_t>(1, ceil_div(blocks, nqt)), ntiles);
+    const int64_t tps = ceil_div(ntiles, round8 && fit >= 8 ? fit / 8 * 8 : fit);
+    const int64_t nsplit = ceil_div(ntiles, tps);
+    HIPANN_REQUIRE(nqt * nsplit < (int64_t)0x7fffffff, "grid too large");
+    return {nsplit, tps};
+}
+
+// The lists' geometry and scratch.  Image scans: one round of resident blocks (W = 8 / 4: one block per CU; W = 2:
+// two) — fewer, longer splits admit fewer candidates into the per-split lists (≈ k·ln(rows / k) per list), the
+// epilogue's slow path.  GEMM lists: ≈2048 blocks; small tables (an IVF coarse quantizer: 1024 centroids = 8 tiles)
+// go down to one column tile per block rather than leaving CUs idle.
+static void flat_lists_scratch(FlatCall &c) {
+    FlatShard &sh = c.sh;
+    FlatSplit s;
+    if (c.m.image()) {
+        c.W = flat_bf16_waves(c.nq);
+        c.nqt = ceil_div(c.nq, 32 * c.W);
+        s = flat_split_geometry(c.tune.blocks > 0 ? c.tune.blocks : (c.W == 2 ? 512 : 256), c.nqt, sh.n,
+                                flat_bf16_tile_rows(), false);
+        sh.qimg.ensure(c.m.i8 ? flat_i8_img_bytes(c.nq, c.d, 32 * c.W) : flat_bf16_img_bytes(c.nq, c.d, 32 * c.W),
+                       sh.device);
+    } else {
+        c.nqt = ceil_div(c.nq, 128);
+        s = flat_split_geometry(2048, c.nqt, sh.n, 128, true);
+    }
+    c.nsplit = s.nsplit, c.tps = s.tps;
+    sh.part_d.ensure((size_t)c.nsplit * c.nq * c.m.kscan * sizeof(float), sh.device);
+    sh.part_i.ensure((size_t)c.nsplit * c.nq * c.m.kscan * sizeof(int), sh.device);
+}
+
+static FlatCandRun flat_lists_run(const FlatCall &c) {
+    FlatCandRun r;
+    r.lists = (int)c.nsplit;
+    return r;
+}
+
+// GEMM lists: fp32 matrix cores, or the 2- / 3-term split-bf16 products (query-major lists for the rerank).
+static FlatCandRun flat_gemm_lists(FlatCall &c) {
+    FlatShard &sh = c.sh;
+    const int k = c.m.kscan;
+    if (c.m.form == kFlatFp32) {
+        launch_flat_gemm_topk(c.xq, c.qn, c.nq, sh.xb, sh.xn.get<float>(), sh.n, c.d, c.metric, k, (int)c.nsplit, c.tps,
+                              sh.part_d.get<float>(), sh.part_i.get<int>(), c.st);
+    } else {
+        const int np = c.m.form == kFlatSplit3 ? 3 : 2;
+        sh.qsplit.ensure(flat_bf_qsplit_bytes(c.nq, c.d, np), sh.device);
+        launch_flat_gemm_topk_bf(np, c.xq, c.qn, c.nq, sh.qsplit.get<void>(), sh.xb, sh.xn.get<float>(), sh.n, c.d,
+                                 c.metric, k, (int)c.nsplit, c.tps, sh.part_d.get<float>(), sh.part_i.get<int>(),
+                                 c.m.exact ? 1 : 0, c.st);
+    }
+    return flat_lists_run(c);
+}
+
+// The bf16 list kernel.  Seeded (large tables): first the k-th best key of each query over the first 64K rows — the
+// same kernel's lists over them and flat_bf16_seed (its lists start empty: every row an insert, ≈1 ms at 1024
+// queries — what the bounded passes' keys mode replaces); the scan then admits only keys ≤ that bound.
+static FlatCandRun flat_bf16_lists(FlatCall &c) {
+    FlatShard &sh = c.sh;
+    const int64_t nq = c.nq;
+    const int k = c.m.kscan;
+    if (c.m.seeded) {
+        const int64_t seed_rows = 65536;
+        const int64_t stiles = seed_rows / flat_bf16_tile_rows();
+        const int64_t snsplit = std::min<int64_t>(stiles, std::max<int64_t>(1, ceil_div(256, c.nqt)));
+        const int64_t stps = ceil_div(stiles, snsplit);
+        sh.seed.ensure(sizeof(float) * ((size_t)snsplit * nq * k * 2 + (size_t)nq), sh.device);
+        float *spd = sh.seed.get<float>() + nq;
+        int *spi = reinterpret_cast<int *>(spd + (size_t)snsplit * nq * k);
+        launch_flat_bf16_topk(c.xq, c.qn, nq, sh.qimg.p, sh.xb16.p, sh.xn.get<float>(), seed_rows, c.d, c.metric, k,
+                              (int)ceil_div(stiles, stps), stps, spd, spi, nullptr, false, c.st);
+        launch_flat_bf16_seed(spd, (int)ceil_div(stiles, stps), nq, k, sh.seed.get<float>(), c.st);
+    }
+    launch_flat_bf16_topk(c.xq, c.qn, nq, sh.qimg.p, sh.xb16.p, sh.xn.get<float>(), sh.n, c.d, c.metric, k,
+                          (int)c.nsplit, c.tps, sh.part_d.get<float>(), sh.part_i.get<int>(),
+                          c.m.seeded ? sh.seed.get<float>() : nullptr, c.m.seeded, c.st);
+    return flat_lists_run(c);
+}
+
+// The bounded passes' plan for this call: the seed sample's rows, the passes' tile boundaries within every split —
+// pass p scans tiles [pb[p], pb[p+1]) under the bound from everything before it (the seed for pass 0) — and the
+// per-(query, split) candidate capacity.
+struct FlatPassPlan {
+    int64_t sample;
+    std::vector<int64_t> pb;
+    int cap;
+};
+static FlatPassPlan flat_plan_passes(const FlatCall &c) {
+    FlatPassPlan p;
+    const int64_t R = flat_bf16_tile_rows(), div = c.tune.pass_a;
+    p.sample = std::max<int64_t>(256, std::min<int64_t>(c.tune.sample / 256 * 256, flat_keys_kth_max()));
+    if (div < 0) p.pb = flat_pass_plan(c.tps, c.nsplit, R, p.sample, c.m.kscan, c.nq, c.tune.passes);
+    else if (div > 1 && c.tps / div >= 1) p.pb = {0, c.tps / div, c.tps};
+    else p.pb = {0, c.tps};
+    p.cap = flat_pass_cap(p.pb, c.nsplit, R, p.sample, c.m.kscan);
+    return p;
+}
+
+// The batch's query image in the scan's format; int8: with the queries' scales and residuals (the rerank's query
+// term), by the fused preparation (which also writes the ‖q‖² still owed) or its three-launch form.
+static void flat_bounded_queries(FlatCall &c) {
+    FlatShard &sh = c.sh;
+    if (!c.m.i8) return launch_b16_tile_rows(c.xq, c.nq, c.d, 32 * c.W, sh.qimg.p, c.st);
+    sh.qscale.ensure(sizeof(float) * (size_t)c.nq, sh.device);
+    sh.qres.ensure(sizeof(float) * (size_t)c.nq, sh.device);
+    if (c.m.i8_prep) {
+        launch_i8_query_prep(c.xq, c.nq, c.d, c.qn_owed, sh.qscale.get<float>(), sh.qres.get<float>(), 32 * c.W,
+                             sh.qimg.p, c.st);
+    } else {
+        launch_i8_row_scale(c.xq, c.nq, c.d, sh.qscale.get<float>(), sh.qres.get<float>(), c.st);
+        launch_i8_tile_rows(c.xq, sh.qscale.get<float>(), c.nq, c.d, 32 * c.W, sh.qimg.p, c.st);
+    }
+}
+
+// HIPANN_FLAT_CAND_DEBUG: the candidate cells' fill after the passes (a host synchronisation of its own)
+static void flat_cand_debug_print(const FlatCall &c, const FlatPassPlan &p, const FlatCandRun &r) {
+    const size_t ncell = (size_t)c.nq * r.nsplit;
+    std::vector<int> hn(ncell);
+    std::vector<float> hb((size_t)c.nq);
+    HIPANN_CHECK(hipMemcpyAsync(hn.data(), r.cn, sizeof(int) * ncell, hipMemcpyDeviceToHost, c.st));
+    HIPANN_CHECK(hipMemcpyAsync(hb.data(), r.bound, sizeof(float) * c.nq, hipMemcpyDeviceToHost, c.st));
+    HIPANN_CHECK(hipStreamSynchronize(c.st));
+    long long tot = 0;
+    int mx = 0;
+    for (int v : hn) { tot += v; mx = std::max(mx, v); }
+    std::fprintf(stderr, "hipann flat cand: nsplit %lld tps %lld passes %zu pass0 %lld cap %d mean %.2f max %d bound[0] %g\n",
+                 (long long)r.nsplit, (long long)c.tps, p.pb.size() - 1, (long long)p.pb[1], r.cap,
+                 (double)tot / (double)ncell, mx, (double)hb[0]);
+}
+
+// Bounded passes (64-dim K-step kernel, flat_b16k64.hip).  The seed: the kernel's keys mode over a sample of the
+// first rows (a dense nq × S matrix, one tile per block, per chunk of 1024 queries = 4 query tiles through one 64 MB
+// slab of keys) and its k-th order statistic (flat_keys_kth).  Then every row with key ≤ the bound goes to a
+// per-(query, split) candidate buffer.  Pass 0 covers the first tiles of every split under the 16K-row seed bound;
+// after each pass the bound is re-merged from all candidates so far (the k-th best key over every row scanned) and
+// the next pass continues (flat_pass_plan: at 10M rows 4 passes over 5 / 20 / 98 / 488 tiles per split, ≈ 8.5
+// candidates per query and split), no row scanned twice.  flat_cand_select keeps each query's k best for the rerank.
+static FlatCandRun flat_bounded_passes(FlatCall &c) {
+    FlatShard &sh = c.sh;
+    const int64_t nq = c.nq, seed_qc = 1024;
+    const int k = c.m.kscan, QM = 32 * c.W;
+    const FlatPassPlan p = flat_plan_passes(c);
+    const size_t ncell = (size_t)nq * c.nsplit;
+    sh.seed.ensure(sizeof(float) * (size_t)nq, sh.device);
+    sh.cand.ensure(std::max(ncell * ((size_t)p.cap * 8 + 4), (size_t)std::min(nq, seed_qc) * p.sample * sizeof(float)),
+                   sh.device);
+    flat_bounded_queries(c);
+    float *cd = sh.cand.get<float>(), *bound = sh.seed.get<float>();
+    int *ci = reinterpret_cast<int *>(cd + ncell * p.cap), *cn = ci + ncell * p.cap;
+    FlatCandRun r;
+    r.cd = cd, r.ci = ci, r.cn = cn, r.bound = bound, r.nsplit = (int)c.nsplit, r.cap = p.cap;
+    FlatK64Args a;  // the operands: the images, their chunk count and (int8) scales, the L2 key terms
+    a.qimg = sh.qimg.p, a.qn = c.qn, a.nq = nq, a.xn = sh.xn.get<float>(), a.metric = c.metric;
+    a.ximg = c.m.i8 ? sh.xi8.p : sh.xb16.p, a.nk = c.m.i8 ? flat_i8_nk(c.d) : (int)ceil_div(c.d, 32);
+    a.qscale = c.m.i8 ? sh.qscale.get<float>() : nullptr, a.xscale = c.m.i8 ? sh.xscale.get<float>() : nullptr;
+    a.cand_d = cd;
+    const size_t qtile_bytes = c.m.i8 ? flat_i8_img_bytes(QM, c.d, QM) : flat_bf16_img_bytes(QM, c.d, QM);
+    for (int64_t c0 = 0; c0 < nq; c0 += seed_qc) {  // keys mode: the sample's tiles as splits of one tile
+        FlatK64Args s = a;
+        s.qimg = static_cast<const char *>(sh.qimg.p) + (size_t)(c0 / QM) * qtile_bytes;
+        s.qn = c.qn ? c.qn + c0 : nullptr, s.qscale = a.qscale ? a.qscale + c0 : nullptr;
+        s.nq = std::min(seed_qc, nq - c0), s.N = p.sample, s.keys = true;
+        s.nqt = (int)ceil_div(s.nq, QM), s.nsplit = (int)(p.sample / flat_bf16_tile_rows());
+        s.tiles_per_split = 1, s.tile_begin = 0, s.tile_end = 1;
+        launch_flat_bf16_k64(s, c.st);
+        launch_flat_keys_kth(cd, (int)p.sample, s.nq, k, bound + c0, c.st);
+    }
+    a.N = sh.n, a.nqt = (int)c.nqt, a.nsplit = (int)c.nsplit, a.tiles_per_split = c.tps;
+    a.bound = bound, a.cand_i = ci, a.cand_n = cn, a.cap = p.cap;
+    for (size_t i = 0; i + 1 < p.pb.size(); ++i) {
+        a.tile_begin = p.pb[i], a.tile_end = p.pb[i + 1], a.resume = i > 0;
+        launch_flat_bf16_k64(a, c.st);
+        if (i + 2 < p.pb.size()) launch_flat_cand_bound(cd, cn, r.nsplit, r.cap, nq, k, bound, c.st);
+    }
+    // overflowed queries are flagged here, ahead of the rerank's own flags (the fallback re-runs both)
+    flat_reset_flags(c);
+    launch_flat_cand_select(r.cd, r.ci, r.cn, r.nsplit, r.cap, nq, k, sh.part_d.get<float>(), sh.part_i.get<int>(),
+                            sh.nflag.get<int>(), sh.flagged.get<int>(), c.st);
+    if (c.tune.cand_debug) flat_cand_debug_print(c, p, r);
+    r.lists = 1, r.flags_reset = true;
+    return r;
+}
+
+// Exact forms: each query's lists merged to the best scan keys, those rows recomputed in the direct form and
+// bound-checked (ivf_rerank_topk, slot lists query-major); flagged queries re-run in flat_shard_finish.
+static void flat_rerank(FlatCall &c, const FlatCandRun &r) {
+    if (!r.flags_reset) flat_reset_flags(c);
+    ScopedTiming t(c.ix.timer_merge, c.st);
+    IvfRerankArgs a = flat_rerank_args(c);
+    a.pd = c.sh.part_d.get<float>(), a.pi = c.sh.part_i.get<int>(), a.nprobe = r.lists, a.k = c.m.kscan;
+    launch_ivf_rerank(a, c.st);
+}
+
+static void flat_merge_lists(FlatCall &c, const FlatCandRun &r) {
+    ScopedTiming t(c.ix.timer_merge, c.st);
+    launch_merge_parts<int>(c.sh.part_d.get<float>(), c.sh.part_i.get<int>(), r.lists, c.nq, c.m.kscan, c.kout,
+                            c.sh.label_offset, 1.f, c.out_sign, c.D, c.I, c.st);
+}
+
+// What flat_shard_finish has left to do, from the mode and the stages' results — the one place a FlatPending is built.
+static FlatPending flat_pending(const FlatCall &c, const FlatCandRun &r) {
+    FlatPending p;
+    p.kind = c.m.pend_kind, p.rerun_form = c.m.rerun_form, p.i8 = c.m.i8;
+    p.nq = c.nq, p.xq = c.xq, p.k = c.m.k_user, p.kout = c.kout, p.D = c.D, p.I = c.I;
+    p.cr_d = r.cd, p.cr_bound = r.bound, p.cr_i = r.ci, p.cr_n = r.cn, p.cr_nsplit = r.nsplit, p.cr_cap = r.cap;
+    p.xmax2 = c.xmax2, p.rxmax = c.rxmax;
+    return p;
+}
+
 // Launch phase of a shard search: every kernel of the search up to the exact forms' flag count, enqueued on `st`
-// without a host synchronisation.  pend says what flat_shard_finish has left to do (kNone: the output is complete
+// without a host synchronisation (queries already on the shard's device; D: nq×kout fp32 raw distances, ±inf pads;
+// I: nq×kout int64 labels, −1 pads).  pend says what flat_shard_finish has left to do (kNone: the output is complete
 // once `st` drains).
 static void flat_shard_launch(FlatIndex &ix, FlatShard &sh, int64_t nq, const float *xq, int k, int kout, float *D,
                               int64_t *I, hipStream_t st, int form_override, FlatPending &pend) {
     pend = FlatPending{};
     DeviceGuard g(sh.device);
-    const int d = ix.d, metric = ix.metric;
-    const float out_sign = metric == kIP ? -1.f : 1.f;
     HIPANN_REQUIRE(k <= HIPANN_MAX_K, "k larger than HIPANN_MAX_K");
-    // set below when this call computes ‖q‖² into sh.qn (or already: the caller prepared it, qn_given)
+    const FlatModeIn in{nq, sh.n, ix.d, ix.metric, k, kout, form_override >= 0 ? form_override : ix.form,
+                        form_override >= 0, flat_tuning()};
+    FlatCall c{ix, sh, nq, xq, kout, D, I, st, in.tune, flat_resolve_mode(in), ix.d, ix.metric,
+               ix.metric == kIP ? -1.f : 1.f};
+    const FlatScanMode &m = c.m;
+    // sh.qn holds ‖q‖² of this batch only if the caller prepared it, until flat_query_norms says otherwise
     sh.qn_of = sh.qn_given == xq && sh.qn_given_nq == nq ? xq : nullptr;
     sh.qn_nq = nq;
-    if (nq <= 0) return;
-    if (sh.n == 0) {  // no rows: pads only
-        launch_merge_parts<int>(nullptr, nullptr, 0, nq, k, kout, sh.label_offset, 1.f, out_sign, D, I, st);
-        return;
-    }
+    if (m.path == kFlatPathNone) return;
+    if (m.path == kFlatPathPads)
+        return launch_merge_parts<int>(nullptr, nullptr, 0, nq, k, kout, sh.label_offset, 1.f, c.out_sign, D, I, st);
     HIPANN_REQUIRE(sh.n <= (int64_t)0x7ffffffe, "shard larger than 2^31-2 rows");
-    // Large k, or a small table (an IVF coarse quantizer: nq x nlist keys are a few MB): the GEMM writes
-    // the key matrix and one wave per query selects — the fused epilogue would spend its time
-    // filling empty lists, one query tile per CU.
-    // nq < 20 on a table of ≤ 1024 rows (the coarse quantizer of the extension's nq = 1 call): direct-form
-    // keys over ≥ 16-row waves + one bitwise select per query row (the fused scan's nparts × k partial
-    // lists took one wave 47 µs to merge at nlist 1024)
-    if (k > kFusedMaxK || (nq >= kBlasThreshold && sh.n <= kSmallTable) ||
-        (nq < kBlasThreshold && sh.n <= 1024 && kout <= 64 && scan_smem_bytes((int)nq, d) <= 64 * 1024)) {
-        const float *qn = nullptr;
-        if (nq >= kBlasThreshold && metric == kL2) {
-            if (!(sh.qn_given == xq && sh.qn_given_nq == nq)) {
-                sh.qn.ensure((size_t)nq * sizeof(float), sh.device);
-                launch_row_norms(xq, nq, d, sh.qn.get<float>(), st);
-            }
-            qn = sh.qn.get<float>();
-            sh.qn_of = xq;
-            sh.qn_nq = nq;
-        }
-        flat_shard_search_bigk(ix, sh, nq, xq, qn, k, kout, D, I, st);
-        return;
-    }
-    // nq < 20 on a large table (the extension's per-query calls, faiss_index.cpp:737): form 5's int8 image as the
-    // filter — flat_i8_scan (a quarter of the fp32 rows' bytes), 64 candidates per query, the exact direct-form
-    // rerank with the int8 residual bound; queries it cannot certify re-run on the fp32 direct scan below.
-    // HIPANN_FLAT_I8_SMALL=0 keeps every nq < 20 call on the fp32 scan (A/B).
-    static const bool i8_small_env = [] { const char *e = std::getenv("HIPANN_FLAT_I8_SMALL"); return !e || std::atoi(e); }();
-    const int req_form = form_override >= 0 ? form_override : ix.form;
-    if (nq <= flat_i8_scan_max_nq() && req_form == kFlatI8Exact && i8_small_env && sh.n >= 65536 && d <= 1024 &&
-        kout <= flat_i8_scan_k() && k <= flat_i8_scan_k()) {
-        const int kf = flat_i8_scan_k();
-        ensure_i8_image(ix, sh, d, st);
-        const float xmax2 = flat_xmax2(ix, sh, d, st);
-        const int64_t nw = flat_i8_scan_waves(sh.n);
-        const int G = (int)std::min<int64_t>(64, nw);
-        const float *qn = nullptr;
-        if (metric == kL2) {
-            sh.qn.ensure((size_t)nq * sizeof(float), sh.device);
-            launch_row_norms(xq, nq, d, sh.qn.get<float>(), st);
-            qn = sh.qn.get<float>();
-        }
-        sh.qscale.ensure(sizeof(float) * (size_t)nq, sh.device);
-        sh.qres.ensure(sizeof(float) * (size_t)nq, sh.device);
-        sh.qimg.ensure((size_t)nq * flat_i8_nk(d) * 4 * 16, sh.device);
-        sh.part_d.ensure((size_t)nw * nq * kf * sizeof(float), sh.device);
-        sh.part_i.ensure((size_t)nw * nq * kf * sizeof(int), sh.device);
-        sh.mid_d.ensure((size_t)G * nq * kf * sizeof(float), sh.device);
-        sh.mid_i.ensure((size_t)G * nq * kf * sizeof(long long), sh.device);
+    if (m.record) ix.last_form = m.last_form, ix.last_kfilt = m.last_kfilt, ix.last_sublists = 0;
+    FlatCandRun run;
+    if (m.path == kFlatPathKeys) {
+        const float *qn = m.need_qn ? flat_query_norms(sh, nq, xq, c.d, st) : nullptr;
+        return flat_shard_search_bigk(ix, sh, nq, xq, qn, k, kout, D, I, st);
+    } else if (m.path == kFlatPathDirect) {
+        return flat_direct_scan(c);
+    } else if (m.path == kFlatPathSmallI8) {
+        flat_small_i8(c);
+    } else {
+        flat_bound_terms(c);  // (host synchronisations at their first use; before ‖q‖², as ever)
+        if (m.need_qn) c.qn = flat_query_norms(sh, nq, xq, c.d, st, m.prep_qn ? &c.qn_owed : nullptr);
+        if (m.form == kFlatBf16Exact) ensure_b16_image(ix, sh, c.d, st);
+        flat_lists_scratch(c);
         {
             ScopedTiming t(ix.timer_main, st);
-            launch_flat_i8_scan(xq, nq, d, metric, sh.xi8.p, sh.xscale.get<float>(), sh.xn.get<float>(), sh.n,
-                                sh.qscale.get<float>(), sh.qres.get<float>(), qn, sh.qimg.p, sh.part_d.get<float>(),
-                                sh.part_i.get<int>(), nw, st);
+            run = m.bounded ? flat_bounded_passes(c) : m.image() ? flat_bf16_lists(c) : flat_gemm_lists(c);
         }
-        sh.nflag.ensure(sizeof(int), sh.device);
-        sh.flagged.ensure(sizeof(int) * (size_t)nq, sh.device);
-        HIPANN_CHECK(hipMemsetAsync(sh.nflag.p, 0, sizeof(int), st));
-        {
-            ScopedTiming t(ix.timer_merge, st);
-            float *md = sh.mid_d.get<float>();
-            int *mi = reinterpret_cast<int *>(sh.mid_i.p);
-            launch_flat_i8_group_merge(sh.part_d.get<float>(), sh.part_i.get<int>(), (int)nw, (int)nq, G, md, mi, st);
-            IvfRerankArgs a = flat_rerank_args(sh, nq, kout, metric, xq, d, xmax2, D, I);
-            a.pd = md, a.pi = mi, a.nprobe = G, a.k = kf, a.rxmax = sh.i8_rxmax, a.qres = sh.qres.get<float>();
-            launch_ivf_rerank(a, st);
-        }
-        if (form_override < 0) {
-            ix.last_form = kFlatI8Exact;
-            ix.last_kfilt = kf;
-            ix.last_sublists = 0;
-        }
-        // the flagged count goes to the host with the results; the uncertified queries re-run on the fp32 direct
-        // scan in flat_shard_finish
-        pend = FlatPending{};
-        pend.kind = FlatPending::kSmallI8;
-        pend.nq = nq;
-        pend.xq = xq;
-        pend.k = k;
-        pend.kout = kout;
-        pend.D = D;
-        pend.I = I;
-        flag_readback(sh, st);
-        return;
+        if (!m.exact) return flat_merge_lists(c, run);
+        flat_rerank(c, run);
     }
-    if (nq < kBlasThreshold) {
-        if (form_override < 0) {
-            ix.last_form = kFlatFp32;  // the direct form
-            ix.last_kfilt = 0;
-            ix.last_sublists = 0;
-        }
-        // direct form (fvec_L2sqr / fvec_inner_product)
-        // ≥ 512 rows per wave on large tables; small ones (the IVF coarse quantizer's 1024 centroids at
-        // nq = 1) are spread over waves of ≥ 16 rows (2 waves of 512 rows took 234 us for 1024 × 768)
-        int64_t nwaves = std::min<int64_t>(8192, std::max<int64_t>(std::min<int64_t>(256, ceil_div(sh.n, 16)),
-                                                                   ceil_div(sh.n, 512)));
-        const int64_t rpw = ceil_div(sh.n, nwaves);
-        nwaves = ceil_div(sh.n, rpw);
-        const int64_t nw_alloc = ceil_div(nwaves, 4) * 4;
-        // the scan holds its queries in ≤ 64 KiB of LDS: larger d·nq runs as several query chunks (d = 1536 fits 10
-        // queries; one query up to d = 16384)
-        int qc = (int)nq;
-        while (qc > 1 && scan_smem_bytes(qc, d) > 64 * 1024) --qc;
-        HIPANN_REQUIRE(scan_smem_bytes(qc, d) <= 64 * 1024, "dimension too large for the scan path");
-        sh.part_d.ensure((size_t)nw_alloc * qc * k * sizeof(float), sh.device);
-        sh.part_i.ensure((size_t)nw_alloc * qc * k * sizeof(int), sh.device);
-        const int groups = (int)std::min<int64_t>(256, ceil_div(nw_alloc, 32));
-        if (nw_alloc > 256) {
-            sh.mid_d.ensure(sizeof(float) * (size_t)groups * qc * kout, sh.device);
-            sh.mid_i.ensure(sizeof(long long) * (size_t)groups * qc * kout, sh.device);
-        }
-        for (int64_t q0 = 0; q0 < nq; q0 += qc) {
-            const int64_t nc = std::min<int64_t>(qc, nq - q0);
-            {
-                ScopedTiming t(ix.timer_main, st);
-                launch_flat_scan_topk(xq + q0 * d, (int)nc, sh.xb, sh.n, d, metric, k, (int)nw_alloc, rpw,
-                                      sh.part_d.get<float>(), sh.part_i.get<int>(), st);
-            }
-            ScopedTiming t(ix.timer_merge, st);
-            if (nw_alloc > 256) {
-                // thousands of per-wave lists: groups of ~32 merged by one wave each, then the group lists by one
-                // 4-wave block per query (one wave per query took ~1 ms for 8192 lists at 10M rows, nq = 1)
-                launch_merge_parts_2level<int>(sh.part_d.get<float>(), sh.part_i.get<int>(), (int)nw_alloc, nc, k, kout,
-                                               sh.label_offset, 1.f, out_sign, D + q0 * kout, I + q0 * kout,
-                                               sh.mid_d.get<float>(), sh.mid_i.get<long long>(), groups, st);
-            } else {
-                launch_merge_parts<int>(sh.part_d.get<float>(), sh.part_i.get<int>(), (int)nw_alloc, nc, k, kout,
-                                        sh.label_offset, 1.f, out_sign, D + q0 * kout, I + q0 * kout, st);
-            }
-        }
-        return;
-    }
-    // BLAS form: ‖q‖² + ‖x‖² − 2 q·x on fp32 MFMA.  ‖q‖² is launched by qn_now() ahead of its first reader (the int8
-    // bounded passes compute it inside their query preparation instead, the same bits)
-    const float *qn = nullptr;
-    bool qn_launch = false;
-    if (metric == kL2) {
-        if (!(sh.qn_given == xq && sh.qn_given_nq == nq)) {
-            sh.qn.ensure((size_t)nq * sizeof(float), sh.device);
-            qn_launch = true;
-        }
-        qn = sh.qn.get<float>();
-        sh.qn_of = xq;
-        sh.qn_nq = nq;
-    }
-    auto qn_now = [&]() {
-        if (qn_launch) launch_row_norms(xq, nq, d, sh.qn.get<float>(), st);
-        qn_launch = false;
-    };
-    int form = form_override >= 0 ? form_override : ix.form;
-    static const bool seed_env = [] { const char *e = std::getenv("HIPANN_FLAT_BF16_SEED"); return !e || std::atoi(e); }();
-    // The exact forms keep kf candidates per query (per split and query on the list kernels) as the filter; the
-    // rerank returns kout.  kout ≤ kRerankMaxK: kf = 32 (the bf16 image: at 10M × 768 the 10th and 16th distances
-    // are ≈2 apart, inside its rounding bound ≈1.3, the 10th and 32nd ≈5; the split scan: IP 32, L2 16).  Larger
-    // kout (request_k = k + |tombstones|, faiss_index.cpp:713-715): kf = min(64, max(base, 2·kout)).  The list
-    // kernels hold kf in LDS (capped by their launchers' LDS budget) and need kf ≥ kout + 4 of margin; the bounded
-    // passes take any kout ≤ kf ≤ 64 — a query whose kout-th distance is within the bound of the kf-th key goes to
-    // the all-candidate rerank, certified against the pass bound.  Otherwise: the 3-term split (fp32-level).
-    int kf = 0;
-    bool bounded = false;
-    // kFlatI8Exact runs only as the bounded passes (256-query blocks, >= 512K rows, d <= 1024 so the int32 sums
-    // convert to fp32 exactly); elsewhere the bf16 image's paths
-    if (form == kFlatI8Exact &&
-        !(flat_bf16_resumable(nq, d, 64) && seed_env && sh.n >= 8 * 65536 && d <= 1024))
-        form = kFlatBf16Exact;
-    if (form == kFlatI8Exact) {
-        // the int8 rounding bound is ≈3× the bf16 one (E ≈ 4.4 against 1.3-1.7 at 768 dims on U(-1, 1)): a
-        // 64-deep filter keeps the 10th distance clear of it (the 10th-to-32nd gap is ≈5, the 10th-to-64th ≈8)
-        kf = 64;
-        bounded = true;
-    } else if (form == kFlatSplit2Exact || form == kFlatBf16Exact) {
-        const int base = metric == kIP || form == kFlatBf16Exact ? kFlatRerankKIP : kRerankK;
-        kf = kout <= kRerankMaxK ? base : std::min(64, std::max(base, 2 * kout));
-        if (form == kFlatBf16Exact) {
-            bounded = flat_bf16_resumable(nq, d, kf) && seed_env && sh.n >= 8 * 65536;
-            if (!bounded) kf = std::min(kf, flat_bf16_topk_kmax(nq));
-        } else {
-            kf = std::min(kf, flat_gemm_topk_bf_kmax(2));
-        }
-    }
-    const bool exact = kf > 0 && (kout <= kRerankMaxK || (bounded ? kout <= kf : kout + 4 <= kf));
-    if (kf > 0 && !exact) form = kFlatSplit3;
-    const int k_user = k;
-    if (exact) k = kf;
-    // the split scans' LDS lists hold fewer rows at 3 terms (k <= 38 at 8 waves): a longer list takes the fp32
-    // matrix cores (exact fp32 products, lists up to 64)
-    if ((form == kFlatSplit3 || form == kFlatSplit2) && k > flat_gemm_topk_bf_kmax(form == kFlatSplit3 ? 3 : 2))
-        form = kFlatFp32;
-    if (form_override < 0) {
-        ix.last_form = form;
-        ix.last_kfilt = exact ? kf : 0;
-        ix.last_sublists = 0;
-    }
-    int64_t nsplit;
-    bool flags_ready = false;  // the bounded passes' select already reset nflag and flagged overflows
-    // the bounded passes' candidate buffers and bound, for the flagged queries' second rerank
-    const float *cr_d = nullptr, *cr_bound = nullptr;
-    const int *cr_i = nullptr, *cr_n = nullptr;
-    int cr_nsplit = 0, cr_cap = 0;
-    // the exact forms' max ‖x‖² (cached; its first computation uses sh.nflag as scratch, so before any flags)
-    const float xmax2 = exact ? flat_xmax2(ix, sh, d, st) : 0.f;
-    const bool i8 = form == kFlatI8Exact;
-    float rxmax = sh.bf16_rxmax;  // the rerank bound's row term of the form that filtered
-    if (i8) {
-        // one int8 product per element (int32 sums) over a tiled int8 image with per-row scales, built once
-        ensure_i8_image(ix, sh, d, st);
-        rxmax = sh.i8_rxmax;
-    }
-    // HIPANN_I8_PREP_FUSED=0 (A/B): the int8 query preparation as row_norms + i8_row_scale + i8_tile_rows
-    static const bool prep_fused = [] { const char *e = std::getenv("HIPANN_I8_PREP_FUSED"); return !e || std::atoi(e); }();
-    const bool i8_prep = i8 && bounded && seed_env && sh.n >= 8 * 65536 && prep_fused;
-    if (!i8_prep) qn_now();
-    if (form == kFlatBf16Exact || i8) {
-        // one plain bf16 product per element over the tiled bf16 image (flat_bf16.hip), built once
-        if (!i8 && !sh.xb16_ok) {
-            sh.xb16.ensure(flat_bf16_img_bytes(sh.n, d, flat_bf16_tile_rows()), sh.device);
-            launch_b16_tile_rows(sh.xb, sh.n, d, flat_bf16_tile_rows(), sh.xb16.p, st);
-            // the rows' largest bf16 rounding residual ‖x̂ − x‖ (the rerank's bound)
-            sh.tmpnorm.ensure(sizeof(float) * (size_t)sh.n, sh.device);
-            launch_b16_row_residual2(sh.xb, sh.n, d, sh.tmpnorm.get<float>(), st);
-            sh.nflag.ensure(sizeof(int), sh.device);
-            launch_ivf_max_norm(sh.tmpnorm.get<float>(), sh.n, sh.nflag.get<unsigned>(), st);
-            unsigned bits = 0;
-            HIPANN_CHECK(hipMemcpyAsync(&bits, sh.nflag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-            HIPANN_CHECK(hipStreamSynchronize(st));  // later searches may run on other streams
-            ++ix.host_syncs;
-            sh.tmpnorm.release();
-            float r2;
-            std::memcpy(&r2, &bits, sizeof(r2));
-            sh.bf16_rxmax = std::sqrt(r2) * 1.0001f;
-            sh.xb16_ok = true;
-        }
-        const int W = flat_bf16_waves(nq);
-        const int64_t nqt = ceil_div(nq, 32 * W);
-        // the scan's operand images, chunk count and (int8) scales
-        const void *ximg = i8 ? sh.xi8.p : sh.xb16.p;
-        const int nk = i8 ? flat_i8_nk(d) : (int)ceil_div(d, 32);
-        const float *qsc = nullptr, *xsc = i8 ? sh.xscale.get<float>() : nullptr;
-        const int64_t ntiles = ceil_div(sh.n, flat_bf16_tile_rows());
-        static const int64_t blocks_env = [] {
-            const char *e = std::getenv("HIPANN_FLAT_BF16_BLOCKS");  // A/B: target grid size
-            return e ? (int64_t)std::atoll(e) : (int64_t)0;
-        }();
-        // one round of resident blocks (W = 8 / 4: one block per CU; W = 2: two) — fewer, longer splits admit
-        // fewer candidates into the per-split lists (≈ k·ln(rows / k) per list), the epilogue's slow path
-        nsplit = std::max<int64_t>(1, ceil_div(blocks_env > 0 ? blocks_env : (W == 2 ? 512 : 256), nqt));
-        nsplit = std::min<int64_t>(nsplit, ntiles);
-        const int64_t tps = ceil_div(ntiles, nsplit);
-        nsplit = ceil_div(ntiles, tps);
-        HIPANN_REQUIRE(nqt * nsplit < (int64_t)0x7fffffff, "grid too large");
-        sh.part_d.ensure((size_t)nsplit * nq * k * sizeof(float), sh.device);
-        sh.part_i.ensure((size_t)nsplit * nq * k * sizeof(int), sh.device);
-        sh.qimg.ensure(i8 ? flat_i8_img_bytes(nq, d, 32 * W) : flat_bf16_img_bytes(nq, d, 32 * W), sh.device);
-        // seed bound (large tables): the k-th best key of each query over a sample of the first rows.  Bounded
-        // passes (below): the sample's keys from the same kernel in its keys mode (a dense nq × S matrix, one
-        // tile per block) and their k-th order statistic (flat_keys_kth); otherwise the 32-dim list kernel over
-        // 64K rows and flat_bf16_seed (its lists start empty: every row an insert, ≈1 ms at 1024 queries — what
-        // the keys mode replaces).  The main passes then admit only keys ≤ that bound.
-        const bool seeded = seed_env && sh.n >= 8 * 65536;
-        static const int64_t pass_div = [] {
-            const char *e = std::getenv("HIPANN_FLAT_PASS_A");  // A/B: two passes, 1/x of each split in pass A
-            return e ? (int64_t)std::atoll(e) : (int64_t)-1;
-        }();
-        static const int64_t sample_env = [] {
-            const char *e = std::getenv("HIPANN_FLAT_SAMPLE");  // A/B: rows of the seed sample (multiple of 256)
-            return e ? (int64_t)std::atoll(e) : (int64_t)16384;
-        }();
-        const int64_t sample = std::max<int64_t>(256, std::min<int64_t>(sample_env / 256 * 256, flat_keys_kth_max()));
-        // the passes' tile boundaries within every split: pass p scans tiles [pb[p], pb[p+1]) under the bound
-        // from everything before it (the seed for pass 0)
-        const std::vector<int64_t> pb = pass_div >= 0
-            ? std::vector<int64_t>(pass_div > 1 && tps / pass_div >= 1 ? std::vector<int64_t>{0, tps / pass_div, tps}
-                                                                     : std::vector<int64_t>{0, tps})
-            : flat_pass_plan(tps, nsplit, flat_bf16_tile_rows(), sample, k, nq);
-        const int cap = flat_pass_cap(pb, nsplit, flat_bf16_tile_rows(), sample, k);
-        const size_t ncell = (size_t)nq * nsplit;
-        // the keys-mode seed pass runs per chunk of 1024 queries (4 query tiles) through one 64 MB slab of keys
-        const int64_t seed_qc = 1024;
-        ScopedTiming t(ix.timer_main, st);
-        if (seeded && bounded) {
-            sh.seed.ensure(sizeof(float) * (size_t)nq, sh.device);
-            sh.cand.ensure(std::max(ncell * ((size_t)cap * 8 + 4), (size_t)std::min(nq, seed_qc) * sample * sizeof(float)),
-                           sh.device);
-            if (i8) {  // the queries' scales, residuals (the rerank's query term) and int8 image
-                sh.qscale.ensure(sizeof(float) * (size_t)nq, sh.device);
-                sh.qres.ensure(sizeof(float) * (size_t)nq, sh.device);
-                if (i8_prep) {
-                    launch_i8_query_prep(xq, nq, d, qn_launch ? sh.qn.get<float>() : nullptr, sh.qscale.get<float>(),
-                                         sh.qres.get<float>(), 32 * W, sh.qimg.p, st);
-                    qn_launch = false;
-                } else {
-                    launch_i8_row_scale(xq, nq, d, sh.qscale.get<float>(), sh.qres.get<float>(), st);
-                    launch_i8_tile_rows(xq, sh.qscale.get<float>(), nq, d, 32 * W, sh.qimg.p, st);
-                }
-                qsc = sh.qscale.get<float>();
-            } else {
-                launch_b16_tile_rows(xq, nq, d, 32 * W, sh.qimg.p, st);
-            }
-            const size_t qtile_bytes = i8 ? flat_i8_img_bytes(32 * W, d, 32 * W) : flat_bf16_img_bytes(32 * W, d, 32 * W);
-            for (int64_t c0 = 0; c0 < nq; c0 += seed_qc) {
-                const int64_t cn = std::min(seed_qc, nq - c0);
-                launch_flat_bf16_k64(static_cast<const char *>(sh.qimg.p) + (size_t)(c0 / (32 * W)) * qtile_bytes,
-                                     qn ? qn + c0 : nullptr, cn, ximg, sh.xn.get<float>(), sample, nk, metric,
-                                     (int)ceil_div(cn, 32 * W), (int)(sample / flat_bf16_tile_rows()), 1, 0, 1, nullptr,
-                                     sh.cand.get<float>(), nullptr, nullptr, 0, false, true, st, qsc ? qsc + c0 : nullptr,
-                                     xsc);
-                launch_flat_keys_kth(sh.cand.get<float>(), (int)sample, cn, k, sh.seed.get<float>() + c0, st);
-            }
-        } else if (seeded) {
-            const int64_t seed_rows = 65536;
-            const int64_t stiles = seed_rows / flat_bf16_tile_rows();
-            const int64_t snsplit = std::min<int64_t>(stiles, std::max<int64_t>(1, ceil_div(256, nqt)));
-            const int64_t stps = ceil_div(stiles, snsplit);
-            sh.seed.ensure(sizeof(float) * ((size_t)snsplit * nq * k * 2 + (size_t)nq), sh.device);
-            float *spd = sh.seed.get<float>() + nq;
-            int *spi = reinterpret_cast<int *>(spd + (size_t)snsplit * nq * k);
-            launch_flat_bf16_topk(xq, qn, nq, sh.qimg.p, sh.xb16.p, sh.xn.get<float>(), seed_rows, d, metric, k,
-                                  (int)ceil_div(stiles, stps), stps, spd, spi, nullptr, false, st);
-            launch_flat_bf16_seed(spd, (int)ceil_div(stiles, stps), nq, k, sh.seed.get<float>(), st);
-        }
-        // bounded passes (64-dim K-step kernel, flat_b16k64.hip): every row with key ≤ the bound goes to a
-        // per-(query, split) candidate buffer.  Pass 0 covers the first tiles of every split under the 16K-row
-        // seed bound; after each pass the bound is re-merged from all candidates so far (the k-th best key over
-        // every row scanned) and the next pass continues (flat_pass_plan: at 10M rows 4 passes over 5 / 20 / 98 /
-        // 488 tiles per split, ≈ 8.5 candidates per query and split), no row scanned twice.  flat_cand_select keeps
-        // each query's k best for the rerank.
-        if (seeded && bounded) {
-            static const bool dbg = std::getenv("HIPANN_FLAT_CAND_DEBUG") != nullptr;
-            float *cd = sh.cand.get<float>();
-            int *ci = reinterpret_cast<int *>(cd + ncell * cap);
-            int *cn = ci + ncell * cap;
-            float *bound = sh.seed.get<float>();
-            for (size_t p = 0; p + 1 < pb.size(); ++p) {
-                launch_flat_bf16_k64(sh.qimg.p, qn, nq, ximg, sh.xn.get<float>(), sh.n, nk, metric, (int)nqt,
-                                     (int)nsplit, tps, pb[p], pb[p + 1], bound, cd, ci, cn, cap, p > 0, false, st, qsc,
-                                     xsc);
-                if (p + 2 < pb.size()) launch_flat_cand_bound(cd, cn, (int)nsplit, cap, nq, k, bound, st);
-            }
-            sh.nflag.ensure(sizeof(int), sh.device);
-            sh.flagged.ensure(sizeof(int) * (size_t)nq, sh.device);
-            HIPANN_CHECK(hipMemsetAsync(sh.nflag.p, 0, sizeof(int), st));
-            // overflowed queries are flagged here, ahead of the rerank's own flags (the fallback re-runs both)
-            launch_flat_cand_select(cd, ci, cn, (int)nsplit, cap, nq, k, sh.part_d.get<float>(), sh.part_i.get<int>(),
-                                    sh.nflag.get<int>(), sh.flagged.get<int>(), st);
-            if (dbg) {
-                std::vector<int> hn(ncell);
-                std::vector<float> hb((size_t)nq);
-                HIPANN_CHECK(hipMemcpyAsync(hn.data(), cn, sizeof(int) * ncell, hipMemcpyDeviceToHost, st));
-                HIPANN_CHECK(hipMemcpyAsync(hb.data(), bound, sizeof(float) * nq, hipMemcpyDeviceToHost, st));
-                HIPANN_CHECK(hipStreamSynchronize(st));
-                long long tot = 0;
-                int mx = 0;
-                for (int v : hn) { tot += v; mx = std::max(mx, v); }
-                std::fprintf(stderr, "hipann flat cand: nsplit %lld tps %lld passes %zu pass0 %lld cap %d mean %.2f max %d bound[0] %g\n",
-                             (long long)nsplit, (long long)tps, pb.size() - 1, (long long)pb[1], cap, (double)tot / (double)ncell, mx,
-                             (double)hb[0]);
-            }
-            cr_d = cd;
-            cr_i = ci;
-            cr_n = cn;
-            cr_nsplit = (int)nsplit;
-            cr_cap = cap;
-            cr_bound = bound;
-            nsplit = 1;
-            flags_ready = true;
-        } else {
-            launch_flat_bf16_topk(xq, qn, nq, sh.qimg.p, sh.xb16.p, sh.xn.get<float>(), sh.n, d, metric, k,
-                                  (int)nsplit, tps, sh.part_d.get<float>(), sh.part_i.get<int>(),
-                                  seeded ? sh.seed.get<float>() : nullptr, seeded, st);
-        }
-    } else {
-        const int64_t nqt = ceil_div(nq, 128);
-        const int64_t ntiles = ceil_div(sh.n, 128);
-        // ≈2048 blocks; small tables (an IVF coarse quantizer: 1024 centroids = 8 tiles) go down to one
-        // column tile per block rather than leaving CUs idle
-        nsplit = std::max<int64_t>(1, ceil_div(2048, nqt));
-        nsplit = std::min<int64_t>(nsplit, ntiles);
-        if (nsplit >= 8) nsplit = nsplit / 8 * 8;
-        const int64_t tps = ceil_div(ntiles, nsplit);
-        nsplit = ceil_div(ntiles, tps);
-        HIPANN_REQUIRE(nqt * nsplit < (int64_t)0x7fffffff, "grid too large");
-        sh.part_d.ensure((size_t)nsplit * nq * k * sizeof(float), sh.device);
-        sh.part_i.ensure((size_t)nsplit * nq * k * sizeof(int), sh.device);
-        ScopedTiming t(ix.timer_main, st);
-        if (form == kFlatFp32) {
-            launch_flat_gemm_topk(xq, qn, nq, sh.xb, sh.xn.get<float>(), sh.n, d, metric, k, (int)nsplit, tps,
-                                  sh.part_d.get<float>(), sh.part_i.get<int>(), st);
-        } else {
-            const int np = form == kFlatSplit3 ? 3 : 2;
-            sh.qsplit.ensure(flat_bf_qsplit_bytes(nq, d, np), sh.device);
-            launch_flat_gemm_topk_bf(np, xq, qn, nq, sh.qsplit.get<void>(), sh.xb, sh.xn.get<float>(), sh.n, d, metric,
-                                     k, (int)nsplit, tps, sh.part_d.get<float>(), sh.part_i.get<int>(), exact ? 1 : 0,
-                                     st);
-        }
-    }
-    if (!exact) {
-        ScopedTiming t(ix.timer_merge, st);
-        launch_merge_parts<int>(sh.part_d.get<float>(), sh.part_i.get<int>(), (int)nsplit, nq, k, kout, sh.label_offset,
-                                1.f, out_sign, D, I, st);
-        return;
-    }
-    // exact form: merge each query's nsplit lists to the 16 best scan keys, recompute those rows in the
-    // direct form, bound-check (ivf_rerank_topk, slot lists query-major); flagged queries re-run on split3
-    if (!flags_ready) {
-        sh.nflag.ensure(sizeof(int), sh.device);
-        sh.flagged.ensure(sizeof(int) * (size_t)nq, sh.device);
-        HIPANN_CHECK(hipMemsetAsync(sh.nflag.p, 0, sizeof(int), st));
-    }
-    {
-        ScopedTiming t(ix.timer_merge, st);
-        // (int8: the row term and each query's own residual from the int8 images; qres makes the rerank read them)
-        IvfRerankArgs a = flat_rerank_args(sh, nq, kout, metric, xq, d, xmax2, D, I);
-        a.pd = sh.part_d.get<float>(), a.pi = sh.part_i.get<int>(), a.nprobe = (int)nsplit, a.k = k;
-        a.rxmax = form == kFlatBf16Exact || i8 ? rxmax : -1.f, a.qres = i8 ? sh.qres.get<float>() : nullptr;
-        launch_ivf_rerank(a, st);
-    }
-    pend = FlatPending{};
-    pend.kind = FlatPending::kExact;
-    pend.nq = nq;
-    pend.xq = xq;
-    pend.k = k_user;
-    pend.kout = kout;
-    pend.D = D;
-    pend.I = I;
-    pend.cr_d = cr_d;
-    pend.cr_bound = cr_bound;
-    pend.cr_i = cr_i;
-    pend.cr_n = cr_n;
-    pend.cr_nsplit = cr_nsplit;
-    pend.cr_cap = cr_cap;
-    pend.xmax2 = xmax2;
-    pend.rxmax = rxmax;
-    pend.i8 = i8;
+    // the flagged count goes to the host with the results; flat_shard_finish re-runs what was not certified
+    pend = flat_pending(c, run);
     flag_readback(sh, st);
 }
 
 // The second half of a shard search, once the host has synchronised with the launch phase's stream (its flag
 // count read back into sh.h_nflag): nothing to do unless the exact form's bound check flagged queries.  Flagged
-// queries are rare (0 on every benchmark batch); their re-runs are synchronous.
+// queries are rare (0 on every benchmark batch); their re-runs are synchronous, on the form pend names (the fp32
+// direct scan after the small-batch int8 scan, the 3-term split after the batched exact forms).
 void flat_shard_finish(FlatIndex &ix, FlatShard &sh, const FlatPending &pend, hipStream_t st) {
     if (pend.kind == FlatPending::kNone) return;
     int nf = *sh.h_nflag.get<int>();
     if (nf <= 0) return;
     DeviceGuard g(sh.device);
-    const int d = ix.d, metric = ix.metric;
-    const int kout = pend.kout;
-    const float *xq = pend.xq;
-    float *D = pend.D;
-    int64_t *I = pend.I;
+    const int d = ix.d, kout = pend.kout;
     int *fl = sh.flagged.get<int>();
-    int rerun_form = kFlatSplit3;
-    if (pend.kind == FlatPending::kSmallI8) {
-        rerun_form = kFlatFp32;
-    } else if (pend.cr_d) {
-        const float *cr_d = pend.cr_d, *cr_bound = pend.cr_bound;
-        const int *cr_i = pend.cr_i, *cr_n = pend.cr_n;
-        const int cr_nsplit = pend.cr_nsplit, cr_cap = pend.cr_cap;
-        const float xmax2 = pend.xmax2, rxmax = pend.rxmax;
-        const bool i8 = pend.i8;
+    if (pend.cr_d) {
         // bounded passes: rerank each flagged query over all its buffered candidates, certified against the pass
-        // bound (launch_flat_cand_rerank); only what that cannot certify re-runs on SPLIT3
-        const int P = flat_cand_rerank_parts(cr_nsplit);
+        // bound (launch_flat_cand_rerank); only what that cannot certify re-runs
+        const bool dbg = flat_tuning().cand_debug;
+        const int P = flat_cand_rerank_parts(pend.cr_nsplit);
         sh.crd.ensure(sizeof(float) * (size_t)nf * P * kout, sh.device);
         sh.cri.ensure(sizeof(long long) * (size_t)nf * P * kout, sh.device);
         sh.covf.ensure(sizeof(int) * (size_t)nf * P, sh.device);
         sh.nflag2.ensure(sizeof(int), sh.device);
         sh.flagged2.ensure(sizeof(int) * (size_t)nf, sh.device);
         HIPANN_CHECK(hipMemsetAsync(sh.nflag2.p, 0, sizeof(int), st));
-        static const bool dbg = std::getenv("HIPANN_FLAT_CAND_DEBUG") != nullptr;
         if (dbg) sh.tmpnorm.ensure(sizeof(float) * 4 * (size_t)nf, sh.device);
+        FlatCandRerankArgs a;
+        a.flagged = fl, a.nf = nf;
+        a.cand_d = pend.cr_d, a.cand_i = pend.cr_i, a.cand_n = pend.cr_n, a.nsplit = pend.cr_nsplit, a.cap = pend.cr_cap;
+        a.bound = pend.cr_bound, a.Q = pend.xq, a.X = sh.xb, a.d = d, a.nrows = sh.n, a.label_offset = sh.label_offset;
+        a.xmax2 = pend.xmax2, a.rxmax = pend.rxmax, a.metric = ix.metric, a.kout = kout;
+        a.part_d = sh.crd.get<float>(), a.part_i = sh.cri.get<long long>(), a.ovf = sh.covf.get<int>();
+        a.D = pend.D, a.I = pend.I, a.nflag2 = sh.nflag2.get<int>(), a.flagged2 = sh.flagged2.get<int>();
+        a.dbg = dbg ? sh.tmpnorm.get<float>() : nullptr, a.qres = pend.i8 ? sh.qres.get<float>() : nullptr;
         {
             ScopedTiming t(ix.timer_merge, st);
-            launch_flat_cand_rerank(fl, nf, cr_d, cr_i, cr_n, cr_nsplit, cr_cap, cr_bound, xq, sh.xb, d, sh.n,
-                                    sh.label_offset, xmax2, rxmax, metric, kout, sh.crd.get<float>(),
-                                    sh.cri.get<long long>(), sh.covf.get<int>(), D, I, sh.nflag2.get<int>(),
-                                    sh.flagged2.get<int>(), st, dbg ? sh.tmpnorm.get<float>() : nullptr,
-                                    i8 ? sh.qres.get<float>() : nullptr);
+            launch_flat_cand_rerank(a, st);
         }
         ix.cand_reranked += nf;
         const int nf1 = nf;
@@ -1026,13 +1144,13 @@ void flat_shard_finish(FlatIndex &ix, FlatShard &sh, const FlatPending &pend, hi
     sh.fq.ensure(sizeof(float) * (size_t)nf * d, sh.device);
     sh.fD.ensure(sizeof(float) * (size_t)nf * kout, sh.device);
     sh.fI.ensure(sizeof(int64_t) * (size_t)nf * kout, sh.device);
-    launch_ivf_gather_queries(xq, fl, nf, d, sh.fq.get<float>(), st);
+    launch_ivf_gather_queries(pend.xq, fl, nf, d, sh.fq.get<float>(), st);
     {
         TimerPause p0(ix.timer_main), p1(ix.timer_merge);
         flat_shard_search(ix, sh, nf, sh.fq.get<float>(), pend.k, kout, sh.fD.get<float>(), sh.fI.get<int64_t>(), st,
-                          rerun_form);
+                          pend.rerun_form);
     }
-    launch_ivf_scatter_results(sh.fD.get<float>(), sh.fI.get<int64_t>(), fl, nf, kout, D, I, st);
+    launch_ivf_scatter_results(sh.fD.get<float>(), sh.fI.get<int64_t>(), fl, nf, kout, pend.D, pend.I, st);
 }
 
 void flat_shard_search(FlatIndex &ix, FlatShard &sh, int64_t nq, const float *xq, int k, int kout, float *D,
@@ -1512,7 +1630,8 @@ extern "C" int hipann_debug_flat_pass_plan(int64_t tps, int64_t nsplit, int64_t 
                                            int64_t *bounds, int *nb, int *cap) {
     try {
         if (tps < 1 || nsplit < 1 || sample < 256 || k < 1 || nq < 1 || !bounds || !nb || !cap) return -1;
-        const std::vector<int64_t> pb = hipann::flat_pass_plan(tps, nsplit, hipann::flat_bf16_tile_rows(), sample, k, nq);
+        const std::vector<int64_t> pb = hipann::flat_pass_plan(tps, nsplit, hipann::flat_bf16_tile_rows(), sample, k, nq,
+                                                               hipann::flat_tuning().passes);
         if (pb.size() < 2 || pb.size() > 7) return -1;
         for (size_t i = 0; i < pb.size(); ++i) bounds[i] = pb[i];
         *nb = (int)pb.size();
@@ -1521,4 +1640,25 @@ extern "C" int hipann_debug_flat_pass_plan(int64_t tps, int64_t nsplit, int64_t 
     } catch (...) {
         return -1;
     }
+}
+
+// test hook (tests/test_flat_scan_mode.py): the mode of a shard search as flat_shard_launch resolves it, with no
+// device.  in[0..12): nq, n (the shard's rows), d, metric, k, kout, the requested form, is_override, then the switches
+// the decision reads: HIPANN_FLAT_I8_SMALL, HIPANN_FLAT_BF16_SEED, HIPANN_I8_PREP_FUSED, HIPANN_B16_K64 (0 / 1).
+// out[0..16): path (FlatPath), form, record, last_form, last_kfilt, exact, bounded, seeded, i8, i8_prep, kscan,
+// k_user, pending kind, re-run form, need_qn, prep_qn.  0, or -1 on short arrays or a value out of range.
+extern "C" int hipann_debug_flat_scan_mode(const int *in, int nin, int *out, int nout) {
+    using namespace hipann;
+    if (!in || !out || nin < 12 || nout < 16 || in[0] < 0 || in[1] < 0 || in[2] < 1 || in[4] < 1 || in[5] < 1) return -1;
+    if ((in[3] != kL2 && in[3] != kIP) || in[6] < kFlatFp32 || in[6] > kFlatI8Exact) return -1;
+    FlatModeIn mi;
+    mi.nq = in[0], mi.n = in[1], mi.d = in[2], mi.metric = in[3], mi.k = in[4], mi.kout = in[5];
+    mi.form = in[6], mi.is_override = in[7] != 0;
+    mi.tune.i8_small = in[8] != 0, mi.tune.seed = in[9] != 0, mi.tune.i8_prep_fused = in[10] != 0;
+    mi.tune.b16_k64 = in[11] != 0;
+    const FlatScanMode m = flat_resolve_mode(mi);
+    const int o[16] = {m.path, m.form, m.record, m.last_form, m.last_kfilt, m.exact, m.bounded, m.seeded,
+                       m.i8, m.i8_prep, m.kscan, m.k_user, m.pend_kind, m.rerun_form, m.need_qn, m.prep_qn};
+    std::copy(o, o + 16, out);
+    return 0;
 }

@@ -2468,26 +2468,19 @@ flat_cand_rerank_final(const int *__restrict__ flagged, int P, const float *__re
     }
 }
 
-void launch_flat_cand_rerank(const int *flagged, int nf, const float *cand_d, const int *cand_i, const int *cand_n,
-                             int nsplit, int cap, const float *bound, const float *Q, const float *X, int d,
-                             int64_t nrows, int64_t label_offset, float xmax2, float rxmax, int metric, int kout,
-                             float *part_d, long long *part_i, int *ovf, float *D, int64_t *I, int *nflag2,
-                             int *flagged2, hipStream_t st, float *dbg, const float *qres) {
-    if (nf <= 0) return;
-    HIPANN_REQUIRE(kout >= 1 && kout <= 64 && nsplit >= 1 && cap >= 1, "flat cand rerank: bad arguments");
-    const int P = std::min(kCandRerankParts, nsplit);
-    dim3 g1((unsigned)nf, (unsigned)P);
-    if (metric == kIP) {
-        hipLaunchKernelGGL(flat_cand_rerank_part<true>, g1, dim3(256), 0, st, flagged, cand_d, cand_i, cand_n, nsplit,
-                           cap, Q, X, d, nrows, label_offset, kout, part_d, part_i, ovf);
-        hipLaunchKernelGGL(flat_cand_rerank_final<true>, dim3((unsigned)nf), dim3(64), 0, st, flagged, P, bound, Q, d,
-                           xmax2, rxmax, kout, part_d, part_i, ovf, D, I, nflag2, flagged2, dbg, qres);
-    } else {
-        hipLaunchKernelGGL(flat_cand_rerank_part<false>, g1, dim3(256), 0, st, flagged, cand_d, cand_i, cand_n, nsplit,
-                           cap, Q, X, d, nrows, label_offset, kout, part_d, part_i, ovf);
-        hipLaunchKernelGGL(flat_cand_rerank_final<false>, dim3((unsigned)nf), dim3(64), 0, st, flagged, P, bound, Q, d,
-                           xmax2, rxmax, kout, part_d, part_i, ovf, D, I, nflag2, flagged2, dbg, qres);
-    }
+void launch_flat_cand_rerank(const FlatCandRerankArgs &a, hipStream_t st) {
+    if (a.nf <= 0) return;
+    HIPANN_REQUIRE(a.kout >= 1 && a.kout <= 64 && a.nsplit >= 1 && a.cap >= 1, "flat cand rerank: bad arguments");
+    const int P = std::min(kCandRerankParts, a.nsplit);
+    dim3 g1((unsigned)a.nf, (unsigned)P);
+    auto go = [&](auto part, auto final) {
+        hipLaunchKernelGGL(part, g1, dim3(256), 0, st, a.flagged, a.cand_d, a.cand_i, a.cand_n, a.nsplit, a.cap, a.Q,
+                           a.X, a.d, a.nrows, a.label_offset, a.kout, a.part_d, a.part_i, a.ovf);
+        hipLaunchKernelGGL(final, dim3((unsigned)a.nf), dim3(64), 0, st, a.flagged, P, a.bound, a.Q, a.d, a.xmax2,
+                           a.rxmax, a.kout, a.part_d, a.part_i, a.ovf, a.D, a.I, a.nflag2, a.flagged2, a.dbg, a.qres);
+    };
+    if (a.metric == kIP) go(flat_cand_rerank_part<true>, flat_cand_rerank_final<true>);
+    else go(flat_cand_rerank_part<false>, flat_cand_rerank_final<false>);
     HIPANN_CHECK(hipGetLastError());
 }
 

@@ -320,6 +320,7 @@ struct FlatPending {
     int64_t nq = 0;
     const float *xq = nullptr;
     int k = 0, kout = 0;  // k of the re-run (k_user on the batched exact forms), output width
+    int rerun_form = kFlatSplit3;  // the form the flagged queries re-run on (FlatForm)
     float *D = nullptr;
     int64_t *I = nullptr;
     // kExact over the bounded passes: the candidate buffers and pass bound for the all-candidate rerank
@@ -554,11 +555,30 @@ int64_t ivf_mfma_bf_qsplit_bytes(int64_t nq, int d, int np);
 // Form 4 (bounded passes): the flagged queries' exact top-kout over ALL their buffered candidates, certified
 // against the pass bound (every unbuffered row has scan key > bound[q]); queries it cannot certify (a cell
 // overflowed, or the k-th distance within the error bound of bound[q]) are appended to flagged2.
-void launch_flat_cand_rerank(const int *flagged, int nf, const float *cand_d, const int *cand_i, const int *cand_n,
-                             int nsplit, int cap, const float *bound, const float *Q, const float *X, int d,
-                             int64_t nrows, int64_t label_offset, float xmax2, float rxmax, int metric, int kout,
-                             float *part_d, long long *part_i, int *ovf, float *D, int64_t *I, int *nflag2,
-                             int *flagged2, hipStream_t st, float *dbg = nullptr, const float *qres = nullptr);
+struct FlatCandRerankArgs {
+    const int *flagged = nullptr;  // the nf flagged queries
+    int nf = 0;
+    // the passes' candidate buffers (nsplit cells of cap entries per query), their counts and the pass bound
+    const float *cand_d = nullptr;
+    const int *cand_i = nullptr, *cand_n = nullptr;
+    int nsplit = 0, cap = 0;
+    const float *bound = nullptr;
+    const float *Q = nullptr, *X = nullptr;
+    int d = 0;
+    int64_t nrows = 0, label_offset = 0;
+    float xmax2 = 0.f, rxmax = 0.f;
+    int metric = kL2, kout = 0;
+    // scratch: flat_cand_rerank_parts(nsplit) partial lists of kout per flagged query, their overflow marks
+    float *part_d = nullptr;
+    long long *part_i = nullptr;
+    int *ovf = nullptr;
+    float *D = nullptr;
+    int64_t *I = nullptr;
+    int *nflag2 = nullptr, *flagged2 = nullptr;
+    float *dbg = nullptr;         // HIPANN_FLAT_CAND_DEBUG: 4 floats per flagged query
+    const float *qres = nullptr;  // the int8 image: the queries' residuals
+};
+void launch_flat_cand_rerank(const FlatCandRerankArgs &a, hipStream_t st);
 int flat_cand_rerank_parts(int nsplit);
 // launch_ivf_rerank's arguments: the scan's lists (pd / pi: nprobe slots of kslot entries per query, or slot_off's
 // slots), the filter depth k, the rows and the outputs; then what only some callers set.
@@ -674,12 +694,31 @@ void launch_flat_bf16_topk(const float *Q, const float *qn, int64_t nq, void *qi
                            int64_t N, int d, int metric, int k, int nsplit, int64_t tiles_per_split, float *pd, int *pi,
                            const float *seed, bool image_ready, hipStream_t st);
 // bounded passes of the 64-dim K-step kernel (flat_b16k64.hip): candidate buffers, their bound and select
-bool flat_bf16_resumable(int64_t nq, int d, int k);
-void launch_flat_bf16_k64(const void *qimg, const float *qn, int64_t nq, const void *ximg, const float *xn, int64_t N,
-                          int nk, int metric, int nqt, int nsplit, int64_t tiles_per_split, int64_t tile_begin,
-                          int64_t tile_end, const float *bound, float *cand_d, int *cand_i, int *cand_n, int cap,
-                          bool resume, bool keys, hipStream_t st, const float *qscale = nullptr,
-                          const float *xscale = nullptr);
+// (k64_on: the caller's HIPANN_B16_K64 switch)
+bool flat_bf16_resumable(int64_t nq, int d, int k, bool k64_on);
+// One launch of flat_bf16_k64: nqt query tiles × nsplit column splits, each block over tiles [tile_begin, tile_end) of
+// its split's tiles_per_split.  A pass appends the rows with key ≤ bound[q] to the (query, split) cells of cand_d /
+// cand_i (cap entries each, counts in cand_n; resume: the counts continue).  keys: cand_d is the dense nq × N key
+// matrix instead, and bound / cand_i / cand_n / cap stay unset.  qscale and xscale: the int8 images' scales (both or
+// neither).
+struct FlatK64Args {
+    const void *qimg = nullptr;  // the queries: image, ‖q‖² (L2), count
+    const float *qn = nullptr;
+    int64_t nq = 0;
+    const void *ximg = nullptr;  // the rows: image, ‖x‖² (L2), count
+    const float *xn = nullptr;
+    int64_t N = 0;
+    int nk = 0, metric = kL2;    // chunks per row of the images
+    int nqt = 0, nsplit = 1;
+    int64_t tiles_per_split = 0, tile_begin = 0, tile_end = 0;
+    const float *bound = nullptr;
+    float *cand_d = nullptr;
+    int *cand_i = nullptr, *cand_n = nullptr;
+    int cap = 0;
+    bool resume = false, keys = false;
+    const float *qscale = nullptr, *xscale = nullptr;
+};
+void launch_flat_bf16_k64(const FlatK64Args &a, hipStream_t st);
 // form kFlatI8Exact (flat_b16k64.hip): per-row int8 scale s = max|x|/127 and residual ‖x − s·x̂‖ (×1.0001) per row;
 // the tiled int8 image (64 dims per 64-B chunk row, chunk count rounded up to even, zero-filled); its bytes
 int flat_i8_nk(int d);
