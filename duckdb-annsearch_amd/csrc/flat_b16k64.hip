@@ -23,7 +23,6 @@
 #include "wave_topk.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
@@ -136,14 +135,7 @@ __device__ __forceinline__ void k64_epilogue_row(const k64_f32x4 (&sm)[NJ], floa
 // per byte moved.  The int32 sums are exact (|acc| <= d·127² < 2^24 for d <= 1040) and live in the float
 // accumulators' registers bit for bit until the tile's epilogue turns them into q·x = acc·s_q·s_x with the
 // per-query / per-row scales (qscale / xscale); everything after that is the bf16 path's.
-// STAG (A/B only, HIPANN_K64_STAGGER=1; measured slower, see launch_flat_bf16_k64) (the int8 bounded passes,
-// d ≥ 384): waves W/2..W−1 run half a K-step behind waves 0..W/2−1 — in K-step g's
-// barrier interval a late wave computes chunk 1 of g − 1, then (when g − 1 ended a tile) its epilogue, then chunk 0 of
-// g.  Waves w and w + W/2 share a SIMD, so one wave's epilogue (≈ 650 VALU instructions per tile) and LDS read burst
-// run beside its partner's MFMAs instead of both waves converting at the same barrier-aligned moment
-// (MI355X_MICROARCH.md, two waves per SIMD, item 9).  Same loads, same order, same counted waits, one extra barrier
-// interval at the end; the stage a late wave still reads (g − 1) is never the one refilled in interval g ((g + 3) mod 5).
-template <bool L2M, bool KEYS, bool I8 = false, int MBW = 2, bool STAG = false>
+template <bool L2M, bool KEYS, bool I8 = false, int MBW = 2>
 __global__ void __launch_bounds__(64 * K64Geom<MBW>::W, 1) __attribute__((amdgpu_waves_per_eu(1, 2)))
 flat_bf16_k64(const k64_u32x4 *__restrict__ Qt, const float *__restrict__ qnorm, int64_t nq,
               const k64_u32x4 *__restrict__ Xt, const float *xnorm, int64_t N, int nk, int nqt, int nsplit,
@@ -350,12 +342,11 @@ flat_bf16_k64(const k64_u32x4 *__restrict__ Qt, const float *__restrict__ qnorm,
         else __builtin_amdgcn_s_waitcnt(kWaitStep);
         stage = stage + 1 < NB ? stage + 1 : 0;
     };
-    // row blocks converted per epilogue part: 8 (32 values + 16 row terms beside the accumulators); STAG: 4, which frees
-    // the 16 registers the staggered halves' longer fragment lifetimes need
+    // row blocks converted per epilogue part: 8 (32 values + 16 row terms beside the accumulators)
 #ifndef HIPANN_K64_EJ
 #define HIPANN_K64_EJ 0
 #endif
-    constexpr int EJ = HIPANN_K64_EJ ? HIPANN_K64_EJ : (STAG ? 4 : 8);
+    constexpr int EJ = HIPANN_K64_EJ ? HIPANN_K64_EJ : 8;
     // the tile's epilogue (after its last K-step)
     auto epilogue = [&]() __attribute__((always_inline)) {
         const int64_t x0 = t * K64_TN;
@@ -449,119 +440,17 @@ flat_bf16_k64(const k64_u32x4 *__restrict__ Qt, const float *__restrict__ qnorm,
         ++t;
     };
 
-    // ---- STAG: the staggered schedule (see the template comment) ----
-    // Both halves run ONE instruction stream — the half only selects operands (a branch per half duplicated the
-    // accumulator updates and the allocator spilled ~1000 registers): per barrier interval g a chunk x, an epilogue
-    // site, a chunk y, an epilogue site.  Early half: x = chunk 0 of K-step g, y = chunk 1 of g, epilogue after y when
-    // g ends a tile.  Late half: x = chunk 1 of g − 1, epilogue after x when g − 1 ended a tile, y = chunk 0 of g.
-    // Both issue the query fragments two K-steps ahead (A(g + 2) spread over chunk y, into slot SLP — read by the late
-    // half's chunk x before) and the tile piece B(g + 3) at the end of y: the waits are the unstaggered schedule's.
-    auto chunk_rt = [&](int h, int stg, const k64_u32x4 (&a)[MBW], auto vm_c, int sli_dummy, int64_t gb, int stgb,
-                        auto sli_c) __attribute__((always_inline)) {
-        constexpr int VM = decltype(vm_c)::value, SLI = decltype(sli_c)::value;
-        (void)sli_dummy;
-        __builtin_amdgcn_sched_barrier(0);
-        const k64_u32x4 *Bc = smem_k64 + stg * K64_SU + h * K64_BU + g4 * K64_TN + (m16 ^ (g4 << 1));
-        if constexpr ((VM & 1) != 0) issue_a(std::integral_constant<int, SLI>{});
-        k64_b16x8 bf[16];
-#pragma unroll
-        for (int jb = 0; jb < 16; ++jb) bf[jb] = __builtin_bit_cast(k64_b16x8, Bc[16 * jb]);
-#pragma unroll
-        for (int jb = 0; jb < 16; ++jb) {
-#pragma unroll
-            for (int mb = 0; mb < MBW; ++mb) {
-                if constexpr (I8) {
-                    const k64_i32x4 ai = __builtin_bit_cast(k64_i32x4, a[mb]);
-                    const k64_i32x4 bi = __builtin_bit_cast(k64_i32x4, bf[jb]);
-                    acc[mb][jb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ai, bi, acc[mb][jb], 0, 0, 0);
-                } else {
-                    acc[mb][jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(k64_b16x8, a[mb]), bf[jb],
-                                                                          acc[mb][jb], 0, 0, 0);
-                }
-            }
-        }
-        if constexpr ((VM & 2) != 0) issue_b(gb, stgb);
-        constexpr int NAv = (VM & 1) != 0 ? 2 * MBW : 0, NBv = (VM & 2) != 0 ? PIECES : 0;
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-#pragma unroll
-        for (int p = 0; p < 16; ++p) {
-            __builtin_amdgcn_sched_group_barrier(0x008, MBW, 0);
-            if (p < 12) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            if constexpr (NAv > 0) {
-                if (p % (16 / NAv) == 1 % (16 / NAv)) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-            }
-            if constexpr (NBv > 0) {
-                if (p >= 16 - NBv) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-#ifndef HIPANN_STAG_DBG
-#define HIPANN_STAG_DBG 0
-#endif
-    const bool late = STAG && HIPANN_STAG_DBG != 2 && wave >= K64Geom<MBW>::W / 2;  // wave-uniform
-    auto body_stag = [&](int64_t g, auto slot_c) __attribute__((always_inline)) {
-        constexpr int SL = decltype(slot_c)::value;
-        constexpr int SLP = (SL + 2) % 3, SLN = (SL + 1) % 3;  // slots of K-steps g − 1 and g + 1
-        const bool xn = g < G && ks == ks_xn;
-        if constexpr ((HIPANN_K64_ABLATE & 8) == 0) __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (xn) load_xn(t);
-        __builtin_amdgcn_sched_barrier(0);
-        const int stgb = stage < 2 ? stage + 3 : stage - 2;
-        const int stprev = stage == 0 ? NB - 1 : stage - 1;
-        k64_u32x4 ax[MBW], ay[MBW];
-#pragma unroll
-        for (int mb = 0; mb < MBW; ++mb) {
-            ax[mb] = late ? ar[SLP][1][mb] : ar[SL][0][mb];
-            ay[mb] = late ? ar[SL][0][mb] : ar[SL][1][mb];
-        }
-        if (late ? g >= 1 : g < G)
-            chunk_rt(late ? 1 : 0, late ? stprev : stage, ax, std::integral_constant<int, 0>{}, 0, 0, 0,
-                     std::integral_constant<int, SLN>{});
-#if HIPANN_STAG_DBG != 1
-        if (late && g >= 1 && ks == 0) {  // g − 1 ended a tile (g = G included: G is whole tiles)
-            // the epilogue's VALU at a lower priority than the partner's MFMA issue (MI355X_MICROARCH.md, two waves per
-            // SIMD, item 2: arbitration by priority, then age)
-            __builtin_amdgcn_s_setprio(0);
+    auto step = [&](int64_t g, auto slot_c) __attribute__((always_inline)) {
+        body(g, slot_c);
+        if (++ks == ns) {
+            ks = 0;
             epilogue();
-            __builtin_amdgcn_s_setprio(2);
         }
-#endif
-        if (g < G)
-            chunk_rt(late ? 0 : 1, stage, ay, std::integral_constant<int, 3>{}, 0, clampg(g + 3), stgb,
-                     std::integral_constant<int, SLP>{});
-        if (!late && g < G && ks == ns - 1) {
-            __builtin_amdgcn_s_setprio(0);
-            epilogue();
-            __builtin_amdgcn_s_setprio(2);
-        }
-        // A(g + 1), B(g + 1) landed; B(g + 2), A(g + 2), B(g + 3) (and the norms issued at the top) may stay in flight
-        if (xn) __builtin_amdgcn_s_waitcnt(kWaitStepXn);
-        else __builtin_amdgcn_s_waitcnt(kWaitStep);
-        ks = ks + 1 < ns ? ks + 1 : 0;
-        stage = stage + 1 < NB ? stage + 1 : 0;
     };
-    if constexpr (STAG) {
-        __builtin_amdgcn_s_setprio(2);
-        for (int64_t g = 0; g <= G; g += 3) {
-            body_stag(g, std::integral_constant<int, 0>{});
-            if (g + 1 <= G) body_stag(g + 1, std::integral_constant<int, 1>{});
-            if (g + 2 <= G) body_stag(g + 2, std::integral_constant<int, 2>{});
-        }
-    } else {
-        auto step = [&](int64_t g, auto slot_c) __attribute__((always_inline)) {
-            body(g, slot_c);
-            if (++ks == ns) {
-                ks = 0;
-                epilogue();
-            }
-        };
-        for (int64_t g = 0; g < G; g += 3) {
-            step(g, std::integral_constant<int, 0>{});
-            if (g + 1 < G) step(g + 1, std::integral_constant<int, 1>{});
-            if (g + 2 < G) step(g + 2, std::integral_constant<int, 2>{});
-        }
+    for (int64_t g = 0; g < G; g += 3) {
+        step(g, std::integral_constant<int, 0>{});
+        if (g + 1 < G) step(g + 1, std::integral_constant<int, 1>{});
+        if (g + 2 < G) step(g + 2, std::integral_constant<int, 2>{});
     }
     // no LDS-DMA copy may land after the block's LDS is handed to the next block
     __builtin_amdgcn_s_waitcnt(0xF70u);
@@ -946,8 +835,7 @@ int flat_keys_kth_max() { return 256 * KTH_KPT; }
 void launch_flat_keys_kth(const float *keys, int S, int64_t nq, int k, float *bound, hipStream_t st) {
     if (nq <= 0) return;
     HIPANN_REQUIRE(S >= k && S <= 256 * KTH_KPT, "flat_keys_kth: sample size");
-    // HIPANN_FLAT_KTH_NARROW=0 (A/B): the full 32-round bisection over every register
-    static const int narrow = [] { const char *e = std::getenv("HIPANN_FLAT_KTH_NARROW"); return e ? std::atoi(e) : 1; }();
+    const int narrow = 1;  // (0, the full 32-round bisection over every register, is the test hook's other side)
     // keys per thread sized to the sample
     if (S <= 256 * 16)
         hipLaunchKernelGGL(flat_keys_kth<16>, dim3((unsigned)nq), dim3(256), 0, st, keys, S, nq, k, bound, narrow);
@@ -1331,19 +1219,14 @@ void launch_flat_bf16_k64(const FlatK64Args &a, hipStream_t st) {
                            a.tiles_per_split, a.tile_begin, a.tile_end, a.bound, a.cand_d, a.cand_i, a.cand_n, a.cap,
                            a.resume ? 1 : 0, qscale, xscale);
     };
-    // HIPANN_K64_STAGGER=1 (A/B, measured and rejected in r06): the staggered schedule (STAG above).  Same-box A/B,
-    // alternating: 10M x 768 kernel 7.86-7.92 → 9.08-9.10 ms, C2 1.00 → 1.23, C5 9.69 → 11.12 (with the epilogue at
-    // s_setprio 0 under the partner's MFMAs: no better) — the default keeps every wave on the same K-step.  It needs
-    // ≥ 3 K-steps per tile (the tile's norms are loaded two K-steps before its epilogue).
-    static const bool stag_env = [] { const char *e = std::getenv("HIPANN_K64_STAGGER"); return e && std::atoi(e); }();
-    const bool stag = stag_env && nk / 2 >= 3;
+    // (r06, measured and rejected: a staggered schedule, waves W/2..W−1 half a K-step behind their SIMD partners so one
+    // wave's epilogue runs beside the other's MFMAs.  Same-box A/B, alternating: 10M x 768 kernel 7.86-7.92 →
+    // 9.08-9.10 ms, C2 1.00 → 1.23, C5 9.69 → 11.12 (with the epilogue at s_setprio 0 under the partner's MFMAs: no
+    // better) — every wave stays on the same K-step.  DESIGN §5 names the commit that holds the code.)
     if (qscale) {
         if (keys) {
             if (metric == kL2) go(flat_bf16_k64<true, true, true>);
             else go(flat_bf16_k64<false, true, true>);
-        } else if (stag) {
-            if (metric == kL2) go(flat_bf16_k64<true, false, true, 2, true>);
-            else go(flat_bf16_k64<false, false, true, 2, true>);
         } else {
             if (metric == kL2) go(flat_bf16_k64<true, false, true>);
             else go(flat_bf16_k64<false, false, true>);
@@ -1356,12 +1239,6 @@ void launch_flat_bf16_k64(const FlatK64Args &a, hipStream_t st) {
         else go(flat_bf16_k64<false, false>);
     }
     HIPANN_CHECK(hipGetLastError());
-}
-
-// HIPANN_FLAT_CAND_NARROW=0 (A/B): the one-wave-per-query wave-list kernels
-static bool cand_narrow_on(int k) {
-    static const bool env = [] { const char *e = std::getenv("HIPANN_FLAT_CAND_NARROW"); return !e || std::atoi(e); }();
-    return env && k <= 64;
 }
 
 // narrow: the one-block-per-query narrowed kernels (k ≤ 64), else the one-wave-per-query wave lists
@@ -1392,12 +1269,12 @@ static void launch_flat_cand_select_as(bool narrow, const float *cand_d, const i
 
 void launch_flat_cand_bound(const float *cand_d, const int *cand_n, int nsplit, int cap, int64_t nq, int k,
                             float *bound, hipStream_t st) {
-    launch_flat_cand_bound_as(cand_narrow_on(k), cand_d, cand_n, nsplit, cap, nq, k, bound, st);
+    launch_flat_cand_bound_as(k <= 64, cand_d, cand_n, nsplit, cap, nq, k, bound, st);
 }
 
 void launch_flat_cand_select(const float *cand_d, const int *cand_i, const int *cand_n, int nsplit, int cap, int64_t nq,
                              int k, float *out_d, int *out_i, int *nflag, int *flagged, hipStream_t st) {
-    launch_flat_cand_select_as(cand_narrow_on(k), cand_d, cand_i, cand_n, nsplit, cap, nq, k, out_d, out_i, nflag,
+    launch_flat_cand_select_as(k <= 64, cand_d, cand_i, cand_n, nsplit, cap, nq, k, out_d, out_i, nflag,
                                flagged, st);
 }
 

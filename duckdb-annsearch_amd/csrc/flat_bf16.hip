@@ -31,7 +31,6 @@
 #include "runtime.hpp"
 #include "wave_topk.hpp"
 
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
@@ -369,7 +368,8 @@ __global__ void __launch_bounds__(256) flat_bf16_seed(const float *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
-constexpr int kB16StagesDefault = 4;  // 10M x 768: 19.16 (3) / 18.68 (4) / 19.06 (5) ms
+// RA stages (LDS-DMA chunks in flight = stages − 1).  10M x 768: 19.16 (3) / 18.68 (4) / 19.06 (5) ms
+constexpr int kB16StagesDefault = 4;
 int flat_bf16_waves(int64_t nq) { return nq >= 256 ? 8 : nq >= 128 ? 4 : 2; }
 int flat_bf16_tile_rows() { return B16_TN; }
 // the largest list length k (≤ 64) of flat_bf16_topk's LDS lists at this batch size (its launcher's LDS check)
@@ -428,32 +428,21 @@ void launch_flat_bf16_topk(const float *Q, const float *qn, int64_t nq, void *qi
         hipLaunchKernelGGL(kern, grid, block, smem, st, qa, qn, nq, xa, xn, N, nk, k, nqt, nsplit, tiles_per_split, pd,
                            pi, seed);
     };
-    static const bool ra = [] { const char *e = std::getenv("HIPANN_B16_RA"); return !e || std::atoi(e); }();
-    // RA stages (HIPANN_B16_NB = 3..5, A/B): LDS-DMA chunks in flight = NB − 1
-    static const int nb = [] { const char *e = std::getenv("HIPANN_B16_NB"); const int v = e ? std::atoi(e) : 0;
-                               return v >= 3 && v <= 5 ? v : kB16StagesDefault; }();
-    const size_t smem_ra = (size_t)nb * (B16_TN * 4) * 16 + (size_t)QM * k * 8;
-    if (ra && W == 8 && smem_ra <= 160 * 1024) {
+    if (W == 8) {
+        // 8 waves: the RA kernel.  Its LDS (kB16StagesDefault tile stages of 16 KiB + the lists) is below the three
+        // 32 KiB stages + lists that were just required to fit.
+        const size_t smem_ra = (size_t)kB16StagesDefault * (B16_TN * 4) * 16 + (size_t)QM * k * 8;
         auto go_ra = [&](auto kern) {
             hipLaunchKernelGGL(kern, grid, block, smem_ra, st, qa, qn, nq, xa, xn, N, nk, k, nqt, nsplit, tiles_per_split,
                                pd, pi, seed);
         };
-        if (metric == kL2) {
-            if (nb == 3) go_ra(flat_bf16_topk<true, 8, true, 3>);
-            else if (nb == 4) go_ra(flat_bf16_topk<true, 8, true, 4>);
-            else go_ra(flat_bf16_topk<true, 8, true, 5>);
-        } else {
-            if (nb == 3) go_ra(flat_bf16_topk<false, 8, true, 3>);
-            else if (nb == 4) go_ra(flat_bf16_topk<false, 8, true, 4>);
-            else go_ra(flat_bf16_topk<false, 8, true, 5>);
-        }
+        if (metric == kL2) go_ra(flat_bf16_topk<true, 8, true, kB16StagesDefault>);
+        else go_ra(flat_bf16_topk<false, 8, true, kB16StagesDefault>);
     } else if (metric == kL2) {
-        if (W == 8) go(flat_bf16_topk<true, 8, false>);
-        else if (W == 4) go(flat_bf16_topk<true, 4, false>);
+        if (W == 4) go(flat_bf16_topk<true, 4, false>);
         else go(flat_bf16_topk<true, 2, false>);
     } else {
-        if (W == 8) go(flat_bf16_topk<false, 8, false>);
-        else if (W == 4) go(flat_bf16_topk<false, 4, false>);
+        if (W == 4) go(flat_bf16_topk<false, 4, false>);
         else go(flat_bf16_topk<false, 2, false>);
     }
     HIPANN_CHECK(hipGetLastError());

@@ -3,7 +3,7 @@
 // Replaces the faiss-metal Flat pipeline (MetalIndexFlat::search, MetalIndexFlat.mm:294-369):
 //   l2_norm*.metal            → row_norms_f32
 //   simdgroup_gemm*.metal + warp/block_select.metal (nq×N distance matrix, then select)
-//                             → flat_gemm_topk: fp32 MFMA Q·Xᵀ with the L2 epilogue and a
+//                             → flat_gemm_topk2: fp32 MFMA Q·Xᵀ with the L2 epilogue and a
 //                               wave-distributed top-k fused in; the nq×N matrix never exists
 //   fused_l2_topk.metal (small nq streaming scan)
 //                             → flat_scan_topk: direct Σ(q−x)², HBM-bound
@@ -11,14 +11,13 @@
 //
 // Distance forms follow FAISS CPU (the parity target, SURVEY §8a semantic contract):
 //   nq <  20  → direct Σ(q−x)² (fvec_L2sqr)                      → flat_scan_topk
-//   nq >= 20  → ‖q‖² + ‖x‖² − 2·q·x, clamped ≥ 0 (BLAS path)      → flat_gemm_topk
+//   nq >= 20  → ‖q‖² + ‖x‖² − 2·q·x, clamped ≥ 0 (BLAS path)      → flat_gemm_topk2
 //   IP        → q·x, best = largest (selected as key = −q·x)
 #include "common.hpp"
 #include "wave_topk.hpp"
 
 #include <algorithm>
 #include <type_traits>
-#include <cstdlib>
 #include <utility>
 
 namespace hipann {
@@ -99,7 +98,10 @@ __device__ __forceinline__ void gemm_stage_store(float *__restrict__ lds, const 
 }
 
 // WRITE = true: no selection — the epilogue writes the keys of every (query, row) pair of the
-// tile to keys_out[q * ldk + row] (the k > 64 path selects from that matrix with rows_topk).
+// tile to keys_out[q * ldk + row] (the k > 64 path selects from that matrix with rows_topk).  This is the only
+// half that is launched (launch_flat_gemm_keys; the fused k ≤ 64 path is flat_gemm_topk2).  The selecting half
+// stays in the source because, with it cut out, the compiler orders eight scalar instructions of this half's
+// prologue differently (profiles/flat_variants_prune/README.md).
 template <bool VEC4, bool WRITE = false>
 __global__ void __launch_bounds__(256, 1)
 flat_gemm_topk(const float *__restrict__ Q, const float *__restrict__ qnorm, int64_t nq,
@@ -1289,107 +1291,6 @@ rows_select_narrow(const float *__restrict__ keys, int64_t ldk, int ncols, int64
     }
 }
 
-// rows_select_block — rows of 257..1024 keys: rows_select_small's select with the row spread over a
-// block of 4 waves (column c = 256·wave + 64·j + lane, J = 4 registers per lane); each search step sums
-// the waves' ballot counts through LDS (one barrier), the compaction runs in (wave, j, lane) = column
-// order, and wave 0 sorts and writes the output (and the IVF plan's count step).  A quarter of the
-// per-wave ballot chain of the one-wave version (16 µs for 1024 × 1024 keys).  Measured and rejected (r04): a
-// one-barrier variant (each wave selects its 256 columns' k best, wave 0 merges): 13.5 µs, the same — the
-// barriers are not the critical path.
-__global__ void __launch_bounds__(256)
-rows_select_block(const float *__restrict__ keys, int64_t ldk, int ncols, int64_t nq, int k, int kout,
-                  int64_t label_offset, float out_sign, float *__restrict__ D, int64_t *__restrict__ I,
-                  const int *__restrict__ list_len, int nlist, int chunk_rows, int *__restrict__ ccnt,
-                  int *__restrict__ slot_off, int *__restrict__ qtot) {
-    constexpr int J = 4, WV = 4;
-    __shared__ float sk[64];
-    __shared__ int sc[64];
-    __shared__ int scnt[2][WV];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t q = blockIdx.x;
-    const float *row = keys + q * ldk;
-    float v[J];
-    unsigned u[J];
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const int c = 256 * wv + 64 * j + lane;
-        v[j] = c < ncols ? row[c] : __builtin_nanf("");
-    }
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const float f = v[j] == 0.f ? 0.f : v[j];
-        const unsigned b = __float_as_uint(f);
-        u[j] = v[j] == v[j] ? ((b >> 31) ? ~b : (b | 0x80000000u)) : 0xffffffffu;
-    }
-    unsigned T = 0;
-    for (int bit = 31; bit >= 0; --bit) {
-        const unsigned cand = T | (1u << bit);
-        int cnt = 0;
-#pragma unroll
-        for (int j = 0; j < J; ++j) cnt += __popcll(__ballot(u[j] < cand));
-        const int par = bit & 1;
-        if (lane == 0) scnt[par][wv] = cnt;
-        __syncthreads();
-        const int tot = scnt[par][0] + scnt[par][1] + scnt[par][2] + scnt[par][3];
-        if (tot < k) T = cand;
-    }
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    int nlt = 0, neq = 0;
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        nlt += __popcll(__ballot(u[j] < T));
-        neq += __popcll(__ballot(u[j] == T && u[j] != 0xffffffffu));
-    }
-    __syncthreads();  // every wave has read the last search step's counts
-    if (lane == 0) { scnt[0][wv] = nlt; scnt[1][wv] = neq; }
-    __syncthreads();
-    int olt = 0, oeq = 0, tlt = 0, teq = 0;
-#pragma unroll
-    for (int w = 0; w < WV; ++w) {
-        olt += w < wv ? scnt[0][w] : 0;
-        oeq += w < wv ? scnt[1][w] : 0;
-        tlt += scnt[0][w];
-        teq += scnt[1][w];
-    }
-    int plt = olt, peq = tlt + oeq;
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const bool a = u[j] < T, b = u[j] == T && u[j] != 0xffffffffu;
-        const unsigned long long ma = __ballot(a), mb = __ballot(b);
-        const int c = 256 * wv + 64 * j + lane;
-        if (a) { const int p = plt + __popcll(ma & lt); sk[p] = v[j]; sc[p] = c; }
-        if (b) { const int p = peq + __popcll(mb & lt); if (p < k) { sk[p] = v[j]; sc[p] = c; } }
-        plt += __popcll(ma);
-        peq += __popcll(mb);
-    }
-    const int nsel = tlt + teq < k ? tlt + teq : k;
-    __syncthreads();
-    if (wv != 0) return;
-    float kk = lane < nsel ? sk[lane] : __builtin_inff();
-    int cc = lane < nsel ? sc[lane] : 0x7fffffff;
-    wave_rank_sort(kk, cc, nsel);
-    const bool pad = lane >= nsel || kk == __builtin_inff();
-    if (lane < kout) {
-        D[q * kout + lane] = pad ? (out_sign > 0.f ? __builtin_inff() : -__builtin_inff()) : kk * out_sign;
-        I[q * kout + lane] = pad ? -1 : (int64_t)cc + label_offset;
-    }
-    if (ccnt) {  // the IVF plan's per-query step (ivf_count_q) on the probes just selected (kout ≤ 64)
-        const int64_t l = lane < kout && !pad ? (int64_t)cc + label_offset : -1;
-        const int len = l >= 0 && l < nlist ? list_len[l] : 0;
-        if (len > 0) atomicAdd(ccnt + (int64_t)(q % kPlanCopies) * nlist + l, 1);
-        const int vv = len > 0 ? (len + chunk_rows - 1) / chunk_rows : 0;
-        int x = vv;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(x, o);
-            if (lane >= o) x += t;
-        }
-        if (lane < kout) slot_off[q * kout + lane] = x - vv;
-        if (lane == 63) qtot[q] = x;
-    }
-}
-
-
 // Raw merge: nparts partial [part][nq][k] (keys, int ids) → one [nq][k] partial (keys, int ids).
 template <int S>
 __global__ void __launch_bounds__(256)
@@ -1433,26 +1334,13 @@ void launch_flat_gemm_topk(const float *Q, const float *qn, int64_t nq, const fl
     const int nqt = (int)ceil_div(nq, GBM);
     const bool vec4 = (d % 4 == 0) && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)X % 16 == 0);
     dim3 grid((unsigned)(nqt * nsplit)), block(256);
-    static const int v1 = [] { const char *e = std::getenv("HIPANN_FLAT_V1"); return e ? std::atoi(e) : 0; }();
-    if (!v1) {
-        const size_t smem2 = gemm2_smem_bytes(k);
-        if (metric == kL2) {
-            if (vec4) hipLaunchKernelGGL((flat_gemm_topk2<true, true>), grid, block, smem2, st, Q, qn, nq, X, xn, N, d, k, nqt, nsplit, tiles_per_split, pd, pi);
-            else hipLaunchKernelGGL((flat_gemm_topk2<false, true>), grid, block, smem2, st, Q, qn, nq, X, xn, N, d, k, nqt, nsplit, tiles_per_split, pd, pi);
-        } else {
-            if (vec4) hipLaunchKernelGGL((flat_gemm_topk2<true, false>), grid, block, smem2, st, Q, qn, nq, X, xn, N, d, k, nqt, nsplit, tiles_per_split, pd, pi);
-            else hipLaunchKernelGGL((flat_gemm_topk2<false, false>), grid, block, smem2, st, Q, qn, nq, X, xn, N, d, k, nqt, nsplit, tiles_per_split, pd, pi);
-        }
-        HIPANN_CHECK(hipGetLastError());
-        return;
-    }
-    const size_t smem = gemm_smem_bytes();
-    if (vec4) {
-        hipLaunchKernelGGL(flat_gemm_topk<true>, grid, block, smem, st, Q, qn, nq, X, xn, N, d, metric, k, nqt,
-                           nsplit, tiles_per_split, pd, pi);
+    const size_t smem2 = gemm2_smem_bytes(k);
+    if (metric == kL2) {
+        if (vec4) hipLaunchKernelGGL((flat_gemm_topk2<true, true>), grid, block, smem2, st, Q, qn, nq, X, xn, N, d, k, nqt, nsplit, tiles_per_split, pd, pi);
+        else hipLaunchKernelGGL((flat_gemm_topk2<false, true>), grid, block, smem2, st, Q, qn, nq, X, xn, N, d, k, nqt, nsplit, tiles_per_split, pd, pi);
     } else {
-        hipLaunchKernelGGL(flat_gemm_topk<false>, grid, block, smem, st, Q, qn, nq, X, xn, N, d, metric, k, nqt,
-                           nsplit, tiles_per_split, pd, pi);
+        if (vec4) hipLaunchKernelGGL((flat_gemm_topk2<true, false>), grid, block, smem2, st, Q, qn, nq, X, xn, N, d, k, nqt, nsplit, tiles_per_split, pd, pi);
+        else hipLaunchKernelGGL((flat_gemm_topk2<false, false>), grid, block, smem2, st, Q, qn, nq, X, xn, N, d, k, nqt, nsplit, tiles_per_split, pd, pi);
     }
     HIPANN_CHECK(hipGetLastError());
 }
@@ -1471,9 +1359,8 @@ static void launch_flat_gemm_topk_bf_t(const float *Q, const float *qn, int64_t 
     HIPANN_CHECK(hipGetLastError());
     // Block shape: 4 waves (128 queries, two blocks per CU) or 8 waves (256 queries, one block per CU, one
     // row staging shared by twice the MFMAs).  Measured at 10M × 768: 2 terms 60.3 ms (4) vs 65.6 ms (8),
-    // 3 terms 90.6 ms (4) vs 86.2 ms (8).  HIPANN_FLAT_BF_WAVES=4|8 overrides (A/B).
-    static const int Wenv = [] { const char *e = std::getenv("HIPANN_FLAT_BF_WAVES"); return e ? std::atoi(e) : 0; }();
-    const int W = Wenv == 4 || Wenv == 8 ? Wenv : (NP == 3 ? 8 : 4);
+    // 3 terms 90.6 ms (4) vs 86.2 ms (8).
+    constexpr int W = NP == 3 ? 8 : 4;
     const int nqt = (int)ceil_div(nq, 32 * W);
     const bool vec4 = (d % 4 == 0) && ((uintptr_t)X % 16 == 0);
     const size_t smem = gemm_bf_smem_bytes(NP, k, W);
@@ -1485,11 +1372,11 @@ static void launch_flat_gemm_topk_bf_t(const float *Q, const float *qn, int64_t 
                            pd, pi, qmajor);
     };
     if (metric == kL2) {
-        if (vec4) W == 8 ? go(flat_gemm_topk_bf<true, true, NP, 8>) : go(flat_gemm_topk_bf<true, true, NP, 4>);
-        else W == 8 ? go(flat_gemm_topk_bf<false, true, NP, 8>) : go(flat_gemm_topk_bf<false, true, NP, 4>);
+        if (vec4) go(flat_gemm_topk_bf<true, true, NP, W>);
+        else go(flat_gemm_topk_bf<false, true, NP, W>);
     } else {
-        if (vec4) W == 8 ? go(flat_gemm_topk_bf<true, false, NP, 8>) : go(flat_gemm_topk_bf<true, false, NP, 4>);
-        else W == 8 ? go(flat_gemm_topk_bf<false, false, NP, 8>) : go(flat_gemm_topk_bf<false, false, NP, 4>);
+        if (vec4) go(flat_gemm_topk_bf<true, false, NP, W>);
+        else go(flat_gemm_topk_bf<false, false, NP, W>);
     }
     HIPANN_CHECK(hipGetLastError());
 }
@@ -1747,7 +1634,7 @@ flat_keys_ksplit(const float *__restrict__ Q, const float *__restrict__ qnorm, i
 // (fb_split4: x = x₁ + x₂ + x₃ exactly for normal floats), and each 16-dim step runs flat_gemm_topk_bf's six term
 // products (FbProducts<3>, smallest first; the dropped ones are ≤ 2⁻²⁶ relative) on v_mfma_f32_32x32x16_bf16
 // with fp32 accumulation: fp32-level keys at 0.375 of the fp32 matrix-core time (the IVF coarse quantizer,
-// HIPANN_COARSE_BF3).  LDS rows of 32 dims are 80 B (64 + 16 pad): a b128 fragment read by 16 lanes of 16
+// CoarseKeysScope in ivf.cpp).  LDS rows of 32 dims are 80 B (64 + 16 pad): a b128 fragment read by 16 lanes of 16
 // consecutive rows touches 16 distinct 4-bank groups.  LDS: [half][buffer][term][64 query rows + 64 table rows]
 // × 80 B = 120 KiB (one block per CU, as flat_keys_ksplit).
 constexpr int KB3_ROW = 80;                 // bytes per staged row (32 bf16 + pad)
@@ -1765,7 +1652,7 @@ __device__ __forceinline__ void kb3_stage_store(char *__restrict__ buf, int rowb
     }
 }
 
-template <bool VEC4, int NS>
+template <bool VEC4>
 __global__ void __launch_bounds__(512)
 flat_keys_bf3(const float *__restrict__ Q, const float *__restrict__ qnorm, int64_t nq, const float *__restrict__ X,
               const float *__restrict__ xnorm, int64_t N, int d, int metric, int nqt, float *__restrict__ keys_out,
@@ -1781,8 +1668,10 @@ flat_keys_bf3(const float *__restrict__ Q, const float *__restrict__ qnorm, int6
     const int nkh = ((d + GBK - 1) / GBK) >> 1;  // chunks per half (the launcher checks the count is even)
     const int kbase = half * nkh * GBK;
     char *hb = lds + half * 2 * KB3_BUF;  // this half's two buffers
-    // NS chunks in flight in registers (set = chunk mod NS) ahead of the LDS buffer being multiplied (2: as
-    // flat_keys_ksplit; deeper rings measured no faster, see the launcher)
+    // NS chunks in flight in registers (set = chunk mod NS) ahead of the LDS buffer being multiplied: 2, as
+    // flat_keys_ksplit (deeper rings measured no faster, see the launcher).  The loops stay written over NS: spelled
+    // out for two steps they compile to another register allocation.
+    constexpr int NS = 2;
     float4 sa[NS][2], sb[NS][2];
     ks_stage_load<VEC4>(Q, q0, nq, d, kbase, t, sa[0]);
     ks_stage_load<VEC4>(X, x0, N, d, kbase, t, sb[0]);
@@ -1865,92 +1754,6 @@ flat_keys_bf3(const float *__restrict__ Q, const float *__restrict__ qnorm, int6
     }
 }
 
-// flat_keys_direct — the same 64 × 64 tiles, MFMAs and k order as flat_keys_small (bit-identical keys), but every
-// wave loads its own A / B fragments straight from memory into a 3-chunk register ring: no LDS staging, no
-// per-chunk barrier.  The inputs are small and cache-resident (the coarse quantizer's queries and centroids),
-// so the doubled L2 reads cost little, while the 4 waves — one per SIMD — no longer wait on each other
-// (flat_keys_small: 32 µs for 1024 × 1024 × 768, ≈ 3× its MFMA time).
-template <bool VEC4>
-__device__ __forceinline__ void keys_frag_load(const float *__restrict__ base, int64_t row, int d, int k0,
-                                               float4 (&r)[4]) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int kk = k0 + 4 * u;
-        const float *src = base + row * (int64_t)d + kk;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (VEC4) {
-            if (kk < d) v = *reinterpret_cast<const float4 *>(src);
-        } else {
-            if (kk + 0 < d) v.x = src[0];
-            if (kk + 1 < d) v.y = src[1];
-            if (kk + 2 < d) v.z = src[2];
-            if (kk + 3 < d) v.w = src[3];
-        }
-        r[u] = v;
-    }
-}
-
-template <bool VEC4, int KR>
-__global__ void __launch_bounds__(256)
-flat_keys_direct(const float *__restrict__ Q, const float *__restrict__ qnorm, int64_t nq, const float *__restrict__ X,
-                 const float *__restrict__ xnorm, int64_t N, int d, int metric, int nqt, float *__restrict__ keys_out,
-                 int64_t ldk) {
-    const int lb = xcd_remap(blockIdx.x, gridDim.x);
-    const int qt = lb % nqt;
-    const int64_t q0 = (int64_t)qt * SBM, x0 = (int64_t)(lb / nqt) * SBM;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int wr = wave >> 1, wc = wave & 1;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int nk = (d + GBK - 1) / GBK;
-    // this lane's fragment rows (rows past the end re-read the last row; their keys are never written)
-    int64_t qa = q0 + 32 * wr + l31, xb = x0 + 32 * wc + l31;
-    qa = qa < nq ? qa : nq - 1;
-    xb = xb < N ? xb : N - 1;
-    constexpr int R = KR;
-    float4 ra[R][4], rb[R][4];
-#pragma unroll
-    for (int s = 0; s < R; ++s)
-        if (s < nk) {
-            keys_frag_load<VEC4>(Q, qa, d, s * GBK + 16 * h, ra[s]);
-            keys_frag_load<VEC4>(X, xb, d, s * GBK + 16 * h, rb[s]);
-        }
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    auto step = [&](int kc, auto slot_c) {
-        constexpr int S = decltype(slot_c)::value;  // kc % R
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ra[S][u][e], rb[S][u][e], acc, 0, 0, 0);
-        if (kc + R < nk) {
-            keys_frag_load<VEC4>(Q, qa, d, (kc + R) * GBK + 16 * h, ra[S]);
-            keys_frag_load<VEC4>(X, xb, d, (kc + R) * GBK + 16 * h, rb[S]);
-        }
-    };
-    for (int kc = 0; kc < nk; kc += R) {
-        [&]<int... P>(std::integer_sequence<int, P...>) {
-            ((kc + P < nk ? step(kc + P, std::integral_constant<int, P>{}) : void()), ...);
-        }(std::make_integer_sequence<int, R>{});
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int64_t q = q0 + 32 * wr + (r & 3) + 8 * (r >> 2) + 4 * h;
-        const int64_t x = x0 + 32 * wc + l31;
-        if (q < nq && x < N) {
-            const float ip = acc[r];
-            float key;
-            if (metric == kL2) {
-                key = fmaf(-2.f, ip, qnorm[q] + xnorm[x]);
-                key = key < 0.f ? 0.f : key;
-            } else {
-                key = -ip;
-            }
-            keys_out[q * ldk + x] = key;
-        }
-    }
-}
-
 // Word copy between device memory and the device mapping of pinned host buffers (small host-pointer
 // calls: no DMA-engine round trips for the query upload and the result download).
 __global__ void __launch_bounds__(256) copy_words(const unsigned *__restrict__ src, unsigned *__restrict__ dst,
@@ -1998,35 +1801,21 @@ void launch_flat_gemm_keys(const float *Q, const float *qn, int64_t nq, const fl
         const int sq = (int)ceil_div(nq, SBM);
         const int64_t blocks = (int64_t)sq * ceil_div(N, SBM);
         dim3 g((unsigned)blocks), b(256);
-        // HIPANN_KEYS = 2 (default; even chunk counts): flat_keys_ksplit; 0 (and odd counts): LDS-staged
-        // (flat_keys_small, 29.7 µs for 1024 × 1024 × 768); 3 / 6: the
-        // register-ring flat_keys_direct with that many chunks in flight (A/B: 34.0 / 35.7 µs).  Measured and
-        // dropped at r04: four K-groups of 4 waves (24.0 µs) and 64-dim stages (25.0 µs) against 23.9 µs.
-        static const int mode = [] { const char *e = std::getenv("HIPANN_KEYS"); return e ? std::atoi(e) : 2; }();
+        // Even chunk counts: the K-split tiles (flat_keys_ksplit, 8 waves, two per SIMD: 23.9 µs for 1024 × 1024 ×
+        // 768); odd counts: LDS-staged on 4 waves (flat_keys_small, 29.7 µs).  Measured and rejected: a register ring
+        // without LDS staging, 3 / 6 chunks in flight (34.0 / 35.7 µs); at r04 four K-groups of 4 waves (24.0 µs) and
+        // 64-dim stages (25.0 µs).
         const int nk = (d + GBK - 1) / GBK;
         // the IVF coarse quantizer: the same tiles on the bf16 matrix cores (3 terms): 25.4 → 22.6-23.0 µs at 1024 ×
-        // 1024 × 768.  Not the matrix cores' time (3.8 µs) and not the loads' depth: HIPANN_KEYS_DEPTH = 4 / 6 chunks
-        // in flight (22.6 / 23.4 / 23.3 µs for 2 / 4 / 6) and two or four independent accumulator chains (22.8 / 22.6
-        // vs 23.7 µs) were measured and left out; PMC: matrix cores busy ≈ 15 %, TD ≈ 33 %, TA ≈ 20 % of the kernel
-        static const int depth = [] { const char *e = std::getenv("HIPANN_KEYS_DEPTH"); return e ? std::atoi(e) : 2; }();
+        // 1024 × 768.  Not the matrix cores' time (3.8 µs) and not the loads' depth: 4 / 6 chunks in flight (22.6 /
+        // 23.4 / 23.3 µs for 2 / 4 / 6) and two or four independent accumulator chains (22.8 / 22.6 vs 23.7 µs) were
+        // measured and left out; PMC: matrix cores busy ≈ 15 %, TD ≈ 33 %, TA ≈ 20 % of the kernel
         if (bf3 && nk % 2 == 0) {
-#define HIPANN_KB3(NS)                                                                                                    \
-    do {                                                                                                                \
-        if (vec4) hipLaunchKernelGGL((flat_keys_bf3<true, NS>), g, dim3(512), 0, st, Q, qn, nq, X, xn, N, d, metric, sq, keys, ldk); \
-        else hipLaunchKernelGGL((flat_keys_bf3<false, NS>), g, dim3(512), 0, st, Q, qn, nq, X, xn, N, d, metric, sq, keys, ldk); \
-    } while (0)
-            if (depth >= 4) HIPANN_KB3(4);
-            else HIPANN_KB3(2);
-#undef HIPANN_KB3
-        } else if (mode == 2 && nk % 2 == 0) {  // default: the K-split tiles (8 waves, two per SIMD)
+            if (vec4) hipLaunchKernelGGL(flat_keys_bf3<true>, g, dim3(512), 0, st, Q, qn, nq, X, xn, N, d, metric, sq, keys, ldk);
+            else hipLaunchKernelGGL(flat_keys_bf3<false>, g, dim3(512), 0, st, Q, qn, nq, X, xn, N, d, metric, sq, keys, ldk);
+        } else if (nk % 2 == 0) {
             if (vec4) hipLaunchKernelGGL(flat_keys_ksplit<true>, g, dim3(512), 0, st, Q, qn, nq, X, xn, N, d, metric, sq, keys, ldk);
             else hipLaunchKernelGGL(flat_keys_ksplit<false>, g, dim3(512), 0, st, Q, qn, nq, X, xn, N, d, metric, sq, keys, ldk);
-        } else if (mode == 3) {
-            if (vec4) hipLaunchKernelGGL((flat_keys_direct<true, 3>), g, b, 0, st, Q, qn, nq, X, xn, N, d, metric, sq, keys, ldk);
-            else hipLaunchKernelGGL((flat_keys_direct<false, 3>), g, b, 0, st, Q, qn, nq, X, xn, N, d, metric, sq, keys, ldk);
-        } else if (mode == 6) {
-            if (vec4) hipLaunchKernelGGL((flat_keys_direct<true, 6>), g, b, 0, st, Q, qn, nq, X, xn, N, d, metric, sq, keys, ldk);
-            else hipLaunchKernelGGL((flat_keys_direct<false, 6>), g, b, 0, st, Q, qn, nq, X, xn, N, d, metric, sq, keys, ldk);
         } else {
             if (vec4) hipLaunchKernelGGL(flat_keys_small<true>, g, b, 0, st, Q, qn, nq, X, xn, N, d, metric, sq, keys, ldk);
             else hipLaunchKernelGGL(flat_keys_small<false>, g, b, 0, st, Q, qn, nq, X, xn, N, d, metric, sq, keys, ldk);
@@ -2034,14 +1823,15 @@ void launch_flat_gemm_keys(const float *Q, const float *qn, int64_t nq, const fl
         HIPANN_CHECK(hipGetLastError());
         return;
     }
+    // one 128 × 128 tile per block: every tile its own split
     const size_t smem = gemm_smem_bytes();
     dim3 grid((unsigned)(nqt * ntiles)), block(256);
     if (vec4)
         hipLaunchKernelGGL((flat_gemm_topk<true, true>), grid, block, smem, st, Q, qn, nq, X, xn, N, d, metric, 1, nqt,
                            (int)ntiles, (int64_t)1, nullptr, nullptr, keys, ldk);
     else
-        hipLaunchKernelGGL((flat_gemm_topk<false, true>), grid, block, smem, st, Q, qn, nq, X, xn, N, d, metric, 1,
-                           nqt, (int)ntiles, (int64_t)1, nullptr, nullptr, keys, ldk);
+        hipLaunchKernelGGL((flat_gemm_topk<false, true>), grid, block, smem, st, Q, qn, nq, X, xn, N, d, metric, 1, nqt,
+                           (int)ntiles, (int64_t)1, nullptr, nullptr, keys, ldk);
     HIPANN_CHECK(hipGetLastError());
 }
 
@@ -2095,37 +1885,24 @@ void launch_rows_topk(const float *keys, int64_t ldk, int64_t ncols, int64_t nq,
     throw HipError("rows_topk: k too large");
 }
 
-// HIPANN_ROWSEL_WAVE=1: rows of 257..1024 keys on one wave (rows_select_small<16>) instead of a block (A/B)
-static bool one_wave_rows() {
-    static const bool v = [] { const char *e = std::getenv("HIPANN_ROWSEL_WAVE"); return e && std::atoi(e); }();
-    return v;
-}
-
 bool launch_rows_select_out(const float *keys, int64_t ldk, int64_t ncols, int64_t nq, int k, int kout,
                             int64_t label_offset, float out_sign, float *D, int64_t *I, hipStream_t st,
                             IvfPlanHook *hook) {
     const int S = (kout + 63) / 64;
     if (S > 4 || ncols > 0x7ffffffe || k > kout) return false;  // the segment path + merge instead
     dim3 grid((unsigned)ceil_div(nq, 4)), block(256);
-    static const bool lists = [] { const char *e = std::getenv("HIPANN_ROWSEL_LIST"); return e && std::atoi(e); }();
-    if (kout <= 64 && ncols <= 1024 && !lists) {  // rows of ≤ 1024 keys: the bitwise select
+    if (kout <= 64 && ncols <= 1024) {  // rows of ≤ 1024 keys: the bitwise select
         const bool h = hook != nullptr;
         const int *ll = h ? hook->list_len : nullptr;
         const int nl = h ? hook->nlist : 0, cr = h ? hook->chunk_rows : 1;
         int *cc = h ? hook->ccnt : nullptr, *so = h ? hook->slot_off : nullptr, *qt = h ? hook->qtot : nullptr;
-        // HIPANN_ROWSEL_NARROW=0 (A/B): rows of 257..1024 keys on the block select instead of the narrowed wave
-        static const bool narrow = [] { const char *e = std::getenv("HIPANN_ROWSEL_NARROW"); return !e || std::atoi(e); }();
+        // rows of 257..1024 keys: the narrowed wave (measured and rejected: the whole-row search on one wave, 16 µs
+        // for 1024 × 1024 keys, and on a block of 4 waves, 13.1 against 11.7 µs)
         if (ncols <= 256)
             hipLaunchKernelGGL(rows_select_small<4>, grid, block, 0, st, keys, ldk, (int)ncols, nq, k, kout,
                                label_offset, out_sign, D, I, ll, nl, cr, cc, so, qt);
-        else if (narrow)
-            hipLaunchKernelGGL(rows_select_narrow<16>, grid, block, 0, st, keys, ldk, (int)ncols, nq, k, kout,
-                               label_offset, out_sign, D, I, ll, nl, cr, cc, so, qt);
-        else if (!one_wave_rows())
-            hipLaunchKernelGGL(rows_select_block, dim3((unsigned)nq), block, 0, st, keys, ldk, (int)ncols, nq, k, kout,
-                               label_offset, out_sign, D, I, ll, nl, cr, cc, so, qt);
         else
-            hipLaunchKernelGGL(rows_select_small<16>, grid, block, 0, st, keys, ldk, (int)ncols, nq, k, kout,
+            hipLaunchKernelGGL(rows_select_narrow<16>, grid, block, 0, st, keys, ldk, (int)ncols, nq, k, kout,
                                label_offset, out_sign, D, I, ll, nl, cr, cc, so, qt);
         HIPANN_CHECK(hipGetLastError());
         if (h) hook->done = true;

@@ -58,14 +58,10 @@ hipStream_t make_stream(int dev) {
 }
 
 // The search-time coarse step's key GEMM on the bf16 matrix cores (flat_keys_bf3: three-term split, fp32-level
-// keys; HIPANN_COARSE_BF3=0 keeps the fp32 matrix cores, A/B).  List assignment (add / append) keeps fp32.
-static bool coarse_bf3() {
-    static const bool v = [] { const char *e = std::getenv("HIPANN_COARSE_BF3"); return !e || std::atoi(e) != 0; }();
-    return v;
-}
+// keys).  List assignment (add / append) keeps fp32.
 struct CoarseKeysScope {
     FlatShard &s;
-    explicit CoarseKeysScope(FlatShard &x) : s(x) { s.keys_bf3 = coarse_bf3(); }
+    explicit CoarseKeysScope(FlatShard &x) : s(x) { s.keys_bf3 = true; }
     ~CoarseKeysScope() { s.keys_bf3 = false; }
 };
 
@@ -577,8 +573,6 @@ void ivf_coarse_and_plan(IvfBatch &b) {
     // the plan's per-query count step rides on the coarse probe select when that path is taken
     IvfPlanHook hook{sh.list_len.get<int>(), nlist, ivf_chunk_rows(), b.ccnt_cur, sh.slot_off.get<int>(),
                      sh.qtot.get<int>(), false};
-    // HIPANN_IVF_SELECT_HOOK=0 (A/B): the count step in its own launch (ivf_count_q) instead of the select's tail
-    static const bool hook_env = [] { const char *e = std::getenv("HIPANN_IVF_SELECT_HOOK"); return !e || std::atoi(e); }();
     if (b.opts.probes_in) {
         // the probe lists come from the caller (the coarse step partitioned over ranks, hipann_ivf_coarse_device +
         // one all-gather): no quantizer launch; the plan counts the probes itself
@@ -586,7 +580,7 @@ void ivf_coarse_and_plan(IvfBatch &b) {
                                     hipMemcpyDeviceToDevice, b.st));
     } else {
         RoctxRange rr("hipann.ivf.coarse");
-        b.qsh.plan_hook = ivf_plan_query_major() && hook_env ? &hook : nullptr;
+        b.qsh.plan_hook = &hook;
         CoarseKeysScope ck(b.qsh);
         try {
             flat_shard_search(*sh.quant, b.qsh, nq, b.xq, np, np, sh.coarse_d.get<float>(), sh.coarse_i.get<int64_t>(), b.st);

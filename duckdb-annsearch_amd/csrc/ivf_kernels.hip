@@ -5,9 +5,9 @@
 // GEMV-shaped distance + select per query.  Here the whole batch is one pipeline on one stream:
 //
 //   coarse quantizer  : the Flat kernels with k = nprobe  (FAISS quantizer->search, same nq<20 rule)
-//   ivf_count         : histogram of (query, probe) pairs per list
-//   ivf_plan          : one block — exclusive scans → bucket offsets and work-item offsets per list
-//   ivf_fill          : scatter (query, probe) pairs into per-list buckets
+//   ivf_count_q       : histogram of (query, probe) pairs per list (or the coarse select's tail, IvfPlanHook)
+//   ivf_planfill_q    : exclusive scans → bucket offsets and work-item offsets per list, and the scatter of
+//                       (query, probe) pairs into per-list buckets (ivf_plan_q + ivf_fill_q for long list tables)
 //   ivf_scan_topk     : one block per work item = (list ℓ, ≤ 32 of the queries probing ℓ).  The
 //                       list's rows stream through LDS ONCE per item (coalesced float4 loads), each
 //                       of the 4 waves computes direct Σ(q−x)² (FAISS IVFFlat scans with fvec_L2sqr)
@@ -20,7 +20,6 @@
 #include "wave_topk.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 #include <utility>
 
 namespace hipann {
@@ -39,147 +38,20 @@ constexpr int IVF_CH = HIPANN_IVF_CH;   // list rows per work item (big lists sp
 
 __device__ __forceinline__ int ivf_nch(int len) { return (len + IVF_CH - 1) / IVF_CH; }
 
-__global__ void ivf_count(const int64_t *__restrict__ probes, int64_t npairs, const int *__restrict__ list_len,
-                          int nlist, int *__restrict__ cnt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npairs) return;
-    const int64_t l = probes[i];
-    if (l < 0 || l >= nlist) return;
-    if (list_len[l] <= 0) return;  // empty, or owned by another shard
-    atomicAdd(cnt + l, 1);
-}
-
-// Single block: bucket_off[l] = Σ_{<l} cnt, item_off[l] = Σ_{<l} ceil(cnt/group)·nch(l) (one item per
-// (query group, row chunk) of each list); cursor[l] = 0; total items in item_off[nlist].
-__global__ void __launch_bounds__(1024) ivf_plan(const int *__restrict__ cnt, const int *__restrict__ list_len,
-                                                 int nlist, int group, int *__restrict__ bucket_off,
-                                                 int *__restrict__ item_off, int *__restrict__ cursor,
-                                                 int *__restrict__ goff) {
-    __shared__ int sb[1024], si[1024], sg[1024];
-    __shared__ int carry_b, carry_i, carry_g;
-    if (threadIdx.x == 0) { carry_b = 0; carry_i = 0; carry_g = 0; }
-    __syncthreads();
-    for (int base = 0; base < nlist; base += 1024) {
-        const int l = base + threadIdx.x;
-        const int c = l < nlist ? cnt[l] : 0;
-        const int groups = l < nlist ? ivf_ngroups(c, group) : 0;
-        const int items = l < nlist ? groups * ivf_nch(list_len[l]) : 0;
-        sb[threadIdx.x] = c;
-        si[threadIdx.x] = items;
-        sg[threadIdx.x] = groups;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {  // Hillis-Steele inclusive scan
-            int vb = 0, vi = 0, vg = 0;
-            if ((int)threadIdx.x >= o) { vb = sb[threadIdx.x - o]; vi = si[threadIdx.x - o]; vg = sg[threadIdx.x - o]; }
-            __syncthreads();
-            sb[threadIdx.x] += vb;
-            si[threadIdx.x] += vi;
-            sg[threadIdx.x] += vg;
-            __syncthreads();
-        }
-        if (l < nlist) {
-            bucket_off[l] = carry_b + sb[threadIdx.x] - c;
-            item_off[l] = carry_i + si[threadIdx.x] - items;
-            if (goff) goff[l] = carry_g + sg[threadIdx.x] - groups;
-            cursor[l] = 0;
-        }
-        __syncthreads();
-        if (threadIdx.x == 1023) { carry_b += sb[1023]; carry_i += si[1023]; carry_g += sg[1023]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        bucket_off[nlist] = carry_b;
-        item_off[nlist] = carry_i;
-        if (goff) goff[nlist] = carry_g;
-    }
-}
-
-__global__ void ivf_fill(const int64_t *__restrict__ probes, int64_t npairs, const int *__restrict__ list_len,
-                         int nlist, const int *__restrict__ bucket_off, int *__restrict__ cursor,
-                         int *__restrict__ bucket) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npairs) return;
-    const int64_t l = probes[i];
-    if (l < 0 || l >= nlist) return;
-    if (list_len[l] <= 0) return;
-    const int pos = atomicAdd(cursor + l, 1);
-    bucket[bucket_off[l] + pos] = (int)i;  // pair index = q * nprobe + p
-}
-
-// Single block: partial-list slots.  Pair i (= q·nprobe + p, probing list l) owns nch(l) consecutive
-// slots (one per row chunk of l; 0 if l is empty or not on this shard): slot_off = exclusive scan.
-// The slots of one query are therefore the contiguous range [slot_off[q·np], slot_off[(q+1)·np]).
-__device__ __forceinline__ void slot_scan_block(const int64_t *__restrict__ probes, int64_t npairs,
-                                                const int *__restrict__ list_len, int nlist, int *__restrict__ slot_off,
-                                                int *wsum) {
-    // Per round, wave w owns the contiguous pairs base + [1024w, 1024w + 1024) as 16 chunks of 64: lane
-    // i of chunk j is pair 64j + i, so the 16 probe loads and the 16 list-length gathers of a lane are
-    // coalesced across the wave and all independent (two memory latencies per round); each chunk is
-    // then scanned with shuffles and the 16 wave totals are combined in LDS.  (The first version gave
-    // each thread 32 consecutive pairs — strided loads — and a 10-step block scan: 43 µs at 32K pairs.)
-    constexpr int J = 16;  // (32 spilled at 1024 threads per block)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int64_t base = 0; base < npairs; base += 16 * 64 * J) {
-        const int64_t seg = base + (int64_t)wave * 64 * J;
-        int l[J];  // list ids fit 32 bits (64-bit ids spilled at 1024 threads per block)
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const int64_t i = seg + 64 * j + lane;
-            const int64_t pv = i < npairs ? probes[i] : -1;
-            l[j] = pv >= 0 && pv < nlist ? (int)pv : -1;
-        }
-        int v[J];
-#pragma unroll
-        for (int j = 0; j < J; ++j) v[j] = l[j] >= 0 ? ivf_nch(list_len[l[j]]) : 0;
-        int run = 0;
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            int x = v[j];
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(x, o);
-                if (lane >= o) x += t;
-            }
-            const int tot = __shfl(x, 63);
-            v[j] = run + x - v[j];  // exclusive offset inside the wave's segment
-            run += tot;
-        }
-        if (lane == 0) wsum[wave] = run;
-        __syncthreads();
-        int off = carry, total = 0;
-        for (int w2 = 0; w2 < 16; ++w2) {
-            const int t = wsum[w2];
-            off += w2 < wave ? t : 0;
-            total += t;
-        }
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const int64_t i = seg + 64 * j + lane;
-            if (i < npairs) slot_off[i] = off + v[j];
-        }
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) slot_off[npairs] = carry;
-}
-
-__global__ void __launch_bounds__(1024) ivf_slot_scan(const int64_t *__restrict__ probes, int64_t npairs,
-                                                      const int *__restrict__ list_len, int nlist,
-                                                      int *__restrict__ slot_off) {
-    __shared__ int wsum[16];
-    slot_scan_block(probes, npairs, list_len, nlist, slot_off, wsum);
-}
-
-// Query-major plan (default): three launches, two of them wide.
+// The plan, query-major: three launches, two of them wide.  Pair i (= q·nprobe + p, probing list l) owns nch(l)
+// consecutive partial-list slots (one per row chunk of l; 0 if l is empty or not on this shard), so the slots of
+// one query are the contiguous range [slot_off[q·np], slot_off[(q+1)·np]).
 //   ivf_count_q  — one wave per query: its pairs' list counts into ccnt (global atomics), the exclusive
 //                  prefix of their slot counts within the query into slot_off, the query's total to qtot
-//   ivf_plan_q   — one block: the list scans of ivf_plan (from ccnt, which it zeroes again for the next
-//                  batch), the exclusive scan of qtot (query slot bases), slot_off[npairs], and the batch's
-//                  other per-query state (the rerank's flag count, the scans' running bounds = +inf)
-//   ivf_fill_q   — one wave per query: slot_off += the query's base, bucket fill
-// (the list-major count / plan / slot scan / fill sequence kept a 1024-pair single block on one CU for
-// the slot scan: ≈ 55 µs of a 1024-query batch)
+//   ivf_plan_q   — one block: the list scans (from ccnt, which it zeroes again for the next batch: bucket_off[l] =
+//                  Σ_{<l} cnt, item_off[l] = Σ_{<l} ceil(cnt/group)·nch(l), one item per (query group, row chunk)
+//                  of each list, cursor[l] = 0, total items in item_off[nlist]), the exclusive scan of qtot (query
+//                  slot bases), slot_off[npairs], and the batch's other per-query state (the rerank's flag count,
+//                  the scans' running bounds = +inf)
+//   ivf_fill_q   — one wave per query: slot_off += the query's base, bucket fill (pair indices into per-list
+//                  buckets)
+// (measured and rejected: a list-major count / plan / slot scan / fill sequence, whose slot scan kept a 1024-pair
+// single block on one CU: ≈ 55 µs of a 1024-query batch)
 __global__ void __launch_bounds__(256) ivf_count_q(const int64_t *__restrict__ probes, int64_t nq, int nprobe,
                                                    const int *__restrict__ list_len, int nlist, int *__restrict__ ccnt,
                                                    int *__restrict__ slot_off, int *__restrict__ qtot) {
@@ -1158,54 +1030,31 @@ void launch_ivf_scan_bigk(const float *Q, int d, int metric, const float *codes,
 }
 
 // ---------------------------------------------------------------------------------------------
-// HIPANN_IVF_PLAN_SPLIT=1: the list-major count / plan / slot scan / fill sequence (A/B)
-bool ivf_plan_query_major() {
-    static const bool split = [] { const char *e = std::getenv("HIPANN_IVF_PLAN_SPLIT"); return e && std::atoi(e); }();
-    return !split;
-}
-
 void launch_ivf_plan(const int64_t *probes, int64_t nq, int nprobe, const int *list_len, int nlist, int group,
                      int *cnt, int *bucket_off, int *item_off, int *cursor, int *bucket, int *slot_off,
                      hipStream_t st, int *nflag_reset, unsigned *qbound, int *ccnt, int *qtot, bool counted,
                      int *ccnt_next, int *cursor_next, int *goff) {
+    HIPANN_REQUIRE(ccnt && qtot && ccnt_next && cursor_next, "ivf_plan: counts and cursors of both parities");
     const int64_t npairs = nq * nprobe;
-    if (ivf_plan_query_major() && ccnt && qtot) {
-        const unsigned gq = (unsigned)std::max<int64_t>(1, ceil_div(nq, (int64_t)4));
-        if (nq > 0 && !counted)  // counted: the coarse probe select already did this step (IvfPlanHook)
-            hipLaunchKernelGGL(ivf_count_q, dim3(gq), dim3(256), 0, st, probes, nq, nprobe, list_len, nlist, ccnt,
-                               slot_off, qtot);
-        // one launch (double-buffered counts and cursors) when the lists fit the block's LDS; HIPANN_IVF_PLANFILL=0
-        // keeps the two (A/B)
-        static const bool fused_env = [] { const char *e = std::getenv("HIPANN_IVF_PLANFILL"); return !e || std::atoi(e); }();
-        if (fused_env && ccnt_next && cursor_next && nlist <= kPlanFillMaxList && nq > 0) {
-            hipLaunchKernelGGL(ivf_planfill_q, dim3(gq), dim3(256), 0, st, probes, nq, nprobe, list_len, nlist, group,
-                               ccnt, ccnt_next, cursor, cursor_next, qtot, slot_off, npairs, cnt, bucket_off, item_off,
-                               bucket, nflag_reset, qbound, goff);
-            HIPANN_CHECK(hipGetLastError());
-            return;
-        }
-        hipLaunchKernelGGL(ivf_plan_q, dim3(1), dim3(1024), 0, st, ccnt, list_len, nlist, group, cnt, bucket_off,
-                           item_off, cursor, qtot, nq, npairs, slot_off, nflag_reset, qbound, goff);
-        if (nq > 0)
-            hipLaunchKernelGGL(ivf_fill_q, dim3(gq), dim3(256), 0, st, probes, nq, nprobe, list_len, nlist, qtot,
-                               bucket_off, cursor, bucket, slot_off);
-        if (cursor_next)  // the fused path expects the other parity's cursors at zero
-            HIPANN_CHECK(hipMemsetAsync(cursor_next, 0, sizeof(int) * kPlanCopies * (size_t)nlist, st));
+    const unsigned gq = (unsigned)std::max<int64_t>(1, ceil_div(nq, (int64_t)4));
+    if (nq > 0 && !counted)  // counted: the coarse probe select already did this step (IvfPlanHook)
+        hipLaunchKernelGGL(ivf_count_q, dim3(gq), dim3(256), 0, st, probes, nq, nprobe, list_len, nlist, ccnt,
+                           slot_off, qtot);
+    // one launch (double-buffered counts and cursors) when the lists fit the block's LDS
+    if (nlist <= kPlanFillMaxList && nq > 0) {
+        hipLaunchKernelGGL(ivf_planfill_q, dim3(gq), dim3(256), 0, st, probes, nq, nprobe, list_len, nlist, group,
+                           ccnt, ccnt_next, cursor, cursor_next, qtot, slot_off, npairs, cnt, bucket_off, item_off,
+                           bucket, nflag_reset, qbound, goff);
         HIPANN_CHECK(hipGetLastError());
         return;
     }
-    if (nflag_reset) HIPANN_CHECK(hipMemsetAsync(nflag_reset, 0, sizeof(int), st));
-    if (qbound) HIPANN_CHECK(hipMemsetD32Async((hipDeviceptr_t)qbound, 0xff800000, (size_t)nq, st));
-    HIPANN_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)nlist, st));
-    if (npairs > 0)
-        hipLaunchKernelGGL(ivf_count, dim3((unsigned)ceil_div(npairs, 256)), dim3(256), 0, st, probes, npairs, list_len,
-                           nlist, cnt);
-    hipLaunchKernelGGL(ivf_plan, dim3(1), dim3(1024), 0, st, cnt, list_len, nlist, group, bucket_off, item_off,
-                       cursor, goff);
-    hipLaunchKernelGGL(ivf_slot_scan, dim3(1), dim3(1024), 0, st, probes, npairs, list_len, nlist, slot_off);
-    if (npairs > 0)
-        hipLaunchKernelGGL(ivf_fill, dim3((unsigned)ceil_div(npairs, 256)), dim3(256), 0, st, probes, npairs, list_len,
-                           nlist, bucket_off, cursor, bucket);
+    hipLaunchKernelGGL(ivf_plan_q, dim3(1), dim3(1024), 0, st, ccnt, list_len, nlist, group, cnt, bucket_off,
+                       item_off, cursor, qtot, nq, npairs, slot_off, nflag_reset, qbound, goff);
+    if (nq > 0)
+        hipLaunchKernelGGL(ivf_fill_q, dim3(gq), dim3(256), 0, st, probes, nq, nprobe, list_len, nlist, qtot,
+                           bucket_off, cursor, bucket, slot_off);
+    // the fused path expects the other parity's cursors at zero
+    HIPANN_CHECK(hipMemsetAsync(cursor_next, 0, sizeof(int) * kPlanCopies * (size_t)nlist, st));
     HIPANN_CHECK(hipGetLastError());
 }
 

@@ -2,8 +2,8 @@
 //
 // Replaces the per-query GEMV-shaped distance + select of MetalIndexIVFFlat::search
 // (faiss-metal/src/MetalIndexIVFFlat.mm:122-256, norms stored with the lists at :305-318).  Same
-// work plan as the VALU kernels in ivf_kernels.hip (ivf_count / ivf_plan / ivf_fill, slots from
-// ivf_slot_scan): an item is (list ℓ, 2048-row chunk of ℓ, group of ≤ G of the queries probing ℓ),
+// work plan as the VALU kernels in ivf_kernels.hip (ivf_count_q / ivf_planfill_q, slots from
+// the per-query prefixes): an item is (list ℓ, 2048-row chunk of ℓ, group of ≤ G of the queries probing ℓ),
 // and every (query, probe, chunk) slot receives exactly one k-list.
 //
 // The block computes the item's (queries × rows) block of q·x with v_mfma_f32_16x16x4_f32 (exact

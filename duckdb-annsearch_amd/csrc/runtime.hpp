@@ -401,7 +401,7 @@ struct IvfShard {
     // queries of the last batch and the re-run's buffers
     float xmax2 = -1.f;
     DevBuf nflag, flagged, fq, fD, fI, coarse_save, tmpnorm;
-    DevBuf ccnt, qtot;             // query-major plan: per-list running counts (kept zero between batches), per-query slot totals
+    DevBuf ccnt, qtot;             // the plan: per-list running counts (kept zero between batches), per-query slot totals
     // the fused plan + fill (ivf_planfill_q): counts and fill cursors double-buffered by batch parity
     // ([2][nlist] each in ccnt / cursor2, zeroed at allocation; each batch zeroes the other parity's pair)
     DevBuf cursor2;
@@ -543,10 +543,10 @@ struct IvfPlanView {
     (p).list_off, (p).list_len, (p).cnt, (p).bucket_off, (p).item_off, (p).bucket, (p).slot_off, (p).nlist, (p).nprobe
 void launch_ivf_plan(const int64_t *probes, int64_t nq, int nprobe, const int *list_len, int nlist, int group,
                      int *cnt, int *bucket_off, int *item_off, int *cursor, int *bucket, int *slot_off,
-                     hipStream_t st, int *nflag_reset = nullptr, unsigned *qbound = nullptr, int *ccnt = nullptr,
-                     int *qtot = nullptr, bool counted = false, int *ccnt_next = nullptr, int *cursor_next = nullptr,
+                     hipStream_t st, int *nflag_reset, unsigned *qbound, int *ccnt, int *qtot, bool counted,
+                     int *ccnt_next, int *cursor_next,
                      // goff[l] = the query groups of the lists before l (nlist + 1 entries): list l's chunk-0 items
-                     int *goff = nullptr);
+                     int *goff);
 int64_t ivf_max_items(int64_t nq, int nprobe, int nlist, int max_nch, int64_t nrows, int group);
 int ivf_mfma_bf_group(int d, int np);
 bool ivf_mfma_bf_supported(int d, bool aligned16, int k, int np);
@@ -773,7 +773,6 @@ void launch_ivf_scan_mfma_bf(int np, const float *Q, int64_t nq, void *qsplit, c
                              int k, int64_t max_items, unsigned *qbound, float *pd, int *pi, hipStream_t st, int sub = 0);
 int ivf_group_size(int form, int d);  // queries per work item of the form's scan kernel
 int ivf_chunk_rows();
-bool ivf_plan_query_major();
 void launch_ivf_scan_bigk(const float *Q, int d, int metric, const float *codes, const IvfPlanView &plan,
                           const int64_t *probes, int64_t npairs, int64_t nslots, int k, float *pd, int *pi, hipStream_t st);
 size_t ivf_scan_smem_bytes();

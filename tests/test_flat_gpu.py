@@ -101,6 +101,20 @@ def test_flat_k_range(gpu, oracle, k):
         check_topk_parity(xb, xq[:nq], D, I, Do, Io, 0, min_exact=0.98)
 
 
+@pytest.mark.parametrize("nq,n,d", [(64, 2048, 64), (64, 2048, 96), (64, 2048, 98), (256, 32768, 64)])
+@pytest.mark.parametrize("metric", [0, 1])
+def test_flat_key_matrix_kernels(gpu, oracle, nq, n, d, metric):
+    """k = 100 takes the key-matrix path; the shapes are the smallest that pick each of its key kernels: 64 × 64 tiles
+    split over K with float4 loads (d = 64: an even count of 32-dim chunks), the unsplit 64 × 64 tiles (d = 96: an odd
+    count), the K-split tiles with scalar loads (d = 98: even, d % 4 != 0) and, at 2 × 256 = 512 tiles of 128 × 128,
+    the large-table key kernel."""
+    xb, xq = faiss_metal_case(n, nq, d)
+    ix = gpu.HipIndexFlat(d, metric, xb)
+    D, I = ix.search(xq, 100)
+    Do, Io = oracle.flat_search(xb, xq, 100, metric)
+    check_topk_parity(xb, xq, D, I, Do, Io, metric)
+
+
 def test_flat_k_greater_than_ntotal_pads(gpu):
     xb = np.array([[1, 0, 0], [0, 1, 0]], np.float32)
     for metric, pad in ((0, np.inf), (1, -np.inf)):

@@ -357,6 +357,32 @@ def test_ivf_large_nprobe(gpu, oracle, nprobe, k):
         check_topk_parity(xb, xq, D, I, Df, If_)
 
 
+_LIST_COUNT_CASES = {}
+
+
+def _list_count_case(gpu, oracle, nlist):
+    """One index and the oracle's inputs per list count, shared by the nprobe cases (4 rows per list on average)."""
+    if nlist not in _LIST_COUNT_CASES:
+        xb, xq = faiss_metal_case(4 * nlist, 64, 64)
+        _LIST_COUNT_CASES[nlist] = (xb, xq) + _ivf(gpu, xb, nlist, 8)
+    return _LIST_COUNT_CASES[nlist]
+
+
+@pytest.mark.parametrize("nprobe", [8, 72])
+@pytest.mark.parametrize("nlist", [256, 1024, 1025, 8193])
+def test_ivf_list_counts_select_and_plan_kernels(gpu, oracle, nlist, nprobe):
+    """The list counts at which the coarse select and the plan change kernels: 256 (the whole key row in one wave's
+    registers), 1024 (the narrowed wave; both carry the plan's count step), 1025 (the list select; the plan counts in
+    its own launch) and 8193, one past the fused plan's list table in LDS (the single-block plan and the fill in two
+    launches).  nprobe = 72 takes the coarse quantizer's k > 64 select at every list count."""
+    xb, xq, ix, (cen, off, ids, codes) = _list_count_case(gpu, oracle, nlist)
+    ix.nprobe = nprobe
+    D, I = ix.search(xq, 10)
+    Do, Io, Po = oracle.ivf_search(cen, off, ids, codes, xq, 10, nprobe)
+    assert np.array_equal(ix.last_probes(len(xq)), Po)
+    check_topk_parity(xb, xq, D, I, Do, Io)
+
+
 @pytest.mark.parametrize("form", [5, 6, 7])
 @pytest.mark.parametrize("metric", [0, 1])
 def test_ivf_exact_form_distances_are_direct(gpu, oracle, metric, form):
