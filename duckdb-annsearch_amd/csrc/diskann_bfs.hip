@@ -31,7 +31,6 @@
 
 #include <cfloat>
 #include <cstdint>
-#include <type_traits>
 
 namespace hipann {
 namespace {
@@ -41,9 +40,6 @@ namespace {
 #endif
 #ifndef HIPANN_BFS_PROF
 #define HIPANN_BFS_PROF 0  // tuning builds: per-phase shader-clock totals of wave 0 into stats[3..6]
-#endif
-#ifndef HIPANN_BFS_SPEC
-#define HIPANN_BFS_SPEC 0  // speculative row / visited-word fetch of the next expansion (measured slower, off)
 #endif
 #ifndef HIPANN_BFS_RV
 #define HIPANN_BFS_RV 128  // VGPRs of row data in flight per lane (rows_in_flight)
@@ -94,13 +90,10 @@ __device__ __forceinline__ unsigned up1_u(unsigned v, int) {
 
 // Row chunks: 8 SQ8 codes (8 B; 1536 codes = 3 chunks per lane exactly) or 4 floats (16 B); lane `l`,
 // chunk t covers chunk index l + 64t.
-#ifndef HIPANN_BFS_SQ8_CHUNK
-#define HIPANN_BFS_SQ8_CHUNK 8  // bytes of SQ8 codes per lane-load (8: global_load_dwordx2, 16: dwordx4)
-#endif
 template <bool SQ8> struct Fmt;
 template <> struct Fmt<true> {
-    static constexpr int kDims = HIPANN_BFS_SQ8_CHUNK;
-    using Chunk = typename std::conditional<HIPANN_BFS_SQ8_CHUNK == 16, uint4, uint2>::type;
+    static constexpr int kDims = 8;
+    using Chunk = uint2;
 };
 template <> struct Fmt<false> {
     static constexpr int kDims = 4;
@@ -112,17 +105,6 @@ constexpr int rows_in_flight(int vg) {
     int p = 1;
     while (p < 32 && 2 * p * vg <= HIPANN_BFS_RV) p *= 2;
     return p;
-}
-// Groups of pg rows in flight at once: HIPANN_BFS_RVG VGPRs of row data (0: one group).  At
-// 1M × 1536 SQ8 a step has ≈46 fresh neighbours, 23 per wave: 3 groups of 8 (144 VGPRs) load them in
-// one round where one group of 16 needed two.
-#ifndef HIPANN_BFS_RVG
-#define HIPANN_BFS_RVG 0
-#endif
-constexpr int groups_in_flight(int vg, int pg) {
-    int g = 1;
-    while ((g + 1) * pg * vg <= HIPANN_BFS_RVG) ++g;
-    return g;
 }
 
 template <int S>
@@ -247,9 +229,10 @@ diskann_bfs(const float *__restrict__ Qs, int nq, int d, const uint8_t *__restri
     constexpr int DC = Fmt<SQ8>::kDims;
     using Chunk = typename Fmt<SQ8>::Chunk;
     constexpr int CB = (int)sizeof(Chunk);
-    // rows in flight per wave: P = NG groups of PG (a power of two, one reduce-scatter per group)
+    // rows in flight per wave: P = NG groups of PG (a power of two, one reduce-scatter per group).  One group; the
+    // loop over groups stays in dist_phase because the compiler orders 24 of the 36 kernels otherwise without it.
     constexpr int PG = rows_in_flight(T * CB / 4);
-    constexpr int NG = groups_in_flight(T * CB / 4, PG);
+    constexpr int NG = 1;
     constexpr int P = PG * NG;
     constexpr int LP = PG >= 32 ? 5 : PG >= 16 ? 4 : PG >= 8 ? 3 : PG >= 4 ? 2 : PG >= 2 ? 1 : 0;
     __shared__ uint32_t s_ids[64];  // this step's fresh neighbours, in neighbour order
@@ -343,8 +326,6 @@ diskann_bfs(const float *__restrict__ Qs, int nq, int d, const uint8_t *__restri
         }
         return acc[0] + acc[1];
     };
-    // Distances of the step's fresh rows s_ids[0, cnt) into s_dist: wave w takes a contiguous share,
-    // P rows in flight at a time (rows past the share re-load its last row; their sums are dropped).
     // Distances of the step's fresh rows s_ids[0, cnt) into s_dist: wave w takes a contiguous share,
     // P rows in flight at a time (rows past the share re-load its last row; their sums are dropped).
     // (Pipelining the next round's loads behind this round's arithmetic needs P = 8 to fit 2 waves
@@ -447,32 +428,9 @@ diskann_bfs(const float *__restrict__ Qs, int nq, int d, const uint8_t *__restri
     int flag = 0;
     unsigned long long evals = 0;
     int steps = 0;
-    // Speculated next expansion (wave 0).  The adjacency row and the visited words of the entry most
-    // likely to be popped next are fetched while the current step's rows are gathered or inserted, so a
-    // correct guess starts the next step's gather without the two dependent round trips (adjacency,
-    // then visited).  A guess never changes what is computed: it is used only when its id equals the
-    // popped one, its visited words were read after every mark of earlier steps (only this workgroup
-    // writes this bitmap), and each mark it implies is confirmed by the returned old word (a
-    // mismatch flags the query for the host path).
-    //   sp_state 0: nothing; 1: sp_nb / sp_md loaded; 2: sp_w (visited word of lane's neighbour) too.
-    unsigned sp_id = kNone;
-    uint32_t sp_nb = kNone, sp_w = 0;
-    bool sp_md = true;
-    int sp_state = 0;
-    unsigned long long sp_hits = 0;
-    uint64_t mark_lanes = 0;    // this step's speculative marks: lanes whose old word must be unmarked
-    uint32_t mark_old = 0, mark_bit = 0;
     auto adj_row = [&](unsigned id, uint32_t &nb_out, bool &md_out) {
         nb_out = lane < R ? adj[(size_t)id * R + lane] : kNone;
         md_out = dupw == nullptr || ((dupw[id >> 5] >> (id & 31)) & 1u);
-    };
-    // visited words of a row's valid neighbours: device-scope loads, which bypass the CU's L1 and read
-    // L2, where the marks (atomics) land
-    auto visited_words = [&](uint32_t nbv) -> uint32_t {
-        const uint64_t s = __ballot(lane < R && nbv == kNone);
-        const int f = s ? __ffsll((unsigned long long)s) - 1 : R;
-        return (lane < f && nbv < N) ? __hip_atomic_load(vis + (nbv >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                     : 0u;
     };
 
     const uint64_t lanes_below = (1ull << lane) - 1;  // lane 63: all lower lanes (no overflow)
@@ -539,10 +497,6 @@ diskann_bfs(const float *__restrict__ Qs, int nq, int d, const uint8_t *__restri
       if (wave == 0) {
         while (!flag) {
         steps++;
-        if (sp_state == 1) {  // a guessed row arrived during the inserts: its visited words now
-            sp_w = visited_words(sp_nb);
-            sp_state = 2;
-        }
         const float thr = len >= L ? res.get_d(L - 1) : __builtin_inff();
         uint64_t best = ~0ull;
 #pragma unroll
@@ -593,16 +547,11 @@ diskann_bfs(const float *__restrict__ Qs, int nq, int d, const uint8_t *__restri
         }
         BFS_T(0);
         // expand: neighbours up to the first sentinel, ids < N, visited insert in order
-        const bool hit = HIPANN_BFS_SPEC && sp_state != 0 && cid == sp_id;
-        const bool hit_w = hit && sp_state == 2;
-        sp_hits += hit ? 1 : 0;
         uint32_t nb;
         // rows flagged at registration as holding a repeated id before their first sentinel (none in
         // a Vamana graph) take the dedupe below; every other row skips it
         bool maydup;
-        if (hit) { nb = sp_nb; maydup = sp_md; }
-        else adj_row(cid, nb, maydup);
-        sp_state = 0;
+        adj_row(cid, nb, maydup);
         const uint64_t sent = __ballot(lane < R && nb == kNone);
         BFS_T(1);
         const int first = sent ? __ffsll((unsigned long long)sent) - 1 : R;
@@ -625,17 +574,7 @@ diskann_bfs(const float *__restrict__ Qs, int nq, int d, const uint8_t *__restri
         BFS_T(2);
         bool fresh = false;
         const unsigned bit = 1u << (nb & 31);
-        mark_lanes = 0;
-        if (hit_w) {
-            // visited words read after every earlier mark: fresh is decided now; the marks go out
-            // and their old words are checked after the gather
-            fresh = valid && !dup && !(sp_w & bit);
-            if (fresh) mark_old = atomicOr(vis + (nb >> 5), bit);
-            mark_bit = bit;
-            mark_lanes = __ballot(fresh);
-        } else if (valid && !dup) {
-            fresh = !(atomicOr(vis + (nb >> 5), bit) & bit);
-        }
+        if (valid && !dup) fresh = !(atomicOr(vis + (nb >> 5), bit) & bit);
         const uint64_t m = __ballot(fresh);
         BFS_T(3);
         if (!m) continue;
@@ -653,9 +592,6 @@ diskann_bfs(const float *__restrict__ Qs, int nq, int d, const uint8_t *__restri
       __syncthreads();
       if (wave == 0) {
         BFS_T(4);
-        // the speculative marks' old words: each must have been unmarked, as the guess assumed
-        if (__ballot(((mark_lanes >> lane) & 1ull) && (mark_old & mark_bit))) flag = 1;
-        mark_lanes = 0;
         // insert_result in neighbour order
         const float dd = lane < cnt ? s_dist[lane] : 0.f;
         const unsigned nbr = lane < cnt ? s_ids[lane] : kNone;
@@ -664,31 +600,6 @@ diskann_bfs(const float *__restrict__ Qs, int nq, int d, const uint8_t *__restri
         const bool full = len >= L;
         const float thr0 = full ? res.get_d(len - 1) : 0.f;
         uint64_t am = __ballot(lane < cnt && (!full || dd < thr0));
-        if (HIPANN_BFS_SPEC) {
-            // the next pop is almost always the smallest of the unexpanded entries, the spill list and the
-            // admitted candidates (a superset of what the inserts leave poppable): fetch its adjacency row
-            // behind the inserts; its visited words go out at the top of the next step
-            uint64_t b = ~0ull;
-#pragma unroll
-            for (int s = 0; s < S; ++s) {
-                const int e = s * 64 + lane;
-                if (e < len && !(res.id[s] & kExpanded)) {
-                    const uint64_t c = ((uint64_t)ford(res.d[s]) << 32) | res.id[s];
-                    b = c < b ? c : b;
-                }
-            }
-            if (lane < nspill) b = spill < b ? spill : b;
-            if ((am >> lane) & 1ull) {
-                const uint64_t c = ((uint64_t)ford(dd) << 32) | nbr;
-                b = c < b ? c : b;
-            }
-            b = wmin_u64(b);
-            if (b != ~0ull) {
-                sp_id = (unsigned)b;
-                adj_row(sp_id, sp_nb, sp_md);
-                sp_state = 1;
-            }
-        }
         // Many admitted candidates and no equal / non-finite distance anywhere: the inserts in neighbour
         // order end in exactly the first L of the sorted union (each binary search lands on the unique
         // insertion point; a candidate rejected at its turn already had L smaller entries ahead of it;
@@ -749,7 +660,6 @@ diskann_bfs(const float *__restrict__ Qs, int nq, int d, const uint8_t *__restri
         if (!flag) atomicAdd(stats + 0, evals);
         atomicMax(stats + 1, (unsigned long long)steps);
         atomicAdd(stats + 2, (unsigned long long)steps);
-        atomicAdd(stats + 9, sp_hits);
     }
 }
 
@@ -779,7 +689,7 @@ void launch_diskann_dup_rows(const uint32_t *adj, int R, int64_t n, uint32_t *du
 
 // S: result slots per lane (L ≤ 64·S); T: row chunks per lane (8 codes or 4 floats each)
 bool diskann_bfs_supported(int d, int fmt, int R, int n_ep, int L, uint32_t N) {
-    const int dc = fmt == 1 ? HIPANN_BFS_SQ8_CHUNK : 4;
+    const int dc = fmt == 1 ? Fmt<true>::kDims : Fmt<false>::kDims;
     return d > 0 && d % dc == 0 && d <= 64 * dc * (fmt == 1 ? 4 : 8) && R > 0 && R <= 64 && n_ep >= 0 &&
            n_ep <= 64 && L >= 1 && L <= 256 && N <= 0x7fffffffu;
 }
@@ -790,7 +700,7 @@ void launch_diskann_bfs(const float *Q, int nq, int d, int fmt, const void *data
                         unsigned long long *stats, hipStream_t st) {
     if (nq <= 0) return;
     HIPANN_REQUIRE(diskann_bfs_supported(d, fmt, R, n_ep, L, N), "diskann_bfs: unsupported shape");
-    const int dc = fmt == 1 ? HIPANN_BFS_SQ8_CHUNK : 4;
+    const int dc = fmt == 1 ? Fmt<true>::kDims : Fmt<false>::kDims;
     const int chunks = (d / dc + 63) / 64;  // row chunks per lane
     const bool s2 = L <= 128;
     const uint8_t *x = static_cast<const uint8_t *>(data);

@@ -1,6 +1,6 @@
-// diskann_db.hpp — (internal) what diskann.hip (bridge, host BFS, DB registry, resident search) and diskann_graph.cpp
-// (graph build, add, remove, prune) share on the host: the HBM-resident DB, the resident search, and the C ABI's
-// error epilogue.
+// diskann_db.hpp — (internal) what diskann.hip (bridge, launchers, DB registry, resident search), diskann_host_bfs.cpp
+// (the lock-step host BFS) and diskann_graph.cpp (graph build, add, remove, prune) share on the host: the HBM-resident
+// DB, the id-gather launcher, the two searches, and the C ABI's error epilogue.
 #pragma once
 #include "../../include/hip_diskann_bridge.h"
 #include "common.hpp"
@@ -28,9 +28,6 @@ struct DiskDB {
     int R = 0;
     DevBuf adj_dev, dupw, visited, flags, bstats, eps_dev;
     DevBuf vbits;  // host BFS: the queries' visited bits on the device (one bit per row and query)
-    DevBuf bfs_ctr;   // host BFS: per group, the id-gather launch's finished-block count (zero between launches)
-    HostBuf bfs_tok;  // host BFS: per group, the token word the launch posts when it is done (polled)
-    unsigned bfs_seq = 0;
     std::vector<uint32_t> adj_host;
     // diskann_hip_build_graph: adj_dev is ahead of adj_host (the resident search refreshes the host copy before it
     // re-runs a flagged query on it); the last build's seconds in search / out-edge prunes / back-edges
@@ -49,6 +46,18 @@ struct DiskDB {
 void resident_search_locked(DiskDB *db, const uint32_t *eps, int n_ep, const float *queries_dev, int nq, int k,
                             int l_search, int metric, int64_t *out_ids_dev, float *out_d_dev, int64_t *stats,
                             hipStream_t st);
+
+// The id-gather launch (diskann.hip): out[i] = the distance of query m[i] to row ids[i] of the DB, for total_n
+// candidates; an id ≥ db.n is an empty slot and leaves out[i] alone.  With vbits (the host BFS's visited sets on the
+// device, vwords words per query) a candidate whose bit is already set comes back as kVisitedBits instead.
+void launch_ids(DiskDB &db, const float *q, const unsigned *ids, const unsigned *m, int total_n, int metric,
+                float *out, hipStream_t st, unsigned *vbits = nullptr, int64_t vwords = 0);
+
+// Host-driven lock-step BFS (diskann_host_bfs.cpp; the reference's structure: host state, one id-gather launch per
+// step) over the host adjacency adj (db->n × R): the body of diskann_hip_search_batch, whose outputs and stats it
+// fills, and the fallback of the resident search for flagged queries.  The caller holds db->mu and the device.
+void host_bfs(DiskDB *db, const uint32_t *adj, int R, const uint32_t *eps, int n_ep, const float *queries, int nq,
+              int k, int l_search, int metric, int64_t *out_ids, float *out_d, int64_t *stats);
 
 inline void set_err(char *buf, int len, const char *msg) {
     if (!buf || len <= 0) return;

@@ -329,7 +329,7 @@ int64_t diskann_hip_add_rows(void *h, const float *rows, int64_t m, int l_build,
             const int64_t per = std::max<int64_t>(1, std::min<int64_t>(bmax, ((int64_t)2 << 30) / (vwords * 4)));
             db->visited.ensure((size_t)per * vwords * 4, dev);
             db->flags.ensure((size_t)bmax * 4, dev);
-            db->bstats.ensure(80, dev);
+            db->bstats.ensure(72, dev);
             db->eps_dev.ensure(4, dev);
         }
         db->adj_host.reserve((size_t)n1 * R);

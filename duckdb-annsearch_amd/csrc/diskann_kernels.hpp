@@ -1,5 +1,5 @@
 // diskann_kernels.hpp — (internal) the one declaration of every launcher of diskann_bfs.hip, diskann_build.hip,
-// diskann_add.hip and diskann_remove.hip, and the two items those files and diskann.hip share on the device.  Every
+// diskann_add.hip and diskann_remove.hip, and the items those files, diskann.hip and diskann_host_bfs.cpp share.  Every
 // one of them includes it, so a definition that disagrees with its callers does not compile.
 #pragma once
 #include "common.hpp"
@@ -7,6 +7,9 @@
 namespace hipann {
 
 constexpr uint32_t kNone = 0xffffffffu;  // the empty adjacency slot / no id
+// what the id-gather kernels (diskann.hip) write for a candidate the query had already visited, and the host BFS
+// (diskann_host_bfs.cpp) drops: a NaN payload no distance arithmetic produces
+constexpr unsigned kVisitedBits = 0x7fc0deadu;
 
 // wave64 butterfly sum, strides 32 … 1 in this order: the summation order is part of every exact-reference contract
 __device__ __forceinline__ float wave_sum(float s) {

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from _bfs_cases import _ragged_graph
+from _host_bfs_cases import ragged_case, ragged_sq8
 from _data import mt19937_uniform
 
 pytestmark = pytest.mark.gpu
@@ -217,25 +218,12 @@ def test_bfs_many_queries_parallel_host(gpu, oracle, metric, fmt):
     """nq = 600 spreads the host BFS phases over worker threads (fixed per-query slot layout); a ragged
     graph (u32::MAX padding after a varying degree, out-of-range ids, duplicate neighbours) and
     duplicate entry points exercise the visited/skip rules of disk_provider.rs:556-577."""
-    rng = np.random.default_rng(11)
-    n, d, R = 4000, 48, 24
-    x = rng.standard_normal((n, d)).astype(np.float32)
-    qs = (x[rng.integers(0, n, 600)] + 0.1 * rng.standard_normal((600, d))).astype(np.float32)
-    _, nn = oracle.flat_search(x, x, R - 4 + 1, 0)
-    adj = np.full((n, R), 0xFFFFFFFF, np.uint32)
-    adj[:, : R - 4] = nn[:, 1:]
-    adj[:, R - 4: R - 2] = rng.integers(0, n, (n, 2))
-    adj[::7, R - 2] = n + 5          # out of range: skipped, not a sentinel
-    adj[::5, 3] = adj[::5, 2]        # duplicate neighbour
-    deg = rng.integers(R // 2, R + 1, n)
-    adj[np.arange(R)[None, :] >= deg[:, None]] = 0xFFFFFFFF
-    eps = [17, 17, 2500]
+    x, qs, adj, eps = ragged_case()
     if fmt == 0:
         db = gpu.DiskannDeviceDB(x, 0)
         kw = dict(vecs=x)
     else:
-        mins, scale = oracle.sq8_train(x)
-        codes = oracle.sq8_encode(x, mins, scale)
+        codes, mins, scale = ragged_sq8()
         db = gpu.DiskannDeviceDB(codes, 1, mins, scale)
         kw = dict(codes=codes, mins=mins, scale=scale)
     ids, dists, st = db.search_batch(adj, eps, qs, 10, 40, metric)
