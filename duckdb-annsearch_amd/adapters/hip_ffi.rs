@@ -155,6 +155,20 @@ extern "C" {
         err_buf: *mut core::ffi::c_char,
         err_len: i32,
     ) -> i32;
+    fn diskann_hip_medoid(db: *mut core::ffi::c_void, row_out: *mut u32, err_buf: *mut core::ffi::c_char, err_len: i32) -> i32;
+    fn diskann_hip_quantize_sq8(
+        db: *mut core::ffi::c_void,
+        err_buf: *mut core::ffi::c_char,
+        err_len: i32,
+    ) -> *mut core::ffi::c_void;
+    fn diskann_hip_export_sq8(
+        db: *mut core::ffi::c_void,
+        codes: *mut core::ffi::c_void,
+        sq8_min: *mut f32,
+        sq8_scale: *mut f32,
+        err_buf: *mut core::ffi::c_char,
+        err_len: i32,
+    ) -> i32;
 }
 
 /// Cached availability: -1 = unchecked, 0 = unavailable, 1 = available (metal_ffi.rs:33-34).
@@ -606,6 +620,56 @@ impl HipDiskDb {
             return None;
         }
         Some(out)
+    }
+
+    /// The row nearest the mean of this fp32 DB's rows, on the GPU — the `medoid(&rows_flat, n, dim)` of
+    /// the CREATE INDEX path over the rows the handle already holds: fp64 mean and distances, smallest (distance, id).
+    /// None ⇒ an SQ8 handle, no rows, or the device failed; the caller computes it on the CPU.
+    pub fn medoid(&self) -> Option<u32> {
+        let mut row = 0u32;
+        let mut err = [0 as core::ffi::c_char; 256];
+        let ret = unsafe { diskann_hip_medoid(self.h, &mut row, err.as_mut_ptr(), err.len() as i32) };
+        if ret != 0 {
+            return None;
+        }
+        Some(row)
+    }
+
+    /// Provider::quantize_sq8 (provider.rs:161-210) of this fp32 DB's rows on the GPU: a new SQ8 handle
+    /// with the codes, min / scale per dimension and a device-side copy of the registered graph, ready for
+    /// search_batch_resident — no read-back of the rows, no CPU codec, no second upload of the adjacency.  This handle
+    /// is not changed; call again after add_rows / remove_ids (the codec's min / max are global).  None ⇒ an SQ8
+    /// source, no rows, a non-finite value, or the device failed.
+    pub fn quantize_sq8(&self) -> Option<HipDiskDb> {
+        let mut err = [0 as core::ffi::c_char; 256];
+        let h = unsafe { diskann_hip_quantize_sq8(self.h, err.as_mut_ptr(), err.len() as i32) };
+        if h.is_null() {
+            return None;
+        }
+        Some(HipDiskDb { h, n: self.n, dim: self.dim, degree: AtomicUsize::new(self.degree.load(Ordering::Acquire)) })
+    }
+
+    /// (codes n × dim, min, scale) of this SQ8 handle back on the host, for the `SQ8\0` trailer
+    /// (index_manager.rs:513-533).  None ⇒ an fp32 handle or the device failed.
+    pub fn export_sq8(&self) -> Option<(Vec<u8>, Vec<f32>, Vec<f32>)> {
+        let mut codes = vec![0u8; self.n.checked_mul(self.dim)?];
+        let mut min = vec![0f32; self.dim];
+        let mut scale = vec![0f32; self.dim];
+        let mut err = [0 as core::ffi::c_char; 256];
+        let ret = unsafe {
+            diskann_hip_export_sq8(
+                self.h,
+                codes.as_mut_ptr() as *mut core::ffi::c_void,
+                min.as_mut_ptr(),
+                scale.as_mut_ptr(),
+                err.as_mut_ptr(),
+                err.len() as i32,
+            )
+        };
+        if ret != 0 {
+            return None;
+        }
+        Some((codes, min, scale))
     }
 
     /// prune() of DESIGN §6 for `targets.len()` nodes over `pools` (targets.len() × pool_cap ids, u32::MAX padding).

@@ -294,6 +294,23 @@ void launch_ids(DiskDB &db, const float *q, const unsigned *ids, const unsigned 
     HIPANN_CHECK(hipGetLastError());
 }
 
+// (described where it is declared, diskann_db.hpp; the copies are from pageable memory, so the vectors may go once
+// the calls return)
+void sq8_fill_decode_tables(DiskDB &db, const float *sq8_min, const float *sq8_scale, hipStream_t st) {
+    const int dim = db.dim;
+    std::vector<float> ab((size_t)dim * 2), abr((size_t)dim * 2);
+    for (int j = 0; j < dim; ++j) {
+        ab[2 * j] = sq8_scale[j] / 255.0f;
+        ab[2 * j + 1] = sq8_min[j];
+        abr[2 * j] = sq8_scale[j];
+        abr[2 * j + 1] = sq8_min[j];
+    }
+    db.ab.ensure(ab.size() * 4, db.device);
+    db.ab_raw.ensure(abr.size() * 4, db.device);
+    HIPANN_CHECK(hipMemcpyAsync(db.ab.p, ab.data(), ab.size() * 4, hipMemcpyHostToDevice, st));
+    HIPANN_CHECK(hipMemcpyAsync(db.ab_raw.p, abr.data(), abr.size() * 4, hipMemcpyHostToDevice, st));
+}
+
 // (described where it is declared, diskann_db.hpp)
 void resident_search_locked(DiskDB *db, const uint32_t *eps, int n_ep, const float *queries_dev, int nq, int k,
                             int l_search, int metric, int64_t *out_ids_dev, float *out_d_dev, int64_t *stats,
@@ -495,21 +512,7 @@ void *diskann_hip_register_db(const void *data, int64_t n, int dim, int fmt, con
         const size_t bytes = (size_t)n * dim * (fmt == DISKANN_HIP_FMT_F32 ? 4 : 1);
         db->data.ensure(bytes + 16, db->device);
         if (bytes) HIPANN_CHECK(hipMemcpyAsync(db->data.p, data, bytes, hipMemcpyHostToDevice, db->stream));
-        if (fmt == DISKANN_HIP_FMT_SQ8) {
-            // ab: (scale/255, min) for the traversal's fused form; ab_raw: (scale, min) for the id-gather
-            // kernels' exact decode
-            std::vector<float> ab((size_t)dim * 2), abr((size_t)dim * 2);
-            for (int j = 0; j < dim; ++j) {
-                ab[2 * j] = sq8_scale[j] / 255.0f;
-                ab[2 * j + 1] = sq8_min[j];
-                abr[2 * j] = sq8_scale[j];
-                abr[2 * j + 1] = sq8_min[j];
-            }
-            db->ab.ensure(ab.size() * 4, db->device);
-            db->ab_raw.ensure(abr.size() * 4, db->device);
-            HIPANN_CHECK(hipMemcpyAsync(db->ab.p, ab.data(), ab.size() * 4, hipMemcpyHostToDevice, db->stream));
-            HIPANN_CHECK(hipMemcpyAsync(db->ab_raw.p, abr.data(), abr.size() * 4, hipMemcpyHostToDevice, db->stream));
-        }
+        if (fmt == DISKANN_HIP_FMT_SQ8) sq8_fill_decode_tables(*db, sq8_min, sq8_scale, db->stream);
         HIPANN_CHECK(hipStreamSynchronize(db->stream));
         return db.release();
     } catch (...) {

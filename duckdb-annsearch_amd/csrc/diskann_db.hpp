@@ -1,6 +1,6 @@
 // diskann_db.hpp — (internal) what diskann.hip (bridge, launchers, DB registry, resident search), diskann_host_bfs.cpp
-// (the lock-step host BFS) and diskann_graph.cpp (graph build, add, remove, prune) share on the host: the HBM-resident
-// DB, the id-gather launcher, the two searches, and the C ABI's error epilogue.
+// (the lock-step host BFS), diskann_graph.cpp (graph build, add, remove, prune) and diskann_quantize.cpp (medoid, SQ8 copy)
+// share on the host: the HBM-resident DB, the id-gather launcher, the two searches, and the C ABI's error epilogue.
 #pragma once
 #include "../../include/hip_diskann_bridge.h"
 #include "common.hpp"
@@ -35,6 +35,7 @@ struct DiskDB {
     double build_s[3] = {0.0, 0.0, 0.0};
     double remove_s[3] = {0.0, 0.0, 0.0};  // the last diskann_hip_remove_ids: pool build, prune, compact
     double add_s[4] = {0.0, 0.0, 0.0, 0.0};  // the last diskann_hip_add_rows: searches, mates, out-edge prunes, back-edges
+    double quantize_s[3] = {0.0, 0.0, 0.0};  // the last diskann_hip_quantize_sq8 from this DB: statistics, encode, rest
     ~DiskDB() {
         if (stream) { DeviceGuard g(device); (void)hipStreamDestroy(stream); }
     }
@@ -58,6 +59,20 @@ void launch_ids(DiskDB &db, const float *q, const unsigned *ids, const unsigned 
 // fills, and the fallback of the resident search for flagged queries.  The caller holds db->mu and the device.
 void host_bfs(DiskDB *db, const uint32_t *adj, int R, const uint32_t *eps, int n_ep, const float *queries, int nq,
               int k, int l_search, int metric, int64_t *out_ids, float *out_d, int64_t *stats);
+
+// An SQ8 DB's decode tables from the codec's per-dimension min / scale (host, db.dim each), queued on st: ab =
+// (scale/255, min), the traversal's fused form, and ab_raw = (scale, min), the id-gather kernels' exact decode.  The
+// one place they are computed: diskann_hip_register_db and diskann_hip_quantize_sq8 fill a handle through it.
+void sq8_fill_decode_tables(DiskDB &db, const float *sq8_min, const float *sq8_scale, hipStream_t st);
+
+// the last call's phase clocks (DiskDB::build_s / add_s / remove_s / quantize_s) for the *_phase_seconds entry points
+template <int N> int phase_seconds(void *h, double *seconds, double (DiskDB::*phases)[N]) {
+    if (!h || !seconds) return -1;
+    auto *db = static_cast<DiskDB *>(h);
+    std::lock_guard<std::mutex> lk(db->mu);
+    for (int i = 0; i < N; ++i) seconds[i] = (db->*phases)[i];
+    return 0;
+}
 
 inline void set_err(char *buf, int len, const char *msg) {
     if (!buf || len <= 0) return;

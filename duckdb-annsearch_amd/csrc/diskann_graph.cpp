@@ -166,15 +166,6 @@ struct VamanaInsert {
     }
 };
 
-// the last call's phase clocks (DiskDB::build_s / add_s / remove_s) for the *_phase_seconds entry points
-template <int N> int phase_seconds(void *h, double *seconds, double (DiskDB::*phases)[N]) {
-    if (!h || !seconds) return -1;
-    auto *db = static_cast<DiskDB *>(h);
-    std::lock_guard<std::mutex> lk(db->mu);
-    for (int i = 0; i < N; ++i) seconds[i] = (db->*phases)[i];
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {

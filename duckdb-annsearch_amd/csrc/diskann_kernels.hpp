@@ -1,6 +1,7 @@
 // diskann_kernels.hpp — (internal) the one declaration of every launcher of diskann_bfs.hip, diskann_build.hip,
-// diskann_add.hip and diskann_remove.hip, and the items those files, diskann.hip and diskann_host_bfs.cpp share.  Every
-// one of them includes it, so a definition that disagrees with its callers does not compile.
+// diskann_add.hip, diskann_remove.hip and diskann_sq8.hip, and the items those files, diskann.hip and
+// diskann_host_bfs.cpp share.  Every one of them includes it, so a definition that disagrees with its callers does not
+// compile.
 #pragma once
 #include "common.hpp"
 
@@ -76,5 +77,17 @@ void launch_diskann_remove_nearest(const float *x, int d, int64_t n, const uint3
                                    unsigned long long *best, hipStream_t st);
 void launch_diskann_remove_compact_adj(const uint32_t *adj, int R, int64_t n, const uint32_t *bits,
                                        const uint32_t *wpre, uint32_t *out, hipStream_t st);
+
+// ---- diskann_sq8.hip ----
+// The column statistics split the rows into slabs of this many rows, one block each: a function of n alone, so the
+// order of every fp64 addition is fixed.
+constexpr int kSq8SlabRows = 512;
+int64_t sq8_stat_slabs(int64_t n);
+int medoid_nearest_blocks(int64_t n);
+void launch_sq8_col_stats(const float *x, int64_t n, int d, bool minmax, bool sum, float *pmin, float *pmax,
+                          double *psum, float *ms, double *mean, hipStream_t st);
+void launch_sq8_encode(const float *x, int64_t n, int d, const float *ms, uint8_t *out, hipStream_t st);
+void launch_medoid_nearest(const float *x, int64_t n, int d, const double *mean, double *bd, uint32_t *bi,
+                           uint32_t *out, hipStream_t st);
 
 }  // namespace hipann

@@ -166,6 +166,10 @@ def lib() -> C.CDLL:
                                       i64p, cp, i32], i64),
             "diskann_hip_batch_mates": ([vp, i64, i32, i32, C.POINTER(C.c_uint32), cp, i32], i32),
             "diskann_hip_add_phase_seconds": ([vp, C.POINTER(C.c_double)], i32),
+            "diskann_hip_medoid": ([vp, C.POINTER(C.c_uint32), cp, i32], i32),
+            "diskann_hip_quantize_sq8": ([vp, cp, i32], vp),
+            "diskann_hip_export_sq8": ([vp, vp, f, f, cp, i32], i32),
+            "diskann_hip_quantize_phase_seconds": ([vp, C.POINTER(C.c_double)], i32),
         }
         missing = [name for name in sig if not hasattr(L, name)]
         if missing:
@@ -761,6 +765,14 @@ class DiskannDeviceDB:
         self.n, self.dim, self.fmt = n, dim, fmt
         self.R = 0  # degree of the registered graph (0: none)
 
+    @classmethod
+    def _from_handle(cls, h, n: int, dim: int, fmt: int, R: int) -> "DiskannDeviceDB":
+        """Wrap a handle the library made itself (quantize_sq8); the object owns it."""
+        db = cls.__new__(cls)
+        db._h = C.c_void_p(h)
+        db.n, db.dim, db.fmt, db.R = n, dim, fmt, R
+        return db
+
     def close(self):
         if getattr(self, "_h", None):
             lib().diskann_hip_release_db(self._h)
@@ -886,6 +898,40 @@ class DiskannDeviceDB:
                      "back_prunes": int(stats[3]), "host_requeries": int(stats[4]), "pools_truncated": int(stats[5]),
                      "unreachable": int(stats[6]), "mate_ids": int(stats[7]), "search_s": sec[0], "mates_s": sec[1],
                      "out_prune_s": sec[2], "back_edge_s": sec[3]}
+
+    def medoid(self) -> int:
+        """The row nearest the mean of this fp32 DB's rows, computed on the GPU: the module-level
+        ``medoid`` is its spec — fp64 mean and distances, the smallest (distance, index)."""
+        row = C.c_uint32(0)
+        eb = _err()
+        _check(lib().diskann_hip_medoid(self._h, C.byref(row), eb, 1024), eb)
+        return int(row.value)
+
+    def quantize_sq8(self) -> "DiskannDeviceDB":
+        """Provider::quantize_sq8 of this fp32 DB's rows on the GPU (DESIGN §6.4): a new SQ8 DiskannDeviceDB with the
+        codes, the per-dimension min / scale and a device-side copy of the registered graph (R = 0 without one).  This
+        DB is not changed.  ``quantize_seconds`` of this DB holds the call's phases afterwards."""
+        eb = _err()
+        h = lib().diskann_hip_quantize_sq8(self._h, eb, 1024)
+        if not h:
+            raise HipAnnError(eb.value.decode(errors="replace") or "hipann error")
+        q = DiskannDeviceDB._from_handle(h, int(lib().diskann_hip_db_size(h)), self.dim, self.FMT_SQ8, self.R)
+        sec = (C.c_double * 3)()
+        if lib().diskann_hip_quantize_phase_seconds(self._h, sec) != 0:
+            raise HipAnnError("diskann_hip_quantize_phase_seconds failed")
+        self.quantize_seconds = {"stats_s": sec[0], "encode_s": sec[1], "rest_s": sec[2]}
+        return q
+
+    def export_sq8(self):
+        """(codes (n, dim) uint8, min (dim,), scale (dim,)) of this SQ8 DB, for the index file's SQ8 trailer."""
+        codes = np.empty((self.n, self.dim), np.uint8)
+        mins = np.empty(self.dim, np.float32)
+        scale = np.empty(self.dim, np.float32)
+        eb = _err()
+        rc = lib().diskann_hip_export_sq8(self._h, codes.ctypes.data_as(C.c_void_p), _ptr(mins, C.c_float),
+                                          _ptr(scale, C.c_float), eb, 1024)
+        _check(rc, eb)
+        return codes, mins, scale
 
     def batch_mates(self, row0: int, b: int, T: int) -> np.ndarray:
         """The mates step of add_rows alone: for each of the rows row0 .. row0+b−1 the ids of its min(T, b−1) nearest

@@ -208,6 +208,38 @@ int diskann_hip_batch_mates(void *db, int64_t row0, int b, int T, uint32_t *out 
  * [2] out-edge prunes, [3] back-edges.  seconds: 4 doubles. */
 int diskann_hip_add_phase_seconds(void *db, double *seconds);
 
+/* ---- extension: entry point and SQ8 search copy computed on the device -----------------
+ * One or two streaming passes over the rows the handle already holds, so the lifecycle needs the rows on the device
+ * once: register -> medoid -> build_graph -> quantize_sq8 -> SQ8 resident search -> add_rows / remove_ids -> quantize
+ * again (the codec's min / max are global, so a re-quantize is the whole pass).  Both device calls take the source's
+ * mutex, run on its stream and read its n rows only; neither changes the source.  No floating-point atomics and a row
+ * split that depends on n alone: two runs give the same bits. */
+
+/* Row nearest the mean of the registered fp32 rows (L2; smallest id on a tie) — hipann.medoid on the device:
+ * c = (sum of the rows) / n and the distances sum_j (double(x_ij) - c_j)^2 in fp64, the smallest (distance, id).  Every
+ * dim >= 1.  Refused: NULL, an SQ8 handle, n = 0.  0 / -1 (message in err_buf). */
+int diskann_hip_medoid(void *db, uint32_t *row_out, char *err_buf, int err_len);
+
+/* Provider::quantize_sq8 (provider.rs:161-210) on the device: a NEW handle, fmt SQ8, holding the codes of the
+ * source's n fp32 rows, min/scale per dimension, and — when the source has a graph registered — a device-to-device
+ * copy of its adjacency (same R), ready for every call an SQ8 handle takes today.  The source is not changed.
+ * Codec, in fp32: min[j], max[j] over the n rows; scale[j] = max - min if that is > 0, else 1;
+ * code = (u8) clamp(roundf(((v - min[j]) / scale[j]) * 255.0f), 0, 255) (IEEE division, round half away from zero).
+ * The handle is filled as diskann_hip_register_db(fmt = SQ8) fills it; the host copy of the adjacency is read back only
+ * when a flagged query needs the host BFS.  A source without a graph gives a handle without one.
+ * Refused with a message (never a slow path): a NULL or SQ8 source, n = 0, a non-finite value in the rows.
+ * Returns the handle (release with diskann_hip_release_db) or NULL (message in err_buf). */
+void *diskann_hip_quantize_sq8(void *db, char *err_buf, int err_len);
+
+/* Codes (n*dim u8), min[dim], scale[dim] of an SQ8 handle back to the host, for the SQ8\0 trailer
+ * (index_manager.rs:513-533).  Any output may be NULL.  Refused: a NULL or fp32 handle.  0 / -1. */
+int diskann_hip_export_sq8(void *db, void *codes /* n*dim uint8 */, float *sq8_min, float *sq8_scale, char *err_buf,
+                           int err_len);
+
+/* Measurement: seconds of the last diskann_hip_quantize_sq8 from `db`: [0] column statistics, [1] encode,
+ * [2] the rest (finite check, graph copy, handle set-up).  3 doubles. */
+int diskann_hip_quantize_phase_seconds(void *db, double *seconds);
+
 int64_t diskann_hip_db_size(void *db);
 
 /* Measurement: record HIP events around every id-gather kernel launch of `db` (on its stream) from now
