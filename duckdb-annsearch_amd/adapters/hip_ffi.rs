@@ -169,6 +169,13 @@ extern "C" {
         err_buf: *mut core::ffi::c_char,
         err_len: i32,
     ) -> i32;
+    fn diskann_hip_set_graph_metric(
+        db: *mut core::ffi::c_void,
+        metric: i32,
+        err_buf: *mut core::ffi::c_char,
+        err_len: i32,
+    ) -> i32;
+    fn diskann_hip_graph_metric(db: *mut core::ffi::c_void) -> i32;
 }
 
 /// Cached availability: -1 = unchecked, 0 = unavailable, 1 = available (metal_ffi.rs:33-34).
@@ -492,7 +499,7 @@ impl HipDiskDb {
                 max_degree as i32,
                 l_build as i32,
                 alpha,
-                0,
+                diskann_hip_graph_metric(self.h),  // the handle's graph metric (set_graph_metric; L2 by default)
                 entry_point,
                 batch_max.min(i32::MAX as usize) as i32,
                 adjacency.as_mut_ptr(),
@@ -534,7 +541,7 @@ impl HipDiskDb {
                 labels.as_ptr(),
                 labels.len() as i64,
                 alpha,
-                0,
+                diskann_hip_graph_metric(self.h),  // the handle's graph metric
                 &mut ep,
                 0,
                 adjacency.as_mut_ptr(),
@@ -589,7 +596,7 @@ impl HipDiskDb {
                 m as i64,
                 l_build as i32,
                 alpha,
-                0,
+                diskann_hip_graph_metric(self.h),  // the handle's graph metric
                 entry_point,
                 batch_max.min(i32::MAX as usize) as i32,
                 batch_mates as i32,
@@ -620,6 +627,21 @@ impl HipDiskDb {
             return None;
         }
         Some(out)
+    }
+
+    /// The metric of the graph this handle builds and maintains (hip_diskann_bridge.h): 0 = L2 (the
+    /// default), 1 = inner product.  An index has one metric for life: set it once from the `.diskann` header's metric
+    /// after registering the DB; build_graph / add_rows / remove_ids / robust_prune then require that metric and refuse
+    /// the other, and quantize_sq8 hands it on.  The searches keep their per-call metric.  false ⇒ a value other than
+    /// 0 / 1.
+    pub fn set_graph_metric(&self, metric: i32) -> bool {
+        let mut err = [0 as core::ffi::c_char; 256];
+        unsafe { diskann_hip_set_graph_metric(self.h, metric, err.as_mut_ptr(), err.len() as i32) == 0 }
+    }
+
+    /// The handle's graph metric (0 = L2, 1 = inner product).
+    pub fn graph_metric(&self) -> i32 {
+        unsafe { diskann_hip_graph_metric(self.h) }
     }
 
     /// The row nearest the mean of this fp32 DB's rows, on the GPU — the `medoid(&rows_flat, n, dim)` of
@@ -692,7 +714,7 @@ impl HipDiskDb {
                 pool_cap as i32,
                 max_degree as i32,
                 alpha,
-                0,
+                diskann_hip_graph_metric(self.h),  // the handle's graph metric
                 out.as_mut_ptr(),
                 err.as_mut_ptr(),
                 err.len() as i32,

@@ -568,6 +568,25 @@ int diskann_hip_multi_batch_distances_ids_device(void *h, const float *queries_d
 
 int64_t diskann_hip_db_size(void *h) { return h ? static_cast<DiskDB *>(h)->n : -1; }
 
+// the metric of the graph the handle builds and maintains (build_shape_check of diskann_graph.cpp reads it)
+int diskann_hip_set_graph_metric(void *h, int metric, char *eb, int el) {
+    return abi_call(eb, el, [&] {
+        HIPANN_REQUIRE(h, "set_graph_metric: null db");
+        HIPANN_REQUIRE(metric == kL2 || metric == kIP, "set_graph_metric: metric must be 0 (L2) or 1 (IP)");
+        auto *db = static_cast<DiskDB *>(h);
+        std::lock_guard<std::mutex> lk(db->mu);
+        db->graph_metric = metric;
+        return 0;
+    });
+}
+
+int diskann_hip_graph_metric(void *h) {
+    if (!h) return -1;
+    auto *db = static_cast<DiskDB *>(h);
+    std::lock_guard<std::mutex> lk(db->mu);
+    return db->graph_metric;
+}
+
 int diskann_hip_set_kernel_timing(void *h, int on) {
     if (!h) return -1;
     auto *db = static_cast<DiskDB *>(h);

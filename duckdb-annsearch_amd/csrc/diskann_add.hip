@@ -8,7 +8,7 @@
 //     A 256-thread workgroup owns a block of 32 rows and walks the column blocks of 128 rows (one 32 × 32 tile per
 //     wave, 16 accumulator registers); b is not bounded.  The norms G_ii come from vamana_batch_norms, which runs the
 //     same chain on the diagonal tiles, so equal rows give G_ii = G_jj = G_ij bit for bit and distance exactly 0.
-//   d(i, j) = max(0, (G_ii + G_jj) − 2·G_ij), the prune's form.
+//   d(i, j) = max(0, (G_ii + G_jj) − 2·G_ij), the prune's form; on an IP handle d(i, j) = −G_ij and no norms are read.
 //   Selection: the tile's distances go through LDS (over the column slice, which is spent); each wave keeps the
 //     sorted top-64 lists (wave_topk.hpp) of 8 of the block's rows in registers across the column blocks and offers
 //     them 64 candidates at a time, ordered by (distance, id); the row itself never enters.
@@ -83,7 +83,9 @@ __global__ void __launch_bounds__(64) vamana_batch_norms(const float *__restrict
     }
 }
 
-// out[i·T + j] = row0 + (the j-th nearest other row of batch row i), UINT32_MAX past min(T, b − 1); 1 ≤ T ≤ 64
+// out[i·T + j] = row0 + (the j-th nearest other row of batch row i), UINT32_MAX past min(T, b − 1); 1 ≤ T ≤ 64.
+// IP: a row's mates are ordered by (−G_ij, id); no norms are read.
+template <bool IP>
 __global__ void __launch_bounds__(256) vamana_batch_mates(const float *__restrict__ xb, int b, int d,
                                                           const float *__restrict__ nrm, uint32_t row0, int T,
                                                           uint32_t *__restrict__ out, unsigned long long *written) {
@@ -100,7 +102,7 @@ __global__ void __launch_bounds__(256) vamana_batch_mates(const float *__restric
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int gi = rb0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        ni[r] = gi < b ? nrm[gi] : 0.f;
+        ni[r] = !IP && gi < b ? nrm[gi] : 0.f;
     }
     for (int cb0 = 0; cb0 < b; cb0 += kCB) {
         f32x16 acc;
@@ -115,13 +117,18 @@ __global__ void __launch_bounds__(256) vamana_batch_mates(const float *__restric
         }
         // the tile's distances; the row itself and cells past b never compete
         const int gj = cb0 + 32 * wave + l31;
-        const float nj = gj < b ? nrm[gj] : 0.f;
+        const float nj = !IP && gj < b ? nrm[gj] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
             const int gi = rb0 + row;
-            float dj = (ni[r] + nj) - 2.f * acc[r];
-            dj = dj < 0.f ? 0.f : dj;
+            float dj;
+            if constexpr (IP) {
+                dj = -acc[r];
+            } else {
+                dj = (ni[r] + nj) - 2.f * acc[r];
+                dj = dj < 0.f ? 0.f : dj;
+            }
             s_b[row * kDD + 32 * wave + l31] = (gi < b && gj < b && gi != gj) ? dj : __builtin_inff();
         }
         __syncthreads();
@@ -187,13 +194,18 @@ __global__ void __launch_bounds__(256) vamana_check_finite(const float *__restri
 }  // namespace
 
 // xb: b rows of d floats on the device (16-B aligned, d % 4 == 0); nrm: b floats of scratch; out: b·T words
-void launch_vamana_batch_mates(const float *xb, int b, int d, uint32_t row0, int T, float *nrm, uint32_t *out,
-                               unsigned long long *written, hipStream_t st) {
+void launch_vamana_batch_mates(const float *xb, int b, int d, uint32_t row0, int T, int metric, float *nrm,
+                               uint32_t *out, unsigned long long *written, hipStream_t st) {
     if (b <= 0) return;
     HIPANN_REQUIRE(d > 0 && d % 4 == 0 && d <= 2048 && T >= 1 && T <= 64, "vamana_batch_mates: unsupported shape");
     const dim3 grid((unsigned)ceil_div(b, kRB));
-    hipLaunchKernelGGL(vamana_batch_norms, grid, dim3(64), 0, st, xb, b, d, nrm);
-    hipLaunchKernelGGL(vamana_batch_mates, grid, dim3(256), 0, st, xb, b, d, nrm, row0, T, out, written);
+    HIPANN_REQUIRE(metric == kL2 || metric == kIP, "vamana_batch_mates: unsupported metric");
+    if (metric == kIP) {
+        hipLaunchKernelGGL(vamana_batch_mates<true>, grid, dim3(256), 0, st, xb, b, d, nrm, row0, T, out, written);
+    } else {
+        hipLaunchKernelGGL(vamana_batch_norms, grid, dim3(64), 0, st, xb, b, d, nrm);
+        hipLaunchKernelGGL(vamana_batch_mates<false>, grid, dim3(256), 0, st, xb, b, d, nrm, row0, T, out, written);
+    }
     HIPANN_CHECK(hipGetLastError());
 }
 

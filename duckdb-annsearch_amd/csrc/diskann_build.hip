@@ -18,6 +18,9 @@
 //   3. selection: wave 0 runs the greedy passes over the finished matrix, 4 pool positions per lane: threshold
 //      t = 1, ·min(alpha, 1.2) …, capped at alpha; a position is selected when its occlusion factor
 //      max_j d(p, i) / d(j, i) over the selected j ahead of it is ≤ t; selecting i updates every later position.
+//   vamana_prune<kIP> (a handle whose graph metric is IP): d = −dot, so (1) computes −Σ p·v by the same
+//   lane split and the keys hold ip_key_bits(dist), (2) is unchanged and d(j, i) = −G_ji (no norms, no clamp), and
+//   (3) is the crate's occluding rule, which remembers per position how many selected entries it has met.
 //
 // Back-edges of a batch — count (atomic per target row; integer), offsets, fill, then one wave per touched row:
 // the row's new sources rank-sorted ascending (the order of arrival never shows), appended when the row has room,
@@ -49,6 +52,7 @@ __device__ __forceinline__ uint32_t load_l2(const uint32_t *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+template <int METRIC>
 __global__ void __launch_bounds__(256) vamana_prune(PruneArgs a) {
     __shared__ unsigned long long s_key[2 * kPoolMax];
     __shared__ __attribute__((aligned(16))) float s_tile[kTileFloats];
@@ -100,21 +104,29 @@ __global__ void __launch_bounds__(256) vamana_prune(PruneArgs a) {
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             const float4 v = xc[u][q4];
-                            float w;
-                            w = p4.x - v.x; s[u] = fmaf(w, w, s[u]);
-                            w = p4.y - v.y; s[u] = fmaf(w, w, s[u]);
-                            w = p4.z - v.z; s[u] = fmaf(w, w, s[u]);
-                            w = p4.w - v.w; s[u] = fmaf(w, w, s[u]);
+                            if constexpr (METRIC == kIP) {
+                                s[u] = fmaf(p4.x, v.x, s[u]);
+                                s[u] = fmaf(p4.y, v.y, s[u]);
+                                s[u] = fmaf(p4.z, v.z, s[u]);
+                                s[u] = fmaf(p4.w, v.w, s[u]);
+                            } else {
+                                float w;
+                                w = p4.x - v.x; s[u] = fmaf(w, w, s[u]);
+                                w = p4.y - v.y; s[u] = fmaf(w, w, s[u]);
+                                w = p4.z - v.z; s[u] = fmaf(w, w, s[u]);
+                                w = p4.w - v.w; s[u] = fmaf(w, w, s[u]);
+                            }
                         }
                     }
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const float r = wave_sum(s[u]);
-                        if (lane == j0 + u) dist = r;
+                        if (lane == j0 + u) dist = METRIC == kIP ? -r : r;
                     }
                 }
             }
-            s_key[kPoolMax + t] = valid ? (((unsigned long long)__float_as_uint(dist) << 32) | id) : kBadKey;
+            const uint32_t kb = METRIC == kIP ? ip_key_bits(dist) : __float_as_uint(dist);
+            s_key[kPoolMax + t] = valid ? (((unsigned long long)kb << 32) | id) : kBadKey;
             __syncthreads();
             // bitonic sort of the 512 keys (ascending)
             for (int k = 2; k <= 2 * kPoolMax; k <<= 1)
@@ -238,8 +250,90 @@ __global__ void __launch_bounds__(256) vamana_prune(PruneArgs a) {
             __syncthreads();
         }
 
-        // ---- 3. greedy selection (wave 0; position p = s·64 + lane) ----
-        if (wave == 0) {
+        // ---- 3. selection (wave 0; position p = s·64 + lane) ----
+        if constexpr (METRIC == kIP) {
+            // The order-dependent rule of DESIGN §6.5 (the crate's lazy loop).  A position is tested against the
+            // selected entries in selection order and stops at its first occluder, so its verdict against the entries
+            // that exist never changes when more are appended: every alive position catches up with the entries it has
+            // not seen at the start of a pass, and the ones still unoccluded meet each new entry as it is selected.
+            if (wave == 0) {
+                float f[4], cd[4];
+                int c[4];     // entries of sel already compared with the position
+                bool pend[4];  // alive in this pass and not occluded so far
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int p = s * 64 + lane;
+                    f[s] = FLT_MAX;
+                    cd[s] = 0.f;
+                    c[s] = 0;
+                    if (p < M) {
+                        f[s] = 0.f;
+                        cd[s] = ip_key_dist((uint32_t)(s_key[p] >> 32));
+                    }
+                }
+                const float alpha = a.alpha, step = fminf(alpha, 1.2f);
+                float th = 1.0f;
+                int nsel = 0;
+                int selpos = 0;  // lane r: the position of the r-th selected entry
+                for (;;) {
+                    const float occ = th + 0.01f;
+                    float bound[4];  // t · d(p, i)
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        pend[s] = f[s] <= th;
+                        bound[s] = __fmul_rn(th, cd[s]);
+                    }
+                    // catch up with the entries selected in earlier passes
+                    for (int l = 0; l < nsel; ++l) {
+                        bool need = false;
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) need |= pend[s] && c[s] <= l;
+                        if (!__ballot(need)) continue;  // (wave-uniform)
+                        const int j = __builtin_amdgcn_readlane(selpos, l);
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) {
+                            const int p = s * 64 + lane;
+                            if (pend[s] && c[s] <= l) {
+                                c[s] = l + 1;
+                                if (j < p) {
+                                    const float g = g_lds ? s_tile[j * MP + p] : load_l2(gs + j * MP + p);
+                                    if (-g < bound[s]) { pend[s] = false; f[s] = occ; }
+                                }
+                            }
+                        }
+                    }
+                    // the first unoccluded position is selected; the later ones meet it
+                    while (nsel < R) {
+                        int i = -1;
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) {
+                            const unsigned long long mask = __ballot(pend[s]);
+                            if (i < 0 && mask) i = s * 64 + __ffsll(mask) - 1;
+                        }
+                        if (i < 0) break;
+                        if (lane == nsel) selpos = i;
+                        nsel++;
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) {
+                            const int p = s * 64 + lane;
+                            if (p == i) {
+                                pend[s] = false;
+                                f[s] = FLT_MAX;
+                            } else if (pend[s]) {  // (p > i: i is the first)
+                                c[s] = nsel;
+                                const float g = g_lds ? s_tile[i * MP + p] : load_l2(gs + i * MP + p);
+                                if (-g < bound[s]) { pend[s] = false; f[s] = occ; }
+                            }
+                        }
+                    }
+                    if (nsel >= R || !(th < alpha)) break;
+                    th = fminf(th * step, alpha);
+                }
+                uint32_t *o = a.out + (size_t)(a.out_by_target ? tgt : (uint32_t)tt) * R;
+                if (lane < R) o[lane] = lane < nsel ? (uint32_t)s_key[selpos] : kNone;
+                if (lane == 0 && s_trunc && a.counters) atomicAdd(a.counters + 1, 1ull);
+            }
+        } else if (wave == 0) {
             float f[4], cd[4], nrm[4];
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
@@ -402,7 +496,10 @@ size_t vamana_gram_bytes(int blocks) { return (size_t)blocks * kPoolMax * kPoolM
 void launch_vamana_prune(const PruneArgs &a, int blocks, hipStream_t st) {
     if (a.m <= 0) return;
     HIPANN_REQUIRE(a.d > 0 && a.d % 4 == 0 && a.R >= 1 && a.R <= 64 && blocks >= 1, "vamana_prune: unsupported shape");
-    hipLaunchKernelGGL(vamana_prune, dim3((unsigned)std::min(blocks, a.m)), dim3(256), 0, st, a);
+    HIPANN_REQUIRE(a.metric == kL2 || a.metric == kIP, "vamana_prune: unsupported metric");
+    const dim3 grid((unsigned)std::min(blocks, a.m));
+    if (a.metric == kIP) hipLaunchKernelGGL(vamana_prune<kIP>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(vamana_prune<kL2>, grid, dim3(256), 0, st, a);
     HIPANN_CHECK(hipGetLastError());
 }
 

@@ -26,6 +26,9 @@ struct DiskDB {
     KernelTimer timer;
     // resident graph + BFS scratch (diskann_hip_register_graph / _search_batch_resident)
     int R = 0;
+    // the metric of the graph this handle builds and maintains (diskann_hip_set_graph_metric): kL2 unless told
+    // otherwise.  The graph-writing calls require their `metric` argument to equal it; the searches do not read it.
+    int graph_metric = kL2;
     DevBuf adj_dev, dupw, visited, flags, bstats, eps_dev;
     DevBuf vbits;  // host BFS: the queries' visited bits on the device (one bit per row and query)
     std::vector<uint32_t> adj_host;

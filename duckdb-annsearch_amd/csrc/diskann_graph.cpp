@@ -27,11 +27,17 @@ void swap_buf(DevBuf &a, DevBuf &b) {
     std::swap(a.device, b.device);
 }
 
-// the shapes the build entry points and remove_ids refuse (a message, never a slow path); `who` names the call
+// the shapes the build entry points and remove_ids refuse (a message, never a slow path); `who` names the call.  The
+// call's metric must be the handle's graph metric (diskann_hip_set_graph_metric; L2 unless the handle was told otherwise).
 void build_shape_check(const DiskDB *db, int R, float alpha, int metric, const char *who = "graph build") {
     const std::string w = std::string(who) + ": ";
-    HIPANN_REQUIRE(metric != kIP, w + "IP is not supported (the crate prunes IP by a different rule)");
-    HIPANN_REQUIRE(metric == kL2, w + "metric must be 0 (L2)");
+    if (db->graph_metric == kL2) {
+        HIPANN_REQUIRE(metric != kIP, w + "IP is not supported (the crate prunes IP by a different rule)");
+        HIPANN_REQUIRE(metric == kL2, w + "metric must be 0 (L2)");
+    } else {
+        HIPANN_REQUIRE(metric == kIP, w + "metric must be 1 (IP): the handle's graph metric is IP "
+                                          "(diskann_hip_set_graph_metric)");
+    }
     HIPANN_REQUIRE(db->fmt == DISKANN_HIP_FMT_F32, w + "an fp32 DB is required (SQ8 is not supported)");
     HIPANN_REQUIRE(R >= 1 && R <= 64, w + "R must be in [1, 64]");
     HIPANN_REQUIRE(db->dim % 4 == 0 && db->dim <= 2048, w + "d must be a multiple of 4 and at most 2048");
@@ -83,6 +89,7 @@ struct VamanaInsert {
     int d = 0, R = 0;
     int T = 0;  // batch mates per row (0: the out-edge prune reads the traversal's lists in place)
     float alpha = 0.f;
+    int metric = kL2;  // the handle's graph metric
     uint32_t ep = 0;
     hipStream_t st = nullptr;
 
@@ -121,7 +128,7 @@ struct VamanaInsert {
     // (the graph's rows once the batch is in).  secs[0] += the out-edge prunes' seconds, secs[1] += the back-edges'.
     void step(uint32_t o0, int b, int K, int64_t rows, bool with_mates, double *secs) {
         PruneArgs p;  // what the two prunes share
-        p.x = x; p.d = d; p.n = (uint32_t)rows; p.R = R; p.alpha = alpha;
+        p.x = x; p.d = d; p.n = (uint32_t)rows; p.R = R; p.alpha = alpha; p.metric = metric;
         p.out = adj; p.out_by_target = 1; p.gram = gram.get<float>();
         // out-edges: N(p) = prune(p, the traversal's list [+ the row's batch mates])
         auto t1 = clk::now();
@@ -223,7 +230,7 @@ int diskann_hip_build_graph(void *h, int R, int l_build, float alpha, int metric
             const int bmax = (int)std::min<int64_t>(batch_max, n - 1);
             VamanaInsert ins;
             ins.x = db->data.get<float>(); ins.adj = db->adj_dev.get<uint32_t>();
-            ins.d = d; ins.R = R; ins.alpha = alpha; ins.ep = ep; ins.st = st;
+            ins.d = d; ins.R = R; ins.alpha = alpha; ins.metric = metric; ins.ep = ep; ins.st = st;
             ins.size("graph build", bmax, K, n, 32, dev);
             HIPANN_CHECK(hipMemsetAsync(ins.pctr.p, 0, 32, st));
             const uint32_t eps1[1] = {ep};
@@ -239,7 +246,7 @@ int diskann_hip_build_graph(void *h, int R, int l_build, float alpha, int metric
                     if (ob <= oa) continue;
                     const int64_t row0 = sgi == 0 ? oa : oa + 1;
                     int64_t sst[4] = {0, 0, 0, 0};
-                    resident_search_locked(db, eps1, 1, ins.x + row0 * d, (int)(ob - oa), K, l_build, kL2,
+                    resident_search_locked(db, eps1, 1, ins.x + row0 * d, (int)(ob - oa), K, l_build, metric,
                                            ins.sid.get<int64_t>() + (oa - o0) * K, ins.sd.get<float>() + (oa - o0) * K,
                                            sst, st);
                     s8[0] += sst[0];
@@ -310,7 +317,8 @@ int64_t diskann_hip_add_rows(void *h, const float *rows, int64_t m, int l_build,
         // ---- everything that can refuse or allocate, before anything a search reads changes ----
         const int bmax = (int)std::min<int64_t>(batch_max, m);
         VamanaInsert ins;
-        ins.d = d; ins.R = R; ins.T = T; ins.alpha = alpha; ins.ep = ep; ins.st = st;  // (x and adj: once grown, below)
+        ins.d = d; ins.R = R; ins.T = T; ins.alpha = alpha; ins.metric = metric; ins.ep = ep; ins.st = st;
+        // (x and adj: once grown, below)
         // (L + T: the pool slots of an out-edge prune with mates)
         HIPANN_REQUIRE((int64_t)bmax * (L + T) < INT32_MAX, "add_rows: batch_max too large");
         // pctr: [0..3] the prunes' counters, [4] mate ids written, [5] (int) the non-finite flag
@@ -372,7 +380,7 @@ int64_t diskann_hip_add_rows(void *h, const float *rows, int64_t m, int l_build,
             // search
             auto t0 = clk::now();
             int64_t sst[4] = {0, 0, 0, 0};
-            resident_search_locked(db, eps1, 1, x + (size_t)c * d, b, K, K, kL2, ins.sid.get<int64_t>(),
+            resident_search_locked(db, eps1, 1, x + (size_t)c * d, b, K, K, metric, ins.sid.get<int64_t>(),
                                    ins.sd.get<float>(), sst, st);
             s8[0] += sst[0];
             s8[4] += sst[3];
@@ -381,7 +389,7 @@ int64_t diskann_hip_add_rows(void *h, const float *rows, int64_t m, int l_build,
             const bool with_mates = T > 0 && b > 1;
             if (with_mates) {
                 auto tm = clk::now();
-                launch_vamana_batch_mates(x + (size_t)c * d, b, d, (uint32_t)c, T, ins.nrm.get<float>(),
+                launch_vamana_batch_mates(x + (size_t)c * d, b, d, (uint32_t)c, T, metric, ins.nrm.get<float>(),
                                           ins.mates.get<uint32_t>(), ins.pctr.get<unsigned long long>() + 4, st);
                 HIPANN_CHECK(hipStreamSynchronize(st));
                 secs[1] += since(tm);
@@ -419,7 +427,7 @@ int diskann_hip_batch_mates(void *h, int64_t row0, int b, int T, uint32_t *out, 
         HIPANN_REQUIRE(h, "batch_mates: null db");
         auto *db = static_cast<DiskDB *>(h);
         std::lock_guard<std::mutex> lk(db->mu);
-        build_shape_check(db, 1, 1.0f, kL2, "batch_mates");
+        build_shape_check(db, 1, 1.0f, db->graph_metric, "batch_mates");
         HIPANN_REQUIRE(T >= 1 && T <= 64, "batch_mates: T must be in [1, 64]");
         HIPANN_REQUIRE(row0 >= 0 && b >= 0 && row0 + b <= db->n, "batch_mates: rows out of range");
         HIPANN_REQUIRE(b == 0 || out, "batch_mates: null out");
@@ -430,7 +438,7 @@ int diskann_hip_batch_mates(void *h, int64_t row0, int b, int T, uint32_t *out, 
         nrm.ensure((size_t)b * 4, db->device);
         od.ensure((size_t)b * T * 4, db->device);
         launch_vamana_batch_mates(db->data.get<float>() + (size_t)row0 * db->dim, b, db->dim, (uint32_t)row0, T,
-                                  nrm.get<float>(), od.get<uint32_t>(), nullptr, st);
+                                  db->graph_metric, nrm.get<float>(), od.get<uint32_t>(), nullptr, st);
         HIPANN_CHECK(hipMemcpyAsync(out, od.p, (size_t)b * T * 4, hipMemcpyDeviceToHost, st));
         HIPANN_CHECK(hipStreamSynchronize(st));
         return 0;
@@ -542,7 +550,8 @@ int64_t diskann_hip_remove_ids(void *h, const int64_t *labels, int64_t n_labels,
             HIPANN_CHECK(hipMemcpyAsync(dlen.p, plen.data(), (size_t)na * 4, hipMemcpyHostToDevice, st));
             unsigned long long *c64 = ctr.get<unsigned long long>();
             PruneArgs pa;  // every slab's prune: its pools in `pool`, the pruned rows written over radj's
-            pa.x = x; pa.d = d; pa.n = (uint32_t)n; pa.R = R; pa.alpha = alpha; pa.pool32 = pool.get<uint32_t>();
+            pa.x = x; pa.d = d; pa.n = (uint32_t)n; pa.R = R; pa.alpha = alpha; pa.metric = metric;
+            pa.pool32 = pool.get<uint32_t>();
             pa.out = radj.get<uint32_t>(); pa.out_by_target = 1; pa.gram = gram.get<float>(); pa.counters = c64;
             // the stream orders fill, prune and the next slab's reuse of `pool`; events split the device time
             for (size_t s = 0; s + 1 < slab_at.size(); ++s) {
@@ -569,7 +578,8 @@ int64_t diskann_hip_remove_ids(void *h, const int64_t *labels, int64_t n_labels,
         unsigned long long hc[4] = {0, 0, 0, ~0ull};
         if (std::binary_search(dead.begin(), dead.end(), ep)) {
             HIPANN_CHECK(hipMemsetAsync(ctr.get<unsigned long long>() + 3, 0xff, 8, st));
-            launch_diskann_remove_nearest(x, d, n, bits.get<uint32_t>(), ep, ctr.get<unsigned long long>() + 3, st);
+            launch_diskann_remove_nearest(x, d, n, bits.get<uint32_t>(), ep, metric,
+                                          ctr.get<unsigned long long>() + 3, st);
             s8[5] = 1;
         }
         // 3. compact into fresh buffers: rows, adjacency (ids replaced by their ranks), repeated-id row bits
@@ -642,6 +652,7 @@ int diskann_hip_robust_prune(void *h, const uint32_t *targets, int m, const uint
         HIPANN_CHECK(hipMemcpyAsync(pl.p, pools, pw * 4, hipMemcpyHostToDevice, st));
         PruneArgs pa;  // target t's pool is pools[t·pool_cap ..], its row out[t·R ..]
         pa.x = db->data.get<float>(); pa.d = db->dim; pa.n = (uint32_t)db->n; pa.R = R; pa.alpha = alpha;
+        pa.metric = metric;
         pa.targets = tg.get<uint32_t>(); pa.m = m; pa.pool32 = pl.get<uint32_t>(); pa.pool_cap = pool_cap;
         pa.out = od.get<uint32_t>(); pa.gram = gram.get<float>();
         launch_vamana_prune(pa, blocks, st);

@@ -19,6 +19,17 @@ __device__ __forceinline__ float wave_sum(float s) {
     return s;
 }
 
+// IP distances (−dot) take both signs, so their raw bits do not order like the floats.  ip_key_bits: −0.0 counts as
+// +0.0, then all bits of a negative flip and the sign bit of a non-negative is set — an unsigned that orders like the
+// float, for the high word of a (distance, id) key; ip_key_dist is its inverse.
+__device__ __forceinline__ uint32_t ip_key_bits(float v) {
+    const uint32_t u = __float_as_uint(v == 0.f ? 0.f : v);
+    return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ip_key_dist(uint32_t k) {
+    return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k);
+}
+
 // ---- diskann_bfs.hip ----
 bool diskann_bfs_supported(int d, int fmt, int R, int n_ep, int L, uint32_t N);
 void launch_diskann_dup_rows(const uint32_t *adj, int R, int64_t n, uint32_t *dupw, hipStream_t st);
@@ -43,6 +54,7 @@ struct PruneArgs {
     int pool_cap = 0;
     int R = 0;
     float alpha = 0.f;
+    int metric = kL2;  // kL2: the triangle-inequality rule of DESIGN §6; kIP: the occluding rule of §6.5
     uint32_t *out = nullptr;
     int out_by_target = 0;  // rows of `out` indexed by the target's id (the adjacency) instead of its position
     float *gram = nullptr;  // gridDim.x × 256² floats
@@ -57,8 +69,8 @@ void launch_vamana_backedges(uint32_t *adj, int R, const uint32_t *tg, int b, in
                              int *plen, hipStream_t st);
 
 // ---- diskann_add.hip ----
-void launch_vamana_batch_mates(const float *xb, int b, int d, uint32_t row0, int T, float *nrm, uint32_t *out,
-                               unsigned long long *written, hipStream_t st);
+void launch_vamana_batch_mates(const float *xb, int b, int d, uint32_t row0, int T, int metric, float *nrm,
+                               uint32_t *out, unsigned long long *written, hipStream_t st);
 void launch_vamana_concat_pool(const int64_t *sid, int K, const uint32_t *mates, int T, int b, uint32_t *pool,
                                int *pbeg, int *plen, hipStream_t st);
 void launch_vamana_check_finite(const float *x, int64_t count, int *flag, hipStream_t st);
@@ -73,7 +85,7 @@ void launch_diskann_remove_pool_len(const uint32_t *adj, int R, int64_t n, const
 void launch_diskann_remove_pool_fill(const uint32_t *adj, int R, int64_t n, const uint32_t *bits,
                                      const uint32_t *targets, const int *pbeg, const int *plen, int cnt, uint32_t *pool,
                                      unsigned long long *gathered, hipStream_t st);
-void launch_diskann_remove_nearest(const float *x, int d, int64_t n, const uint32_t *bits, uint32_t ep,
+void launch_diskann_remove_nearest(const float *x, int d, int64_t n, const uint32_t *bits, uint32_t ep, int metric,
                                    unsigned long long *best, hipStream_t st);
 void launch_diskann_remove_compact_adj(const uint32_t *adj, int R, int64_t n, const uint32_t *bits,
                                        const uint32_t *wpre, uint32_t *out, hipStream_t st);

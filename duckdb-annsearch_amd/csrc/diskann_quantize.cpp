@@ -39,6 +39,7 @@ DiskDB *quantize_sq8(void *h) {
     q->n = n;
     q->dim = d;
     q->fmt = DISKANN_HIP_FMT_SQ8;
+    q->graph_metric = src->graph_metric;
     q->data.ensure((size_t)n * d + 16, dev);
     q->ab.ensure((size_t)d * 8, dev);
     q->ab_raw.ensure((size_t)d * 8, dev);

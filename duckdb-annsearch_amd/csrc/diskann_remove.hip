@@ -13,7 +13,8 @@
 //                    neighbour's row; removed ids, ids ≥ n and padding are written as UINT32_MAX, which the prune drops
 //   rm_nearest_live  the live row nearest a removed entry point by (Σ(a−b)², id): the prune's direct distance (per-lane
 //                    fma chain over float4 chunks lane, lane + 64, …, butterfly sum) and a 64-bit atomicMin on
-//                    dist bits << 32 | id (the distance is non-negative, so its bit order is the float order)
+//                    dist bits << 32 | id (the distance is non-negative, so its bit order is the float order); on an
+//                    IP handle the distance is −dot and the key holds its order-preserving bits (ip_key_bits)
 //   rm_compact_adj   one wave per surviving row: the repaired row written at its new position, every id replaced by
 //                    its rank; slots past the first UINT32_MAX become UINT32_MAX
 // No floating-point atomics: every result is the same from run to run.
@@ -174,6 +175,7 @@ __global__ void __launch_bounds__(256) rm_pool_fill(const uint32_t *__restrict__
     }
 }
 
+template <bool IP>
 __global__ void __launch_bounds__(256) rm_nearest_live(const float *__restrict__ x, int d, int64_t n,
                                                        const uint32_t *__restrict__ bits, uint32_t ep,
                                                        unsigned long long *best) {
@@ -186,14 +188,22 @@ __global__ void __launch_bounds__(256) rm_nearest_live(const float *__restrict__
         float s = 0.f;
         for (int q4 = lane; q4 < (d >> 2); q4 += 64) {
             const float4 p4 = xt[q4], c4 = xc[q4];
-            float w;
-            w = p4.x - c4.x; s = fmaf(w, w, s);
-            w = p4.y - c4.y; s = fmaf(w, w, s);
-            w = p4.z - c4.z; s = fmaf(w, w, s);
-            w = p4.w - c4.w; s = fmaf(w, w, s);
+            if constexpr (IP) {
+                s = fmaf(p4.x, c4.x, s);
+                s = fmaf(p4.y, c4.y, s);
+                s = fmaf(p4.z, c4.z, s);
+                s = fmaf(p4.w, c4.w, s);
+            } else {
+                float w;
+                w = p4.x - c4.x; s = fmaf(w, w, s);
+                w = p4.y - c4.y; s = fmaf(w, w, s);
+                w = p4.z - c4.z; s = fmaf(w, w, s);
+                w = p4.w - c4.w; s = fmaf(w, w, s);
+            }
         }
         s = wave_sum(s);
-        const unsigned long long key = ((unsigned long long)__float_as_uint(s) << 32) | (uint32_t)row;
+        const uint32_t kb = IP ? ip_key_bits(-s) : __float_as_uint(s);
+        const unsigned long long key = ((unsigned long long)kb << 32) | (uint32_t)row;
         mine = key < mine ? key : mine;
     }
     if (lane == 0 && mine != ~0ull) atomicMin(best, mine);
@@ -251,12 +261,15 @@ void launch_diskann_remove_pool_fill(const uint32_t *adj, int R, int64_t n, cons
     HIPANN_CHECK(hipGetLastError());
 }
 
-// best: one 64-bit word, all ones on entry; dist bits << 32 | id of the nearest live row on exit
-void launch_diskann_remove_nearest(const float *x, int d, int64_t n, const uint32_t *bits, uint32_t ep,
+// best: one 64-bit word, all ones on entry; dist bits << 32 | id of the nearest live row on exit (IP: the distance is
+// −dot and its bits are ip_key_bits')
+void launch_diskann_remove_nearest(const float *x, int d, int64_t n, const uint32_t *bits, uint32_t ep, int metric,
                                    unsigned long long *best, hipStream_t st) {
     HIPANN_REQUIRE(d > 0 && d % 4 == 0, "diskann remove: d must be a multiple of 4");
     const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n, 4), 2048);
-    hipLaunchKernelGGL(rm_nearest_live, dim3(grid), dim3(256), 0, st, x, d, n, bits, ep, best);
+    HIPANN_REQUIRE(metric == kL2 || metric == kIP, "diskann remove: unsupported metric");
+    if (metric == kIP) hipLaunchKernelGGL(rm_nearest_live<true>, dim3(grid), dim3(256), 0, st, x, d, n, bits, ep, best);
+    else hipLaunchKernelGGL(rm_nearest_live<false>, dim3(grid), dim3(256), 0, st, x, d, n, bits, ep, best);
     HIPANN_CHECK(hipGetLastError());
 }
 

@@ -170,6 +170,8 @@ def lib() -> C.CDLL:
             "diskann_hip_quantize_sq8": ([vp, cp, i32], vp),
             "diskann_hip_export_sq8": ([vp, vp, f, f, cp, i32], i32),
             "diskann_hip_quantize_phase_seconds": ([vp, C.POINTER(C.c_double)], i32),
+            "diskann_hip_set_graph_metric": ([vp, i32, cp, i32], i32),
+            "diskann_hip_graph_metric": ([vp], i32),
         }
         missing = [name for name in sig if not hasattr(L, name)]
         if missing:
@@ -749,7 +751,7 @@ class DiskannDeviceDB:
 
     FMT_F32, FMT_SQ8 = 0, 1
 
-    def __init__(self, data: np.ndarray, fmt: int = 0, sq8_min=None, sq8_scale=None):
+    def __init__(self, data: np.ndarray, fmt: int = 0, sq8_min=None, sq8_scale=None, graph_metric: int = METRIC_L2):
         if fmt == self.FMT_F32:
             data = np.ascontiguousarray(data, np.float32)
         else:
@@ -764,6 +766,12 @@ class DiskannDeviceDB:
         self._h = C.c_void_p(h)
         self.n, self.dim, self.fmt = n, dim, fmt
         self.R = 0  # degree of the registered graph (0: none)
+        if graph_metric != METRIC_L2:
+            try:
+                self.graph_metric = graph_metric
+            except HipAnnError:
+                self.close()
+                raise
 
     @classmethod
     def _from_handle(cls, h, n: int, dim: int, fmt: int, R: int) -> "DiskannDeviceDB":
@@ -772,6 +780,21 @@ class DiskannDeviceDB:
         db._h = C.c_void_p(h)
         db.n, db.dim, db.fmt, db.R = n, dim, fmt, R
         return db
+
+    @property
+    def graph_metric(self) -> int:
+        """The metric of the graph this handle builds and maintains (METRIC_L2 unless set): build_graph, add_rows,
+        remove_ids and robust_prune run in it and refuse any other ``metric``; quantize_sq8 hands it on.  The searches
+        keep their per-call ``metric``."""
+        m = int(lib().diskann_hip_graph_metric(self._h))
+        if m < 0:
+            raise HipAnnError("diskann_hip_graph_metric failed")
+        return m
+
+    @graph_metric.setter
+    def graph_metric(self, metric: int) -> None:
+        eb = _err()
+        _check(lib().diskann_hip_set_graph_metric(self._h, int(metric), eb, 1024), eb)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -818,9 +841,11 @@ class DiskannDeviceDB:
         self.R = adj.shape[1]
 
     def build_graph(self, R: int = 64, L: int = 128, alpha: float = 1.2, entry_point: int = 0,
-                    batch_max: int = 4096, metric: int = METRIC_L2):
+                    batch_max: int = 4096, metric: Optional[int] = None):
         """Build the DiskANN graph of this fp32 DB on the GPU (batched insert, RobustPrune, back-edges)
-        and leave it registered for search_batch_resident.  Returns (adjacency (n, R) uint32, stats)."""
+        and leave it registered for search_batch_resident.  ``metric`` None: the handle's graph_metric.  Returns
+        (adjacency (n, R) uint32, stats)."""
+        metric = self.graph_metric if metric is None else int(metric)
         if not 0 <= int(entry_point) < 2 ** 32:
             raise HipAnnError("graph build: entry_point must be below n")
         adj = np.empty((self.n, max(int(R), 0)), np.uint32)
@@ -837,12 +862,13 @@ class DiskannDeviceDB:
                      "back_prunes": int(stats[3]), "host_requeries": int(stats[4]), "pools_truncated": int(stats[5]),
                      "unreachable": int(stats[6]), "search_s": sec[0], "out_prune_s": sec[1], "back_edge_s": sec[2]}
 
-    def remove_ids(self, labels, entry_point: int, alpha: float = 1.2, metric: int = METRIC_L2,
+    def remove_ids(self, labels, entry_point: int, alpha: float = 1.2, metric: Optional[int] = None,
                    scratch_words: int = 0):
         """Remove rows from this DB and its registered graph in place (the rows that point at a removed
         row are repaired with RobustPrune, then rows and adjacency are compacted and relabelled; new id = old id −
         removed rows below it).  Duplicate labels and labels outside [0, n) are ignored.  Returns (adjacency (n', R)
         uint32, new entry point, stats) and updates self.n."""
+        metric = self.graph_metric if metric is None else int(metric)
         lab = np.ascontiguousarray(labels, np.int64).reshape(-1)
         if not 0 <= int(entry_point) < 2 ** 32:
             raise HipAnnError("remove_ids: entry_point must be below n")
@@ -868,11 +894,12 @@ class DiskannDeviceDB:
                                     "compact_s": sec[2]}
 
     def add_rows(self, rows, entry_point: int, L: int = 128, alpha: float = 1.2, batch_max: int = 4096,
-                 batch_mates: int = 16, metric: int = METRIC_L2, want_adjacency: bool = True):
+                 batch_mates: int = 16, metric: Optional[int] = None, want_adjacency: bool = True):
         """Append ``rows`` (m, dim) to this fp32 DB and insert them into its registered graph in place (DESIGN §6.3:
         the build's batches continued, each batch row's ``batch_mates`` nearest batch-mates joined to its prune pool).
         The rows get ids n .. n+m−1.  Returns (adjacency (n+m, R) uint32, or None without ``want_adjacency`` — then
         nothing of the graph is copied to the host and stats["unreachable"] is −1 —, stats) and updates self.n."""
+        metric = self.graph_metric if metric is None else int(metric)
         x = np.ascontiguousarray(rows, np.float32)
         if x.ndim == 1:
             x = x.reshape(-1, self.dim)
@@ -935,16 +962,17 @@ class DiskannDeviceDB:
 
     def batch_mates(self, row0: int, b: int, T: int) -> np.ndarray:
         """The mates step of add_rows alone: for each of the rows row0 .. row0+b−1 the ids of its min(T, b−1) nearest
-        other rows of that range, by (distance, id); (b, T) uint32, UINT32_MAX-padded."""
+        other rows of that range, by (distance, id) in the handle's graph_metric; (b, T) uint32, UINT32_MAX-padded."""
         out = np.empty((max(int(b), 0), max(int(T), 0)), np.uint32)
         eb = _err()
         rc = lib().diskann_hip_batch_mates(self._h, int(row0), int(b), int(T), _ptr(out, C.c_uint32), eb, 1024)
         _check(rc, eb)
         return out
 
-    def robust_prune(self, targets, pools, R: int, alpha: float = 1.2, metric: int = METRIC_L2) -> np.ndarray:
+    def robust_prune(self, targets, pools, R: int, alpha: float = 1.2, metric: Optional[int] = None) -> np.ndarray:
         """prune() of DESIGN §6 for each target over its row of `pools` (m, pool_cap) uint32 ids (UINT32_MAX padding;
         the target itself, repeats and ids >= n are dropped).  Returns (m, R) uint32 ids, UINT32_MAX-padded."""
+        metric = self.graph_metric if metric is None else int(metric)
         tg = np.ascontiguousarray(targets, np.uint32).reshape(-1)
         pl = np.ascontiguousarray(pools, np.uint32)
         if pl.ndim != 2 or pl.shape[0] != tg.size:

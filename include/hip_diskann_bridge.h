@@ -114,9 +114,21 @@ int diskann_hip_search_batch_resident_device(void *db, const uint32_t *entry_poi
                                              char *err_buf, int err_len);
 
 /* ---- extension: graph build on the device -------------------------------------------
- * Batched insert + RobustPrune + back-edge update against the registered fp32 DB, L2 only.  Refused with a
- * message (never a slow path): IP, an SQ8 DB, R > 64, L > 256, L < 1, d % 4 != 0, d > 2048, n >= 2^31,
- * alpha < 1 or NaN, entry_point >= n, batch_max < 1.  A refused call leaves a registered graph as it was. */
+ * Batched insert + RobustPrune + back-edge update against the registered fp32 DB, in the handle's graph metric
+ * (below).  Refused with a message (never a slow path): a `metric` other than the handle's graph metric, an SQ8 DB,
+ * R > 64, L > 256, L < 1, d % 4 != 0, d > 2048, n >= 2^31, alpha < 1 or NaN, entry_point >= n, batch_max < 1.  A
+ * refused call leaves a registered graph as it was. */
+
+/* The metric of the graph a handle builds and maintains: 0 (L2, the default) or 1 (IP; the prune is the crate's
+ * occluding rule).  An index has one metric for life, so it is a property of the handle:
+ * diskann_hip_build_graph, _robust_prune, _add_rows and _remove_ids require their `metric` argument to equal it (on a
+ * handle never told otherwise that is L2, and metric = 1 is refused as before), diskann_hip_batch_mates uses it, and
+ * diskann_hip_quantize_sq8 copies it onto the new handle.  It may be set at any time, before or after a graph is
+ * registered; it is taken under the handle's mutex and changes nothing in HBM.  The search entry points keep their
+ * per-call `metric` and do not read it.  set: 0, or -1 (NULL, or a value other than 0 / 1; message in err_buf).
+ * get: the metric, or -1 for NULL. */
+int diskann_hip_set_graph_metric(void *db, int metric, char *err_buf, int err_len);
+int diskann_hip_graph_metric(void *db);
 
 /* Build the graph of the registered fp32 DB on the device (spec: DESIGN §6).  adjacency_out: n*R uint32 (host, may be NULL).
  * On success the graph is also registered on `db`, as after diskann_hip_register_graph.  stats (may be NULL, 8 int64):
@@ -125,7 +137,7 @@ int diskann_hip_search_batch_resident_device(void *db, const uint32_t *entry_poi
 int diskann_hip_build_graph(void *db, int R, int l_build, float alpha, int metric, uint32_t entry_point,
                             int batch_max, uint32_t *adjacency_out, int64_t *stats, char *err_buf, int err_len);
 
-/* prune() of the spec for m targets: pools is m*pool_cap ids (UINT32_MAX-padded; self, repeats and ids >= n are
+/* prune() of the spec (prune_ip() of DESIGN §6.5 on an IP handle) for m targets: pools is m*pool_cap ids (UINT32_MAX-padded; self, repeats and ids >= n are
  * dropped), distances to the target computed on the device.  out: m*R ids, UINT32_MAX-padded.  Host pointers; synchronous. */
 int diskann_hip_robust_prune(void *db, const uint32_t *targets, int m, const uint32_t *pools, int pool_cap, int R,
                              float alpha, int metric, uint32_t *out, char *err_buf, int err_len);
@@ -141,8 +153,9 @@ int diskann_hip_build_phase_seconds(void *db, double *seconds);
  * their live neighbours plus the live neighbours of their removed neighbours (one hop), pruned as in the build.
  * Then the rows and the adjacency are compacted: survivors keep their order, new id = old id − removed rows below
  * it (the label_map `compact` returns), every stored id is relabelled.  A removed entry point is replaced by the
- * nearest live row, (Σ(a−b)², id) ascending.
- * Refused with a message (never a slow path): whatever the build refuses (IP, an SQ8 DB, R > 64, d % 4 != 0,
+ * nearest live row, (Σ(a−b)², id) ascending — (−dot, id) on a handle whose graph metric is IP.
+ * Refused with a message (never a slow path): whatever the build refuses (a `metric` other than the handle's graph
+ * metric, an SQ8 DB, R > 64, d % 4 != 0,
  * d > 2048, n >= 2^31, alpha < 1 or NaN), no graph registered, *entry_point >= n, removing every row.  A refused or
  * failed call leaves the handle answering as before.  No label in range: returns 0 and nothing moves.
  * scratch_words: pool slots (uint32) the repair may hold at once, 0 = 2^28; the result does not depend on it.
@@ -173,8 +186,8 @@ int diskann_hip_remove_phase_seconds(void *db, double *seconds);
  * stood at the batch's start, pruned and back-linked as in the build.  batch_mates = T > 0 adds every batch row's
  * min(T, b-1) nearest other batch rows to its prune pool, so that a burst of mutually similar rows links to itself
  * (without it such rows only see the old graph); T = 0 is bit for bit the build's own loop continued.
- * Refused with a message (never a slow path): whatever the build refuses (IP, an SQ8 DB, d % 4 != 0, d > 2048,
- * alpha < 1 or NaN), no graph registered, L outside [1, 256], batch_max < 1, batch_mates outside [0, 64],
+ * Refused with a message (never a slow path): whatever the build refuses (a `metric` other than the handle's graph
+ * metric, an SQ8 DB, d % 4 != 0, d > 2048, alpha < 1 or NaN), no graph registered, L outside [1, 256], batch_max < 1, batch_mates outside [0, 64],
  * L + batch_mates > 512, entry_point >= n, rows NULL with m > 0, n + m >= 2^31, a non-finite value in rows.  A refused
  * call leaves the handle answering as before; m = 0 returns 0 and nothing moves.  A device failure after the first
  * change cannot be rolled back: the handle keeps its n rows but drops its graph, and searches refuse until a graph is
@@ -199,8 +212,8 @@ int64_t diskann_hip_add_rows(void *db, const float *rows, int64_t m, int l_build
 
 /* The mates step of add_rows alone, over the registered rows row0 .. row0+b-1 (fp32 DB, d % 4 == 0, d <= 2048,
  * 1 <= T <= 64): out[i*T + j] = the id of the j-th nearest other row of the range to row row0+i, ordered by
- * (max(0, (G_ii + G_jj) - 2 G_ij), id) with G the range's Gram matrix; UINT32_MAX past min(T, b-1).  Host pointer;
- * synchronous. */
+ * (max(0, (G_ii + G_jj) - 2 G_ij), id) with G the range's Gram matrix — by (-G_ij, id) on a handle whose graph metric
+ * is IP —; UINT32_MAX past min(T, b-1).  Host pointer; synchronous. */
 int diskann_hip_batch_mates(void *db, int64_t row0, int b, int T, uint32_t *out /* b * T */, char *err_buf,
                             int err_len);
 

@@ -44,9 +44,11 @@ def main():
     ap.add_argument("--scratch-words", type=int, default=0)
     ap.add_argument("--repeat", type=int, default=3, help="timed repetitions of each side (the median is reported)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--metric", choices=["l2", "ip"], default="l2", help="the handles' graph metric (DESIGN §6.5)")
     ap.add_argument("--out-dir", default=None, help="write remove_bench.jsonl and README.md here")
     a = ap.parse_args()
     fractions = a.fraction or [0.01, 0.1, 0.3]
+    gm = 1 if a.metric == "ip" else 0
 
     import torch
 
@@ -58,7 +60,7 @@ def main():
     x, q = make_rows(torch, n, d, a.nq, a.dist, a.seed)
     xh, qh = x.cpu().numpy(), q.cpu().numpy()
     ep = hipann.medoid(xh)
-    db = hipann.DiskannDeviceDB(xh)
+    db = hipann.DiskannDeviceDB(xh, graph_metric=gm)
     t0 = time.perf_counter()
     adj, bst = db.build_graph(R=a.R, L=a.L, alpha=a.alpha, entry_point=ep, batch_max=a.batch_max)
     build_s = time.perf_counter() - t0
@@ -72,27 +74,27 @@ def main():
         gone = np.concatenate([[ep], others[others != ep][:m - 1]]).astype(np.int64)  # the entry point leaves too
         live = np.setdiff1d(np.arange(n), gone)
         xl = np.ascontiguousarray(xh[live])
-        truth = B.exact_topk(torch, x[torch.from_numpy(live).cuda()], q, 10).cpu().numpy()
+        truth = B.exact_topk(torch, x[torch.from_numpy(live).cuda()], q, 10, metric=gm).cpu().numpy()
         rem, reb = [], []
         for _ in range(a.repeat):
-            h = hipann.DiskannDeviceDB(xh)
+            h = hipann.DiskannDeviceDB(xh, graph_metric=gm)
             h.register_graph(adj)
             t0 = time.perf_counter()
             nadj, nep, st = h.remove_ids(gone, ep, alpha=a.alpha, scratch_words=a.scratch_words)
             rem.append((time.perf_counter() - t0, st))
-            rec_rem, sst_rem = recall10(h, nep, qh, truth, a.L)
+            rec_rem, sst_rem = recall10(h, nep, qh, truth, a.L, gm)
             h.close()
             t0 = time.perf_counter()
-            h = hipann.DiskannDeviceDB(xl)
+            h = hipann.DiskannDeviceDB(xl, graph_metric=gm)
             _, rst = h.build_graph(R=a.R, L=a.L, alpha=a.alpha, entry_point=nep, batch_max=a.batch_max)
             reb.append((time.perf_counter() - t0, rst))
-            rec_reb, sst_reb = recall10(h, nep, qh, truth, a.L)
+            rec_reb, sst_reb = recall10(h, nep, qh, truth, a.L, gm)
             h.close()
         rem.sort(key=lambda r: r[0])
         reb.sort(key=lambda r: r[0])
         (rs, st), (bs, rst) = rem[len(rem) // 2], reb[len(reb) // 2]
         deg = (nadj != 0xFFFFFFFF).sum(1)
-        out = {"shape": a.shape, "dist": a.dist, "R": a.R, "L": a.L, "alpha": a.alpha, "fraction": frac,
+        out = {"shape": a.shape, "metric": a.metric, "dist": a.dist, "R": a.R, "L": a.L, "alpha": a.alpha, "fraction": frac,
                "removed": st["removed"], "repeat": a.repeat,
                "remove_s": round(rs, 4), "remove_s_all": [round(r[0], 4) for r in rem],
                "pool_s": round(st["pool_s"], 4), "prune_s": round(st["prune_s"], 4),
