@@ -1164,6 +1164,88 @@ void flat_shard_search(FlatIndex &ix, FlatShard &sh, int64_t nq, const float *xq
     flat_shard_finish(ix, sh, local, st);
 }
 
+
+// ---- range search (flat_range.hip): one shard's two passes ----
+// What the count pass resolved and the fill pass repeats: the kernel (image scan or direct), its parts, the launch
+// arguments.  nparts == 0: the shard has no rows.
+struct FlatRangePlan {
+    bool image = false;
+    int64_t nparts = 0, rpw = 0;
+    int qc = 0;
+    FlatRangeArgs a;
+};
+
+// the scan of one pass: every query against the shard's rows, counting (fill = false) or writing at the offsets
+static void flat_range_pass(FlatIndex &ix, FlatShard &sh, const FlatRangePlan &p, bool fill, float *D, int64_t *I,
+                            hipStream_t st) {
+    ScopedTiming t(ix.timer_main, st);
+    FlatRangeArgs a = p.a;
+    a.D = D, a.I = I;
+    if (p.image) return launch_flat_range_scan(a, fill, st);
+    for (int64_t q0 = 0; q0 < p.a.nq; q0 += p.qc) {
+        a.Q = p.a.Q + q0 * ix.d;
+        a.nq = std::min<int64_t>(p.qc, p.a.nq - q0);
+        a.counts = p.a.counts + q0 * p.nparts;
+        a.off = p.a.off + q0 * p.nparts;
+        launch_flat_range_direct(a, p.rpw, fill, st);
+    }
+}
+
+// Pass A and the offsets: lims_dev (nq + 1 int64, device) is written; the plan is what flat_range_pass(fill) needs.
+// nq >= 20 over finite rows: the bf16 image's threshold scan (the image and its bound terms built once, as form 4
+// does); otherwise — small batches, rows with a non-finite entry (max ‖x‖² or the residual maximum is not finite:
+// no bound exists) — the direct kernel.
+static FlatRangePlan flat_range_count(FlatIndex &ix, FlatShard &sh, int64_t nq, const float *xq, float radius,
+                                      int64_t *lims_dev, hipStream_t st) {
+    DeviceGuard g(sh.device);
+    FlatRangePlan p;
+    const int d = ix.d;
+    if (sh.n == 0) {
+        HIPANN_CHECK(hipMemsetAsync(lims_dev, 0, sizeof(int64_t) * (size_t)(nq + 1), st));
+        return p;
+    }
+    float xmax2 = 0.f;
+    p.image = nq >= kBlasThreshold;
+    if (p.image) {
+        xmax2 = flat_xmax2(ix, sh, d, st);
+        p.image = std::isfinite(xmax2);
+    }
+    if (p.image) {
+        ensure_b16_image(ix, sh, d, st);
+        p.image = std::isfinite(sh.bf16_rxmax);
+    }
+    FlatRangeArgs &a = p.a;
+    a.Q = xq, a.nq = nq, a.X = sh.xb, a.N = sh.n, a.d = d, a.metric = ix.metric, a.radius = radius;
+    a.label_offset = sh.label_offset;
+    if (p.image) {
+        const int QM = flat_range_query_tile();
+        const FlatSplit s = flat_split_geometry(256, ceil_div(nq, QM), sh.n, flat_bf16_tile_rows(), false);
+        p.nparts = s.nsplit;
+        a.tiles_per_split = s.tps;
+        sh.qimg.ensure(flat_bf16_img_bytes(nq, d, QM), sh.device);
+        sh.rg_cth.ensure(sizeof(float) * (size_t)nq, sh.device);
+        if (!sh.rg_stat.p) {
+            sh.rg_stat.ensure(sizeof(unsigned long long), sh.device);
+            HIPANN_CHECK(hipMemsetAsync(sh.rg_stat.p, 0, sizeof(unsigned long long), st));
+        }
+        launch_b16_tile_rows(xq, nq, d, QM, sh.qimg.p, st);
+        launch_flat_range_query_prep(xq, nq, d, ix.metric, radius, xmax2, sh.bf16_rxmax, sh.rg_cth.get<float>(), st);
+        a.qimg = sh.qimg.p, a.ximg = sh.xb16.p, a.xn = sh.xn.get<float>(), a.cth = sh.rg_cth.get<float>();
+        a.stat = sh.rg_stat.get<unsigned long long>();
+    } else {
+        p.nparts = flat_range_direct_parts(sh.n, &p.rpw);
+        p.qc = flat_range_direct_chunk(nq, d);
+    }
+    a.nparts = p.nparts;
+    HIPANN_REQUIRE(nq * p.nparts < (int64_t)0x7fffffff, "range search: too many (query, part) counts");
+    sh.rg_cnt.ensure(sizeof(int) * (size_t)(nq * p.nparts), sh.device);
+    sh.rg_off.ensure(sizeof(int64_t) * (size_t)(nq * p.nparts), sh.device);
+    a.counts = sh.rg_cnt.get<int>(), a.off = sh.rg_off.get<int64_t>();
+    flat_range_pass(ix, sh, p, false, nullptr, nullptr, st);
+    launch_flat_range_offsets(a.counts, nq, p.nparts, sh.rg_off.get<int64_t>(), lims_dev, st);
+    return p;
+}
+
 }  // namespace hipann
 
 // ================================================================================================
@@ -1511,6 +1593,149 @@ int hipann_flat_search_device(void *h, int64_t nq, const float *xq_dev, int64_t 
     });
 }
 
+static int flat_range_host(FlatIndex &ix, int64_t nq, const float *xq, float radius, int64_t *lims, float **D,
+                           int64_t **I) {
+    HIPANN_REQUIRE(lims && D && I, "null output");
+    HIPANN_REQUIRE(nq >= 0 && (nq == 0 || xq), "invalid arguments");
+    HIPANN_REQUIRE(radius == radius, "radius is NaN");
+    *D = nullptr, *I = nullptr;
+    std::fill(lims, lims + nq + 1, (int64_t)0);
+    if (nq == 0 || ix.ntotal() == 0) return 0;
+    const size_t qbytes = (size_t)nq * ix.d * sizeof(float), lbytes = sizeof(int64_t) * (size_t)(nq + 1);
+    ix.h_q.ensure(qbytes);
+    std::memcpy(ix.h_q.p, xq, qbytes);
+    const int np = (int)ix.shards.size();
+    // Pass A on every shard's own stream (devices run concurrently), its lims to a pinned buffer; one host
+    // synchronisation per shard, which sizes the result.
+    std::vector<FlatRangePlan> plan((size_t)np);
+    for (int p = 0; p < np; ++p) {
+        FlatShard &sh = *ix.shards[p];
+        DeviceGuard g(sh.device);
+        sh.q.ensure(qbytes, sh.device);
+        sh.rg_lims.ensure(lbytes, sh.device);
+        sh.h_rg.ensure(lbytes);
+        FenceScope fs(sh.fence, sh.stream, sh.device);
+        HIPANN_CHECK(hipMemcpyAsync(sh.q.p, ix.h_q.p, qbytes, hipMemcpyHostToDevice, sh.stream));
+        plan[(size_t)p] = flat_range_count(ix, sh, nq, sh.q.get<float>(), radius, sh.rg_lims.get<int64_t>(), sh.stream);
+        HIPANN_CHECK(hipMemcpyAsync(sh.h_rg.p, sh.rg_lims.p, lbytes, hipMemcpyDeviceToHost, sh.stream));
+    }
+    for (int p = 0; p < np; ++p) {
+        FlatShard &sh = *ix.shards[p];
+        DeviceGuard g(sh.device);
+        HIPANN_CHECK(hipStreamSynchronize(sh.stream));
+        ++ix.host_syncs;
+        const int64_t *hl = sh.h_rg.get<int64_t>();
+        for (int64_t q = 0; q < nq; ++q) lims[q + 1] += hl[q + 1] - hl[q];
+    }
+    for (int64_t q = 0; q < nq; ++q) lims[q + 1] += lims[q];
+    const int64_t total = lims[nq];
+    if (total == 0) return 0;
+    float *od = static_cast<float *>(std::malloc(sizeof(float) * (size_t)total));
+    int64_t *oi = static_cast<int64_t *>(std::malloc(sizeof(int64_t) * (size_t)total));
+    try {
+        HIPANN_REQUIRE(od && oi, "range search: out of host memory");
+        // Pass B per shard into its own buffers; one shard: straight into the result, several: per query in shard
+        // order, which is ascending label order.
+        std::vector<std::vector<float>> hd((size_t)np);
+        std::vector<std::vector<int64_t>> hi((size_t)np);
+        for (int p = 0; p < np; ++p) {
+            FlatShard &sh = *ix.shards[p];
+            const int64_t ts = sh.h_rg.get<int64_t>()[nq];
+            if (ts == 0) continue;
+            DeviceGuard g(sh.device);
+            sh.rg_d.ensure(sizeof(float) * (size_t)ts, sh.device);
+            sh.rg_i.ensure(sizeof(int64_t) * (size_t)ts, sh.device);
+            FenceScope fs(sh.fence, sh.stream, sh.device);
+            flat_range_pass(ix, sh, plan[(size_t)p], true, sh.rg_d.get<float>(), sh.rg_i.get<int64_t>(), sh.stream);
+            float *dd = od;
+            int64_t *di = oi;
+            if (np > 1) {
+                hd[(size_t)p].resize((size_t)ts), hi[(size_t)p].resize((size_t)ts);
+                dd = hd[(size_t)p].data(), di = hi[(size_t)p].data();
+            }
+            HIPANN_CHECK(hipMemcpyAsync(dd, sh.rg_d.p, sizeof(float) * (size_t)ts, hipMemcpyDeviceToHost, sh.stream));
+            HIPANN_CHECK(hipMemcpyAsync(di, sh.rg_i.p, sizeof(int64_t) * (size_t)ts, hipMemcpyDeviceToHost, sh.stream));
+        }
+        for (int p = 0; p < np; ++p) {
+            FlatShard &sh = *ix.shards[p];
+            if (sh.h_rg.get<int64_t>()[nq] == 0) continue;
+            DeviceGuard g(sh.device);
+            HIPANN_CHECK(hipStreamSynchronize(sh.stream));
+            ++ix.host_syncs;
+        }
+        if (np > 1) {
+            for (int64_t q = 0; q < nq; ++q) {
+                int64_t w = lims[q];
+                for (int p = 0; p < np; ++p) {
+                    const int64_t *hl = ix.shards[p]->h_rg.get<int64_t>();
+                    const int64_t c = hl[q + 1] - hl[q];
+                    if (c == 0) continue;
+                    std::memcpy(od + w, hd[(size_t)p].data() + hl[q], sizeof(float) * (size_t)c);
+                    std::memcpy(oi + w, hi[(size_t)p].data() + hl[q], sizeof(int64_t) * (size_t)c);
+                    w += c;
+                }
+            }
+        }
+    } catch (...) {
+        std::free(od);
+        std::free(oi);
+        throw;
+    }
+    *D = od, *I = oi;
+    return 0;
+}
+
+int hipann_flat_range_search(void *h, int64_t nq, const float *xq, float radius, int64_t *lims, float **D, int64_t **I,
+                             char *eb, int el) {
+    return guard_int(eb, el, [&]() -> int {
+        HIPANN_REQUIRE(h, "null index");
+        auto *ix = static_cast<IndexBase *>(h);
+        HIPANN_REQUIRE(ix->kind == Kind::Flat, "not a Flat index");
+        auto *fx = static_cast<FlatIndex *>(ix);
+        std::lock_guard<std::mutex> lk(fx->mu);
+        return flat_range_host(*fx, nq, xq, radius, lims, D, I);
+    });
+}
+
+void hipann_range_free(float *D, int64_t *I) {
+    std::free(D);
+    std::free(I);
+}
+
+int hipann_flat_range_search_device(void *h, int64_t nq, const float *xq_dev, float radius, int64_t *lims_dev,
+                                    float *D_dev, int64_t *I_dev, int64_t cap, void *stream, char *eb, int el) {
+    return guard_int(eb, el, [&]() -> int {
+        HIPANN_REQUIRE(h, "null index");
+        auto *ix = static_cast<IndexBase *>(h);
+        HIPANN_REQUIRE(ix->kind == Kind::Flat, "not a Flat index");
+        auto *fx = static_cast<FlatIndex *>(ix);
+        std::lock_guard<std::mutex> lk(fx->mu);
+        HIPANN_REQUIRE(fx->shards.size() == 1, "device search needs a single-device index");
+        HIPANN_REQUIRE(nq >= 0 && lims_dev && (nq == 0 || xq_dev) && cap >= 0 && (cap == 0 || (D_dev && I_dev)),
+                       "invalid arguments");
+        HIPANN_REQUIRE(radius == radius, "radius is NaN");
+        FlatShard &sh = *fx->shards[0];
+        hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = the default (null) stream
+        DeviceGuard g(sh.device);
+        FenceScope fs(sh.fence, st, sh.device);  // the previous call's kernels may still use this shard's scratch
+        if (nq == 0) {
+            HIPANN_CHECK(hipMemsetAsync(lims_dev, 0, sizeof(int64_t), st));
+            return 0;
+        }
+        const FlatRangePlan plan = flat_range_count(*fx, sh, nq, xq_dev, radius, lims_dev, st);
+        if (plan.nparts == 0) return 0;
+        // the one readback: the total, against cap
+        sh.h_rg.ensure(sizeof(int64_t));
+        HIPANN_CHECK(hipMemcpyAsync(sh.h_rg.p, lims_dev + nq, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIPANN_CHECK(hipStreamSynchronize(st));
+        ++fx->host_syncs;
+        const int64_t total = *sh.h_rg.get<int64_t>();
+        if (total > cap) return 1;
+        if (total > 0) flat_range_pass(*fx, sh, plan, true, D_dev, I_dev, st);
+        return 0;
+    });
+}
+
 int hipann_merge_topk_device(int metric, int nparts, int64_t nq, int64_t k, const float *D_parts,
                              const int64_t *I_parts, float *D_out, int64_t *I_out, void *stream, char *eb, int el) {
     return guard_int(eb, el, [&]() -> int {
@@ -1661,4 +1886,26 @@ extern "C" int hipann_debug_flat_scan_mode(const int *in, int nin, int *out, int
                        m.i8, m.i8_prep, m.kscan, m.k_user, m.pend_kind, m.rerun_form, m.need_qn, m.prep_qn};
     std::copy(o, o + 16, out);
     return 0;
+}
+
+// measurement hook (tools/flat_range_bench.py): the rows the range scan's bf16 filter has sent to the direct-form
+// recheck since the index was created, summed over its shards (synchronises their devices); -1 on a bad handle
+extern "C" int64_t hipann_debug_flat_range_survivors(void *h) {
+    try {
+        if (!h || static_cast<hipann::IndexBase *>(h)->kind != hipann::Kind::Flat) return -1;
+        auto *fx = static_cast<hipann::FlatIndex *>(h);
+        std::lock_guard<std::mutex> lk(fx->mu);
+        int64_t tot = 0;
+        for (auto &shp : fx->shards) {
+            if (!shp->rg_stat.p) continue;
+            hipann::DeviceGuard g(shp->device);
+            unsigned long long v = 0;
+            HIPANN_CHECK(hipDeviceSynchronize());
+            HIPANN_CHECK(hipMemcpy(&v, shp->rg_stat.p, sizeof(v), hipMemcpyDeviceToHost));
+            tot += (int64_t)v;
+        }
+        return tot;
+    } catch (...) {
+        return -1;
+    }
 }

@@ -16,6 +16,7 @@
 //
 // HBM traffic per batch ≈ Σ_items |ℓ|·4d  (each list read once per 32 queries probing it) instead
 // of Σ_queries Σ_probes |ℓ|·4d for the query-major reference.
+#include "rerank_rows.hpp"
 #include "runtime.hpp"
 #include "wave_topk.hpp"
 
@@ -1137,45 +1138,7 @@ void launch_ivf_merge(const float *pd, const int *pi, const int64_t *ids, int64_
 
 namespace hipann {
 
-// Direct-form sums of 4 rows against one query, lane-strided over the dims (e = lane, lane + 64, ...):
-// the loads of 4 strides are issued before their fmas (3 memory round trips at d = 768 instead of 12);
-// every accumulator still adds its terms in e order, so the sums are the one-stride loop's bit for bit.
-template <bool IP>
-__device__ __forceinline__ void rerank_rows4(const float *__restrict__ qp, const float *const (&xr)[4], int d, int lane,
-                                             float (&acc)[4]) {
-    int e = lane;
-    for (; e + 192 < d; e += 256) {
-        float qv[4], xv[4][4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            qv[s] = qp[e + 64 * s];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) xv[s][u] = xr[u][e + 64 * s];
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (IP) acc[u] = fmaf(qv[s], xv[s][u], acc[u]);
-                else {
-                    const float t = qv[s] - xv[s][u];
-                    acc[u] = fmaf(t, t, acc[u]);
-                }
-            }
-    }
-    for (; e < d; e += 64) {
-        const float qv = qp[e];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float xv = xr[u][e];
-            if (IP) acc[u] = fmaf(qv, xv, acc[u]);
-            else {
-                const float t = qv - xv;
-                acc[u] = fmaf(t, t, acc[u]);
-            }
-        }
-    }
-}
+// rerank_rows4 (the direct-form sums of 4 rows against one query): rerank_rows.hpp, shared with flat_range.hip
 
 #ifndef HIPANN_RR_OLDSEL
 #define HIPANN_RR_OLDSEL 0  // A/B builds: the 32-barrier block select instead of rerank_wave_select

@@ -310,6 +310,11 @@ struct FlatShard {
     unsigned flag_seq = 0;   // the last token posted
     DevBuf app_stat;         // an append's new-row maxima (‖x‖², int8 residual, bf16 residual²)
     hipEvent_t done = nullptr;  // multi-device search: the shard's launch phase has drained (shard 0's stream waits)
+    // range search (flat_range.hip): the filter's per-query constants, the counts and offsets per (query, part), the
+    // host variant's lims / distances / labels, the filter survivors' running count (zeroed at allocation) and the
+    // pinned word lims[nq] is read back into
+    DevBuf rg_cth, rg_cnt, rg_off, rg_lims, rg_d, rg_i, rg_stat;
+    HostBuf h_rg;
 };
 
 // What a deferred Flat shard search (flat_shard_search with a FlatPending) leaves to flat_shard_finish: the exact
@@ -693,6 +698,34 @@ void launch_b16_row_residual2(const float *X, int64_t n, int d, float *out, hipS
 void launch_flat_bf16_topk(const float *Q, const float *qn, int64_t nq, void *qimg, const void *ximg, const float *xn,
                            int64_t N, int d, int metric, int k, int nsplit, int64_t tiles_per_split, float *pd, int *pi,
                            const float *seed, bool image_ready, hipStream_t st);
+// flat_range.hip — range search.  One launch's arguments: the image scan (qimg / ximg / xn / cth set; nparts = row
+// splits of tiles_per_split tiles) or the direct kernel (nparts = waves).  counts / off: [query][nparts].
+struct FlatRangeArgs {
+    const float *Q = nullptr;  // the queries (fp32) and their count
+    int64_t nq = 0;
+    const float *X = nullptr;  // the rows (fp32) and their count
+    int64_t N = 0;
+    int d = 0, metric = kL2;
+    float radius = 0.f;
+    int64_t nparts = 1, tiles_per_split = 0;
+    const void *qimg = nullptr, *ximg = nullptr;
+    const float *xn = nullptr, *cth = nullptr;
+    int *counts = nullptr;
+    const int64_t *off = nullptr;
+    float *D = nullptr;
+    int64_t *I = nullptr;
+    int64_t label_offset = 0;
+    unsigned long long *stat = nullptr;  // += the filter's survivors (count pass)
+};
+int flat_range_query_tile();
+void launch_flat_range_query_prep(const float *Q, int64_t nq, int d, int metric, float radius, float xmax2, float rxmax,
+                                  float *cth, hipStream_t st);
+void launch_flat_range_scan(const FlatRangeArgs &a, bool fill, hipStream_t st);
+void launch_flat_range_offsets(const int *counts, int64_t nq, int64_t nparts, int64_t *off, int64_t *lims,
+                               hipStream_t st);
+int64_t flat_range_direct_parts(int64_t n, int64_t *rows_per_wave);
+int flat_range_direct_chunk(int64_t nq, int d);
+void launch_flat_range_direct(const FlatRangeArgs &a, int64_t rows_per_wave, bool fill, hipStream_t st);
 // bounded passes of the 64-dim K-step kernel (flat_b16k64.hip): candidate buffers, their bound and select
 // (k64_on: the caller's HIPANN_B16_K64 switch)
 bool flat_bf16_resumable(int64_t nq, int d, int k, bool k64_on);

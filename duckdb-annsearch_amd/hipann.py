@@ -94,6 +94,9 @@ def lib() -> C.CDLL:
             "hipann_flat_reconstruct": ([vp, i64, f, cp, i32], i32),
             "hipann_flat_create_device": ([i32, i32, vp, i64, i32, i32, i64, cp, i32], vp),
             "hipann_flat_search_device": ([vp, i64, vp, i64, vp, vp, vp, cp, i32], i32),
+            "hipann_flat_range_search": ([vp, i64, f, C.c_float, i64p, C.POINTER(f), C.POINTER(i64p), cp, i32], i32),
+            "hipann_range_free": ([f, i64p], None),
+            "hipann_flat_range_search_device": ([vp, i64, vp, C.c_float, vp, vp, vp, i64, vp, cp, i32], i32),
             "hipann_flat_set_form": ([vp, i32], i32),
             "hipann_flat_get_form": ([vp], i32),
             "hipann_last_search_path": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], i32),
@@ -353,6 +356,24 @@ class HipIndexFlat(_FlatForm, _Handle):
                                         eb, 1024), eb)
         return D, I
 
+    def range_search(self, x, radius: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """faiss::IndexFlat::range_search: ``(lims, D, I)``; query q's rows are ``[lims[q], lims[q+1])`` of D / I, in
+        ascending label order — every row with Σ(q−x)² < radius (L2) or q·x > radius (IP)."""
+        x = _f32_2d(x, self.d)
+        n = x.shape[0]
+        lims = np.zeros(n + 1, np.int64)
+        dp, ip = C.POINTER(C.c_float)(), C.POINTER(C.c_int64)()
+        eb = _err()
+        _check(lib().hipann_flat_range_search(self._h, n, _ptr(x, C.c_float), radius, _ptr(lims, C.c_int64),
+                                              C.byref(dp), C.byref(ip), eb, 1024), eb)
+        total = int(lims[n])
+        try:
+            D = np.ctypeslib.as_array(dp, (total,)).copy() if total else np.empty(0, np.float32)
+            I = np.ctypeslib.as_array(ip, (total,)).copy() if total else np.empty(0, np.int64)
+        finally:
+            lib().hipann_range_free(dp, ip)
+        return lims, D, I
+
     def reconstruct_n(self, i0: int, n: int) -> np.ndarray:
         """faiss::Index::reconstruct_n: rows [i0, i0 + n) back to host in one call."""
         out = np.empty((max(n, 0), self.d), np.float32)
@@ -384,6 +405,18 @@ class HipIndexFlatDevice(_FlatForm, _Handle):
         eb = _err()
         _check(lib().hipann_flat_search_device(self._h, nq, C.c_void_p(xq_ptr), k, C.c_void_p(d_ptr),
                                                C.c_void_p(i_ptr), C.c_void_p(stream or None), eb, 1024), eb)
+
+
+    def range_search_device(self, nq: int, xq_ptr: int, radius: float, lims_ptr: int, d_ptr: int, i_ptr: int, cap: int,
+                            stream: int = 0) -> bool:
+        """hipann_flat_range_search_device: ``lims_ptr`` (nq + 1 int64, device) is always written; ``d_ptr`` /
+        ``i_ptr`` (``cap`` entries) only when the result fits.  True when filled, False when ``lims[nq] > cap``."""
+        eb = _err()
+        rc = lib().hipann_flat_range_search_device(self._h, nq, C.c_void_p(xq_ptr), radius, C.c_void_p(lims_ptr),
+                                                   C.c_void_p(d_ptr or None), C.c_void_p(i_ptr or None), cap,
+                                                   C.c_void_p(stream or None), eb, 1024)
+        _check(min(rc, 0), eb)
+        return rc == 0
 
 
 def merge_topk_device(metric: int, nparts: int, nq: int, k: int, d_parts: int, i_parts: int, d_out: int, i_out: int,

@@ -179,6 +179,32 @@ void *hipann_flat_create_device(int d, int metric, const float *xb_dev, int64_t 
 int hipann_flat_search_device(void *index, int64_t nq, const float *xq_dev, int64_t k, float *D_dev,
                               int64_t *I_dev, void *stream, char *err_buf, int err_len);
 
+/* faiss::IndexFlat::range_search.  lims: nq+1 int64 (host), lims[0] = 0; query q's results are
+ * [lims[q], lims[q+1]) of *D / *I, ordered by ascending label.  *D / *I: host buffers the library
+ * allocates (NULL when lims[nq] == 0); release with hipann_range_free.  L2: rows with
+ * direct-form Σ(q−x)² < radius; IP: rows with q·x > radius (strict, as FAISS).  0 / -1.
+ * Membership and the distance written are the direct fp32 form every other entry point returns (a row in a top-k
+ * result of the exact forms and in a range result carries the same bits); any number of rows may qualify
+ * (HIPANN_MAX_K does not apply).  nq == 0 writes lims[0] = 0; an empty index returns all-zero lims; a NaN radius is an
+ * error; ±inf is legal (nothing or everything, by the strict comparison).  nq >= 20 over rows without a non-finite
+ * entry: a threshold scan over the tiled bf16 image of HIPANN_FLAT_FORM_BF16_EXACT (built at the first such call) as a
+ * filter that can only add rows, each survivor rechecked in the direct form; otherwise a direct-form scan.  Both run
+ * twice (count, then fill at the offsets of a device prefix sum), so the result is the same bits in the same order on
+ * every run.  Multi-device handles: every shard answers its row range, concatenated per query in shard order.
+ * hipann_last_search_path is left as the last top-k call set it; hipann_last_kernel_ms(which = 0) times the two scan
+ * passes; host synchronisations (two per shard; one when nothing qualifies) count in hipann_flat_host_syncs. */
+int hipann_flat_range_search(void *index, int64_t nq, const float *xq, float radius, int64_t *lims, float **D,
+                             int64_t **I, char *err_buf, int err_len);
+void hipann_range_free(float *D, int64_t *I);
+
+/* Device-resident variant: lims_dev (nq+1 int64) is always written; D_dev / I_dev (cap entries) are
+ * filled only when lims[nq] <= cap.  Returns 0, 1 when the result did not fit (read lims[nq] and
+ * call again), or -1.  Asynchronous on `stream` except for the one readback of the total.  Single-device handles,
+ * like the other _device calls. */
+int hipann_flat_range_search_device(void *index, int64_t nq, const float *xq_dev, float radius, int64_t *lims_dev,
+                                    float *D_dev, int64_t *I_dev, int64_t cap, void *stream, char *err_buf,
+                                    int err_len);
+
 /* k-way merge of `nparts` partial results laid out [part][nq][k] (device memory) into [nq][k]:
  * the k best by (distance, label) — ascending for L2, descending for IP; -1 labels are ignored.
  * The merge step after the RCCL allgather of per-GPU partial top-k. */
