@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <numeric>
 
 using namespace hipann;
@@ -258,6 +259,8 @@ IvfIndex::~IvfIndex() {
         for (hipEvent_t e : s->app_ev)
             if (e) (void)hipEventDestroy(e);
         if (s->app_sync) (void)hipEventDestroy(s->app_sync);
+        for (hipEvent_t e : s->rg_ev)
+            if (e) (void)hipEventDestroy(e);
         if (s->stream) (void)hipStreamDestroy(s->stream);
     }
 }
@@ -831,6 +834,140 @@ void ivf_host_rerun(IvfBatch &b) {
     }
     launch_ivf_scatter_results(sh.fD.get<float>(), sh.fI.get<int64_t>(), sh.flagged.get<int>(), nf, kout, b.D, b.I, b.st);
     HIPANN_CHECK(hipMemcpyAsync(sh.coarse_i.p, sh.coarse_save.p, pbytes, hipMemcpyDeviceToDevice, b.st));
+}
+
+// ---- range search (ivf_range.hip): one query slice on one shard, the stages in their order on the stream ----
+// The slots' masks take 256 bytes per (query, probe, chunk) slot; a query owns at most as many slots as its nprobe
+// longest lists have chunks (ivf_range_query_slots: the host's bound, the device knows the exact count only after the
+// plan).  A batch whose masks would exceed this budget runs in query slices: 64 MiB is the smallest power of two that
+// keeps the headline batch (1024 queries × 32 probes × 5 chunks × 256 B = 42 MB) in one slice.
+constexpr size_t kRangeMaskBudget = (size_t)64 << 20;
+
+int64_t ivf_range_query_slots(const IvfShard &sh, int np) {
+    std::vector<int64_t> nch;
+    for (int64_t len : sh.h_len)
+        if (len > 0) nch.push_back(ceil_div(len, ivf_chunk_rows()));
+    if ((int64_t)nch.size() > np) {
+        std::nth_element(nch.begin(), nch.begin() + np, nch.end(), std::greater<int64_t>());
+        nch.resize((size_t)np);
+    }
+    return std::max<int64_t>(1, std::accumulate(nch.begin(), nch.end(), (int64_t)0));
+}
+
+int64_t ivf_range_slice_queries(int64_t query_slots) {
+    return std::max<int64_t>(1, (int64_t)(kRangeMaskBudget / ((size_t)query_slots * 256)));
+}
+
+struct IvfRangeSlice {
+    float radius = 0.f;
+    bool image = false;  // the fp16 image scan (else the direct kernel)
+    int64_t slots = 0;   // the host's bound of the slice's slots
+    IvfRangeArgs a;
+    IvfPlanView plan{};
+};
+
+// a timed call's stage marks (scan | offsets | fill: begin and end each), read by hipann_debug_ivf_range_info
+void ivf_range_mark(IvfIndex &ix, IvfShard &sh, int i, hipStream_t st) {
+    if (!ix.timer_main.on) return;
+    if (!sh.rg_ev[i]) HIPANN_CHECK(hipEventCreate(&sh.rg_ev[i]));
+    HIPANN_CHECK(hipEventRecord(sh.rg_ev[i], st));
+    if (i == 0) sh.rg_ev_fill = false;
+    if (i == 5) sh.rg_ev_fill = true;
+}
+
+// The scan the slice takes — the fp16 image (built at its first use; its queries are prepared with the batch) or,
+// where ensure_half_codes declines or the image scan does not hold the dimension, the direct kernel — as the mode
+// the shared stages read: the plan's group, the rerank bound's row terms, the query preparation.
+void ivf_range_mode(IvfBatch &b, IvfRangeSlice &r) {
+    IvfShard &sh = b.sh;
+    const int d = b.ix.d;
+    r.image = ivf_mfma_h_supported(d, kRerankK) && (b.ix.metric == kIP || sh.xnorm.p) &&
+              ensure_half_codes(sh, d, b.ix.nlist, b.st);
+    IvfScanMode &m = b.m;
+    m.image = r.image ? 1 : 0;
+    m.form = r.image ? kFormSplit2 : kFormDirect;
+    m.exact = m.tiled = r.image;
+    m.group = r.image ? ivf_mfma_h_group(d) : ivf_group_size(kFormDirect, d);
+}
+
+// the masks and counts of every (query, probe, chunk) slot
+void ivf_range_scan(IvfBatch &b, IvfRangeSlice &r) {
+    IvfShard &sh = b.sh;
+    const int64_t nq = b.nq, slots = nq * ivf_range_query_slots(sh, b.np);
+    HIPANN_REQUIRE(slots < (int64_t)0x7fffffff, "range search: too many slots");
+    r.slots = slots;
+    sh.rg_mask.ensure((size_t)slots * 256, sh.device);
+    sh.rg_cnt.ensure(sizeof(int) * (size_t)slots, sh.device);
+    if (!sh.rg_stat.p) {
+        sh.rg_stat.ensure(2 * sizeof(unsigned long long), sh.device);
+        HIPANN_CHECK(hipMemsetAsync(sh.rg_stat.p, 0, 2 * sizeof(unsigned long long), b.st));
+    }
+    r.plan = b.plan();
+    IvfRangeArgs &a = r.a;
+    a.Q = b.xq, a.nq = nq, a.d = b.ix.d, a.metric = b.ix.metric, a.radius = r.radius, a.codes = sh.codes;
+    a.probes = sh.coarse_i.get<int64_t>(), a.max_nch = std::max(sh.max_nch, 1);
+    a.mask = sh.rg_mask.get<unsigned>(), a.counts = sh.rg_cnt.get<int>();
+    RoctxRange rr("hipann.ivf.range_scan");
+    ScopedTiming t(b.ix.timer_main, b.st);
+    ivf_range_mark(b.ix, sh, 0, b.st);
+    if (r.image) {
+        sh.rg_par.ensure(2 * sizeof(float) * (size_t)nq, sh.device);
+        launch_ivf_range_query_prep(b.xq, nq, a.d, a.metric, r.radius, b.xmax2, sh.half_rxmax, sh.hits.get<float>(),
+                                    sh.hres.get<float>() + nq, sh.rg_par.p, b.st);
+        a.qsplit = sh.hsplit.p, a.par = sh.rg_par.p, a.codes_h = sh.codes_h.p;
+        a.tpass_off = sh.tpass_off.get<int64_t>(), a.xn = sh.xnorm.get<float>();
+        a.stat = sh.rg_stat.get<unsigned long long>();
+        launch_ivf_range_scan_h(a, r.plan, ivf_max_items(nq, b.np, b.ix.nlist, sh.max_nch, sh.n, b.m.group), b.st);
+    } else {
+        launch_ivf_range_direct(a, r.plan, b.st);
+    }
+    ivf_range_mark(b.ix, sh, 1, b.st);
+}
+
+// slot offsets, pair limits and the slice's lims (chain: continuing from lims[0], the slice before)
+void ivf_range_offsets(IvfBatch &b, IvfRangeSlice &r, int64_t *lims_dev, bool chain) {
+    IvfShard &sh = b.sh;
+    sh.rg_soff.ensure(sizeof(int64_t) * ((size_t)r.slots + 1), sh.device);
+    sh.rg_plim.ensure(sizeof(int64_t) * ((size_t)b.nq * b.np + 1), sh.device);
+    ivf_range_mark(b.ix, sh, 2, b.st);
+    launch_ivf_range_offsets(r.a.counts, r.plan.slot_off, b.nq, b.np, chain, sh.rg_soff.get<int64_t>(),
+                             sh.rg_plim.get<int64_t>(), lims_dev, b.st);
+    ivf_range_mark(b.ix, sh, 3, b.st);
+}
+
+// Coarse step, plan, scan and offsets of one slice: lims_dev (nq + 1, device) is written, the slice is ready to fill.
+IvfRangeSlice ivf_range_count(IvfIndex &ix, IvfShard &sh, int np, int64_t nq, const float *xq, float radius,
+                              int64_t *lims_dev, bool chain, hipStream_t st) {
+    DeviceGuard g(sh.device);
+    const IvfSearchOpts opts{};
+    IvfBatch b{ix, sh, nq, xq, 1, 1, nullptr, nullptr, st, opts, np, {}, false, *sh.quant->shards[0]};
+    IvfRangeSlice r;
+    r.radius = radius;
+    ivf_plan_scratch(b);
+    CcntReset ccnt_reset{b.ccnt_cur, ix.nlist, st, true};
+    ivf_range_mode(b, r);
+    ivf_prepare_queries(b);
+    ivf_coarse_and_plan(b);
+    ccnt_reset.armed = false;
+    ivf_range_scan(b, r);
+    ivf_range_offsets(b, r, lims_dev, chain);
+    return r;
+}
+
+// (distance, id) of the slice's admitted rows at their offsets in D / I
+void ivf_range_fill(IvfIndex &ix, IvfShard &sh, const IvfRangeSlice &r, float *D, int64_t *I, hipStream_t st) {
+    DeviceGuard g(sh.device);
+    RoctxRange rr("hipann.ivf.range_fill");
+    ScopedTiming t(ix.timer_main, st);
+    ivf_range_mark(ix, sh, 4, st);
+    launch_ivf_range_fill(r.a, r.plan, sh.ids, sh.rg_soff.get<int64_t>(), D, I, st);
+    ivf_range_mark(ix, sh, 5, st);
+}
+
+// A sliced batch's probe lists, kept for hipann_ivf_last_probes (the coarse step's buffer holds one slice's).
+void ivf_range_keep_probes(IvfShard &sh, int64_t q0, int64_t nqs, int np, hipStream_t st) {
+    HIPANN_CHECK(hipMemcpyAsync(sh.rg_probes.get<int64_t>() + q0 * np, sh.coarse_i.p, sizeof(int64_t) * (size_t)nqs * np,
+                                hipMemcpyDeviceToDevice, st));
 }
 
 }  // namespace
@@ -1554,6 +1691,201 @@ int hipann_ivf_search_probes_device(void *h, int64_t nq, const float *xq_dev, co
     });
 }
 
+// Host variant.  Per query slice: every shard counts (coarse step, plan, scan, offsets) on its own stream and hands
+// back its per-pair limits; one synchronisation sizes the slice; the shards fill; the host appends each query's
+// slices in probe order (a pair's rows live on the one shard that owns its list).
+static int ivf_range_host(IvfIndex &ix, int nprobe, int64_t nq, const float *xq, float radius, int64_t *lims, float **D,
+                          int64_t **I) {
+    HIPANN_REQUIRE(lims && D && I, "null output");
+    HIPANN_REQUIRE(nq >= 0 && (nq == 0 || xq), "invalid arguments");
+    HIPANN_REQUIRE(radius == radius, "radius is NaN");
+    *D = nullptr, *I = nullptr;
+    std::fill(lims, lims + nq + 1, (int64_t)0);
+    const int np = std::min(nprobe > 0 ? nprobe : ix.nprobe, ix.nlist);
+    ix.last_nq = ix.ntotal() == 0 ? 0 : nq;
+    ix.last_np = np;
+    if (nq == 0 || ix.ntotal() == 0) return 0;
+    const size_t qbytes = (size_t)nq * ix.d * sizeof(float);
+    ix.h_q.ensure(qbytes);
+    std::memcpy(ix.h_q.p, xq, qbytes);
+    const int ns = (int)ix.shards.size();
+    int64_t query_slots = 1;
+    for (auto &shp : ix.shards) query_slots = std::max(query_slots, ivf_range_query_slots(*shp, np));
+    const int64_t qs = ivf_range_slice_queries(query_slots);
+    const bool sliced = qs < nq;
+    for (auto &shp : ix.shards) {
+        IvfShard &sh = *shp;
+        DeviceGuard g(sh.device);
+        sh.q.ensure(qbytes, sh.device);
+        sh.coarse_i.ensure(sizeof(int64_t) * (size_t)nq * np, sh.device);  // (a slice's ensure keeps it)
+        FenceScope fs(sh.fence, sh.stream, sh.device);
+        HIPANN_CHECK(hipMemcpyAsync(sh.q.p, ix.h_q.p, qbytes, hipMemcpyHostToDevice, sh.stream));
+    }
+    IvfShard &s0 = *ix.shards[0];
+    if (sliced) s0.rg_probes.ensure(sizeof(int64_t) * (size_t)nq * np, s0.device);
+    float *od = nullptr;
+    int64_t *oi = nullptr;
+    int64_t run = 0;
+    try {
+        std::vector<IvfRangeSlice> sl((size_t)ns);
+        std::vector<std::vector<float>> hd((size_t)ns);
+        std::vector<std::vector<int64_t>> hi((size_t)ns);
+        for (int64_t q0 = 0; q0 < nq; q0 += qs) {
+            const int64_t nqs = std::min(qs, nq - q0), npairs = nqs * np;
+            const size_t pbytes = sizeof(int64_t) * (size_t)(npairs + 1);
+            for (int p = 0; p < ns; ++p) {
+                IvfShard &sh = *ix.shards[p];
+                DeviceGuard g(sh.device);
+                sh.rg_lims.ensure(sizeof(int64_t) * (size_t)(nqs + 1), sh.device);
+                sh.h_rg.ensure(pbytes);
+                FenceScope fs(sh.fence, sh.stream, sh.device);
+                sl[(size_t)p] = ivf_range_count(ix, sh, np, nqs, sh.q.get<float>() + q0 * ix.d, radius,
+                                                sh.rg_lims.get<int64_t>(), false, sh.stream);
+                HIPANN_CHECK(hipMemcpyAsync(sh.h_rg.p, sh.rg_plim.p, pbytes, hipMemcpyDeviceToHost, sh.stream));
+                if (sliced && p == 0) ivf_range_keep_probes(sh, q0, nqs, np, sh.stream);
+            }
+            int64_t total = 0;
+            for (int p = 0; p < ns; ++p) {
+                IvfShard &sh = *ix.shards[p];
+                DeviceGuard g(sh.device);
+                HIPANN_CHECK(hipStreamSynchronize(sh.stream));
+                total += sh.h_rg.get<int64_t>()[npairs];
+            }
+            if (total > 0) {
+                float *nd = static_cast<float *>(std::realloc(od, sizeof(float) * (size_t)(run + total)));
+                if (nd) od = nd;
+                int64_t *ni = static_cast<int64_t *>(std::realloc(oi, sizeof(int64_t) * (size_t)(run + total)));
+                if (ni) oi = ni;
+                HIPANN_REQUIRE(nd && ni, "range search: out of host memory");
+            }
+            for (int p = 0; p < ns; ++p) {
+                IvfShard &sh = *ix.shards[p];
+                const int64_t ts = sh.h_rg.get<int64_t>()[npairs];
+                if (ts == 0) continue;
+                DeviceGuard g(sh.device);
+                sh.rg_d.ensure(sizeof(float) * (size_t)ts, sh.device);
+                sh.rg_i.ensure(sizeof(int64_t) * (size_t)ts, sh.device);
+                FenceScope fs(sh.fence, sh.stream, sh.device);
+                ivf_range_fill(ix, sh, sl[(size_t)p], sh.rg_d.get<float>(), sh.rg_i.get<int64_t>(), sh.stream);
+                float *dd = od + run;
+                int64_t *di = oi + run;
+                if (ns > 1) {
+                    hd[(size_t)p].resize((size_t)ts), hi[(size_t)p].resize((size_t)ts);
+                    dd = hd[(size_t)p].data(), di = hi[(size_t)p].data();
+                }
+                HIPANN_CHECK(hipMemcpyAsync(dd, sh.rg_d.p, sizeof(float) * (size_t)ts, hipMemcpyDeviceToHost, sh.stream));
+                HIPANN_CHECK(hipMemcpyAsync(di, sh.rg_i.p, sizeof(int64_t) * (size_t)ts, hipMemcpyDeviceToHost, sh.stream));
+            }
+            for (int p = 0; p < ns; ++p) {
+                IvfShard &sh = *ix.shards[p];
+                if (sh.h_rg.get<int64_t>()[npairs] == 0) continue;
+                DeviceGuard g(sh.device);
+                HIPANN_CHECK(hipStreamSynchronize(sh.stream));
+            }
+            // the slice's lims; several shards: each pair's rows from the shard that holds them, in pair order
+            int64_t w = run;
+            for (int64_t i = 0; i < npairs; ++i) {
+                if (i % np == 0) lims[q0 + i / np] = w;
+                for (int p = 0; p < ns; ++p) {
+                    const int64_t *pl = ix.shards[p]->h_rg.get<int64_t>();
+                    const int64_t c = pl[i + 1] - pl[i];
+                    if (c == 0) continue;
+                    if (ns > 1) {
+                        std::memcpy(od + w, hd[(size_t)p].data() + pl[i], sizeof(float) * (size_t)c);
+                        std::memcpy(oi + w, hi[(size_t)p].data() + pl[i], sizeof(int64_t) * (size_t)c);
+                    }
+                    w += c;
+                }
+            }
+            run = w;
+        }
+        lims[nq] = run;
+        if (sliced) {
+            DeviceGuard g(s0.device);
+            HIPANN_CHECK(hipMemcpyAsync(s0.coarse_i.p, s0.rg_probes.p, sizeof(int64_t) * (size_t)nq * np,
+                                        hipMemcpyDeviceToDevice, s0.stream));
+            HIPANN_CHECK(hipStreamSynchronize(s0.stream));
+        }
+    } catch (...) {
+        std::free(od);
+        std::free(oi);
+        throw;
+    }
+    *D = od, *I = oi;
+    return 0;
+}
+
+int hipann_ivf_range_search(void *h, int nprobe, int64_t nq, const float *xq, float radius, int64_t *lims, float **D,
+                            int64_t **I, char *eb, int el) {
+    return guard_int(eb, el, [&]() -> int {
+        HIPANN_REQUIRE(h, "null index");
+        auto *ix = static_cast<IndexBase *>(h);
+        HIPANN_REQUIRE(ix->kind == Kind::IVF, "not an IVFFlat index");
+        auto *vx = static_cast<IvfIndex *>(ix);
+        std::lock_guard<std::mutex> lk(vx->mu);
+        return ivf_range_host(*vx, nprobe, nq, xq, radius, lims, D, I);
+    });
+}
+
+int hipann_ivf_range_search_device(void *h, int nprobe, int64_t nq, const float *xq_dev, float radius, int64_t *lims_dev,
+                                   float *D_dev, int64_t *I_dev, int64_t cap, void *stream, char *eb, int el) {
+    return guard_int(eb, el, [&]() -> int {
+        HIPANN_REQUIRE(h, "null index");
+        auto *ix = static_cast<IndexBase *>(h);
+        HIPANN_REQUIRE(ix->kind == Kind::IVF, "not an IVFFlat index");
+        auto *vx = static_cast<IvfIndex *>(ix);
+        std::lock_guard<std::mutex> lk(vx->mu);
+        HIPANN_REQUIRE(vx->shards.size() == 1, "device search needs a single-device index");
+        HIPANN_REQUIRE(nq >= 0 && lims_dev && (nq == 0 || xq_dev) && cap >= 0 && (cap == 0 || (D_dev && I_dev)),
+                       "invalid arguments");
+        HIPANN_REQUIRE(radius == radius, "radius is NaN");
+        IvfShard &sh = *vx->shards[0];
+        hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = the default (null) stream
+        DeviceGuard g(sh.device);
+        FenceScope fs(sh.fence, st, sh.device);  // the previous call's kernels may still use this shard's scratch
+        const int np = std::min(nprobe > 0 ? nprobe : vx->nprobe, vx->nlist);
+        vx->last_nq = sh.live == 0 ? 0 : nq;
+        vx->last_np = np;
+        if (nq == 0 || sh.live == 0) {
+            HIPANN_CHECK(hipMemsetAsync(lims_dev, 0, sizeof(int64_t) * (size_t)(nq + 1), st));
+            return 0;
+        }
+        const int64_t qs = ivf_range_slice_queries(ivf_range_query_slots(sh, np));
+        const bool sliced = qs < nq;
+        sh.coarse_i.ensure(sizeof(int64_t) * (size_t)nq * np, sh.device);
+        if (sliced) sh.rg_probes.ensure(sizeof(int64_t) * (size_t)nq * np, sh.device);
+        // One slice: count, read the total back, fill.  Several: every slice counts first (lims chained from slice to
+        // slice), the total is read back, and only a result that fits runs the slices again, each with its fill.
+        IvfRangeSlice one;
+        for (int64_t q0 = 0; q0 < nq; q0 += qs) {
+            const int64_t nqs = std::min(qs, nq - q0);
+            one = ivf_range_count(*vx, sh, np, nqs, xq_dev + q0 * vx->d, radius, lims_dev + q0, q0 > 0, st);
+            if (sliced) ivf_range_keep_probes(sh, q0, nqs, np, st);
+        }
+        if (sliced)
+            HIPANN_CHECK(hipMemcpyAsync(sh.coarse_i.p, sh.rg_probes.p, sizeof(int64_t) * (size_t)nq * np,
+                                        hipMemcpyDeviceToDevice, st));
+        sh.h_rg.ensure(sizeof(int64_t));
+        HIPANN_CHECK(hipMemcpyAsync(sh.h_rg.p, lims_dev + nq, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIPANN_CHECK(hipStreamSynchronize(st));  // the one readback: the total, against cap
+        const int64_t total = *sh.h_rg.get<int64_t>();
+        if (total > cap) return 1;
+        if (total == 0) return 0;
+        if (!sliced) {
+            ivf_range_fill(*vx, sh, one, D_dev, I_dev, st);
+            return 0;
+        }
+        for (int64_t q0 = 0; q0 < nq; q0 += qs) {
+            const int64_t nqs = std::min(qs, nq - q0);
+            const IvfRangeSlice r = ivf_range_count(*vx, sh, np, nqs, xq_dev + q0 * vx->d, radius, lims_dev + q0, q0 > 0, st);
+            ivf_range_fill(*vx, sh, r, D_dev, I_dev, st);
+        }
+        HIPANN_CHECK(hipMemcpyAsync(sh.coarse_i.p, sh.rg_probes.p, sizeof(int64_t) * (size_t)nq * np,
+                                    hipMemcpyDeviceToDevice, st));
+        return 0;
+    });
+}
+
 int hipann_ivf_add(void *h, int64_t n, const float *xb, const int64_t *ids, char *eb, int el) {
     return guard_int(eb, el, [&]() -> int {
         HIPANN_REQUIRE(h, "null index");
@@ -1811,7 +2143,27 @@ int hipann_debug_ivf_info(void *h, const char *name, double *out) {
     else if (s == "seeded") *out = sh->dbg_seeded;
     else if (s == "cand_off") *out = (double)sh->dbg_cand_off;
     else if (s == "group") *out = sh->dbg_img == 2 ? ivf_mfma_i8_group(d) : sh->dbg_img == 1 ? ivf_mfma_h_group(d) : 0;
-    else return -1;
+    else if (s == "range_survivors" || s == "range_admitted") {
+        // the range scan's filter since creation: rows sent to the recheck, rows the recheck admitted
+        unsigned long long v[2] = {0, 0};
+        if (sh->rg_stat.p) {
+            DeviceGuard g(sh->device);
+            if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(v, sh->rg_stat.p, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
+                return -1;
+        }
+        *out = (double)v[s == "range_admitted" ? 1 : 0];
+    } else if (s == "range_scan_ms" || s == "range_offsets_ms" || s == "range_fill_ms") {
+        // the stages of the last range call made with timing on (its last slice); 0 for a stage that did not run
+        const int i = s == "range_scan_ms" ? 0 : s == "range_offsets_ms" ? 2 : 4;
+        float ms = 0.f;
+        if (sh->rg_ev[i] && sh->rg_ev[i + 1] && (i < 4 || sh->rg_ev_fill)) {
+            DeviceGuard g(sh->device);
+            if (hipEventSynchronize(sh->rg_ev[i + 1]) != hipSuccess ||
+                hipEventElapsedTime(&ms, sh->rg_ev[i], sh->rg_ev[i + 1]) != hipSuccess)
+                return -1;
+        }
+        *out = ms;
+    } else return -1;
     return 0;
 }
 

@@ -447,6 +447,13 @@ struct IvfShard {
     HostBuf fb_host;
     uint64_t fb_seq = 0, fb_seen = 0;
     DevBuf probe_D, probe_I;
+    // range search (ivf_range.hip): the queries' (a_q, c_q), the slots' masks and counts, slot offsets, pair limits,
+    // lims, the shard's results, the filter's counters (survivors, admitted), a sliced batch's probe lists; the
+    // readbacks' pinned buffer; the stage events of a timed call (scan | offsets | fill: begin, end each)
+    DevBuf rg_par, rg_mask, rg_cnt, rg_soff, rg_plim, rg_lims, rg_d, rg_i, rg_stat, rg_probes;
+    HostBuf h_rg;
+    hipEvent_t rg_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool rg_ev_fill = false;  // the last timed call reached its fill
     // test hooks (hipann_debug_ivf_*, tests/test_ivf_scan_gpu.py).  dbg_stop: ivf_shard_search returns after its scan
     // step (no merge, no rerank; D / I stay unwritten).  dbg_seed: the seeded int8 scan by HIPANN_IVF_SEED (-1), off
     // (0) or on (1).  The last search's shape as the scan saw it: queries, probes, entries per slot, sub-lists, image
@@ -726,6 +733,34 @@ void launch_flat_range_offsets(const int *counts, int64_t nq, int64_t nparts, in
 int64_t flat_range_direct_parts(int64_t n, int64_t *rows_per_wave);
 int flat_range_direct_chunk(int64_t nq, int d);
 void launch_flat_range_direct(const FlatRangeArgs &a, int64_t rows_per_wave, bool fill, hipStream_t st);
+// ivf_range.hip — IVF range search.  One query slice on one shard, after the coarse step and the plan: the scan
+// (image or direct) leaves a 64-word admitted-row mask and a count per (query, probe, chunk) slot; the offsets turn
+// the counts into soff (slots + 1), plim (pairs + 1) and lims (nq + 1; chain: continuing from lims[0]); the fill
+// writes (distance, id) at soff[slot] + rank.
+struct IvfRangeArgs {
+    const float *Q = nullptr;  // the slice's queries (fp32) and their count
+    int64_t nq = 0;
+    int d = 0, metric = kL2;
+    float radius = 0.f;
+    const float *codes = nullptr;      // the shard's rows (fp32)
+    const int64_t *probes = nullptr;   // nq × nprobe probe lists (the direct kernel and the fill find their slots by pair)
+    int max_nch = 1;
+    // the image scan: the queries' fp16 terms, (a_q, c_q) per query, the fp16 image, its pass offsets, ‖x‖² (L2)
+    const void *qsplit = nullptr, *par = nullptr, *codes_h = nullptr;
+    const int64_t *tpass_off = nullptr;
+    const float *xn = nullptr;
+    unsigned *mask = nullptr;
+    int *counts = nullptr;
+    unsigned long long *stat = nullptr;  // (optional) += the filter's survivors, += the rows the recheck admitted
+};
+void launch_ivf_range_query_prep(const float *Q, int64_t nq, int d, int metric, float radius, float xmax2, float rxmax,
+                                 const float *its, const float *rq1, void *par, hipStream_t st);
+void launch_ivf_range_scan_h(const IvfRangeArgs &a, const IvfPlanView &plan, int64_t max_items, hipStream_t st);
+void launch_ivf_range_direct(const IvfRangeArgs &a, const IvfPlanView &plan, hipStream_t st);
+void launch_ivf_range_offsets(const int *counts, const int *slot_off, int64_t nq, int nprobe, bool chain, int64_t *soff,
+                              int64_t *plim, int64_t *lims, hipStream_t st);
+void launch_ivf_range_fill(const IvfRangeArgs &a, const IvfPlanView &plan, const int64_t *ids, const int64_t *soff,
+                           float *D, int64_t *I, hipStream_t st);
 // bounded passes of the 64-dim K-step kernel (flat_b16k64.hip): candidate buffers, their bound and select
 // (k64_on: the caller's HIPANN_B16_K64 switch)
 bool flat_bf16_resumable(int64_t nq, int d, int k, bool k64_on);

@@ -262,6 +262,34 @@ int hipann_ivf_coarse_device(void *index, int64_t nq, const float *xq_dev, int64
 int hipann_ivf_search_probes_device(void *index, int64_t nq, const float *xq_dev, const int64_t *probes_dev,
                                     int64_t k, float *D_dev, int64_t *I_dev, void *stream, char *err_buf, int err_len);
 
+/* faiss::IndexIVF::range_search (range_search_preassigned with the IVFFlat scanner).  The probe lists are the coarse
+ * step's of hipann_ivf_search_np (nprobe <= 0: the index's; above nlist: nlist).  Per query, every live row of every
+ * probed list whose direct-form fp32 value passes the strict comparison — L2: Σ(q−x)² < radius, IP: q·x > radius — in
+ * probe order, then position in the list (FAISS's order for one query, and hipann_ivf_export's order of the list);
+ * labels are the lists' ids.  lims: nq+1 int64 (host); *D / *I: host buffers the library allocates (NULL when nothing
+ * qualifies), released with hipann_range_free.  The distance is the value the exact top-k forms return (the same
+ * bits for the same row).  Any number of rows may qualify (HIPANN_MAX_K does not apply); an empty list contributes
+ * nothing; nq == 0 writes lims[0] = 0; an empty index returns all-zero lims; a NaN radius is an error; ±inf is legal; a
+ * query with a NaN entry returns no rows.  The same call returns the same bits in the same order on every run.
+ * The lists are scanned once: a threshold scan over form 6's tiled fp16 image (built at the first call that needs it,
+ * maintained by hipann_ivf_add / hipann_ivf_remove_ids) whose filter can only add rows, each survivor rechecked in
+ * the direct form; shards without a usable image (a non-finite code) take a direct-form kernel.  The scan leaves an
+ * admitted-row bitmask and a count per (query, probe, 2048-row chunk); a device prefix sum places the slots and a fill
+ * pass writes the rows.  The bitmasks take 256 bytes per slot (bounded per query by the chunks of its nprobe longest
+ * lists); above 64 MiB the batch runs in query slices.  Multi-device handles: each shard answers the (query, probe) pairs whose list it owns and the host stitches
+ * each query's slices in probe order.  hipann_ivf_last_probes reports this call's probe lists; hipann_last_search_path
+ * is left as the last top-k call set it; hipann_last_kernel_ms(which = 0) averages over the scan and fill launches. */
+int hipann_ivf_range_search(void *index, int nprobe, int64_t nq, const float *xq, float radius, int64_t *lims,
+                            float **D, int64_t **I, char *err_buf, int err_len);
+
+/* Device-resident variant: lims_dev (nq+1 int64) is always written; D_dev / I_dev (cap entries) are filled only when
+ * lims[nq] <= cap.  Returns 0, 1 when the result did not fit (read lims[nq] and call again), or -1.  Asynchronous on
+ * `stream` except for the one readback of the total.  Single-device handles, like the other _device calls.  (A batch
+ * that runs in query slices counts every slice first and scans a second time only when the result fits.) */
+int hipann_ivf_range_search_device(void *index, int nprobe, int64_t nq, const float *xq_dev, float radius,
+                                   int64_t *lims_dev, float *D_dev, int64_t *I_dev, int64_t cap, void *stream,
+                                   char *err_buf, int err_len);
+
 int hipann_ivf_set_nprobe(void *index, int nprobe);
 int hipann_ivf_get_nprobe(void *index);
 int hipann_ivf_nlist(void *index);
