@@ -23,6 +23,10 @@
 #include <faiss/IndexFlat.h>
 #include <faiss/IndexIVFFlat.h>
 #include <faiss/invlists/InvertedLists.h>
+#if __has_include(<faiss/IndexScalarQuantizer.h>)
+#include <faiss/IndexScalarQuantizer.h>
+#define HIPANN_HAVE_IVFSQ 1
+#endif
 
 #include <algorithm>
 #include <cstdint>
@@ -176,6 +180,69 @@ private:
     size_t nlist_ = 0, nprobe_ = 1;
 };
 
+#ifdef HIPANN_HAVE_IVFSQ
+// IndexIVFScalarQuantizer with QT_8bit codes ("IVFn,SQ8"): hipann_ivfsq_* (hip_ann.h).  Search only: the GPU copy is
+// rebuilt from the CPU index after an add.
+class HipIndexIVFSQ : public faiss::Index {
+public:
+    static bool supported(const faiss::IndexIVFScalarQuantizer &cpu) {
+        return cpu.sq.qtype == faiss::ScalarQuantizer::QT_8bit && dynamic_cast<const faiss::IndexFlat *>(cpu.quantizer) &&
+               cpu.sq.trained.size() == 2 * (size_t)cpu.d;
+    }
+    HipIndexIVFSQ(const faiss::IndexIVFScalarQuantizer &cpu) : faiss::Index(cpu.d, cpu.metric_type), nlist_(cpu.nlist) {
+        auto *flatq = dynamic_cast<const faiss::IndexFlat *>(cpu.quantizer);
+        std::vector<int64_t> offsets(cpu.nlist + 1, 0);
+        for (size_t l = 0; l < cpu.nlist; ++l) offsets[l + 1] = offsets[l] + (int64_t)cpu.invlists->list_size(l);
+        std::vector<int64_t> ids((size_t)offsets[cpu.nlist]);
+        std::vector<uint8_t> codes((size_t)offsets[cpu.nlist] * cpu.d);
+        for (size_t l = 0; l < cpu.nlist; ++l) {  // ArrayInvertedLists → CSR (one byte per dimension)
+            const size_t sz = cpu.invlists->list_size(l);
+            if (!sz) continue;
+            faiss::InvertedLists::ScopedIds li(cpu.invlists, l);
+            faiss::InvertedLists::ScopedCodes lc(cpu.invlists, l);
+            std::copy(li.get(), li.get() + sz, ids.begin() + offsets[l]);
+            std::memcpy(codes.data() + offsets[l] * cpu.d, lc.get(), sz * cpu.d);
+        }
+        // the non-uniform 8-bit quantizer's trained vector: vmin[d] then vdiff[d]
+        const float *vmin = cpu.sq.trained.data(), *vdiff = vmin + cpu.d;
+        char err[512] = {0};
+        void *h = hipann_ivfsq_create((int)cpu.d, to_hip_metric(cpu.metric_type), (int)cpu.nlist, (int)cpu.nprobe,
+                                      cpu.by_residual ? 1 : 0, flatq->get_xb(), vmin, vdiff, offsets.data(), ids.data(),
+                                      codes.data(), 0, err, sizeof err);
+        if (!h) throw std::runtime_error(std::string("hipann_ivfsq_create: ") + err);
+        handle_ = std::make_unique<HipAnnHandle>(h);
+        ntotal = cpu.ntotal;
+        is_trained = true;
+        nprobe_ = cpu.nprobe;
+        by_residual_ = cpu.by_residual;
+    }
+    void add(faiss::idx_t, const float *) override {
+        throw std::runtime_error("HipIndexIVFSQ::add: add to the CPU index and upload again");
+    }
+    void search(faiss::idx_t n, const float *x, faiss::idx_t k, float *distances, faiss::idx_t *labels,
+                const faiss::SearchParameters *params = nullptr) const override {
+        if (k <= 0) throw std::runtime_error("k must be > 0");
+        int np = (int)nprobe_;
+        if (auto *ip = dynamic_cast<const faiss::SearchParametersIVF *>(params))
+            if (ip->nprobe > 0) np = (int)ip->nprobe;
+        char err[512] = {0};
+        check(hipann_ivfsq_search(handle_->h, np, n, x, k, distances, reinterpret_cast<int64_t *>(labels), err, sizeof err),
+              err);
+    }
+    void reset() override { throw std::runtime_error("HipIndexIVFSQ::reset: rebuild from the CPU index"); }
+    void set_nprobe(size_t np) { nprobe_ = np; }
+    size_t nprobe() const { return nprobe_; }
+    size_t nlist() const { return nlist_; }
+    bool by_residual() const { return by_residual_; }
+    void *handle() const { return handle_->h; }
+
+private:
+    std::unique_ptr<HipAnnHandle> handle_;
+    size_t nlist_ = 0, nprobe_ = 1;
+    bool by_residual_ = true;
+};
+#endif
+
 class HipGpuBackend : public GpuBackend {
 public:
     bool IsAvailable() const override { return hipann_available() == 1; }
@@ -189,8 +256,13 @@ public:
     std::unique_ptr<faiss::Index> CpuToGpu(faiss::Index *cpu_index) override {
         if (!IsAvailable()) throw std::runtime_error("HIP GPU backend not available");
         if (auto *ivf = dynamic_cast<faiss::IndexIVFFlat *>(cpu_index)) return std::make_unique<HipIndexIVFFlat>(*ivf);
+#ifdef HIPANN_HAVE_IVFSQ
+        if (auto *sq = dynamic_cast<faiss::IndexIVFScalarQuantizer *>(cpu_index))
+            if (HipIndexIVFSQ::supported(*sq)) return std::make_unique<HipIndexIVFSQ>(*sq);
+#endif
         if (auto *flat = dynamic_cast<faiss::IndexFlat *>(cpu_index)) return std::make_unique<HipIndexFlat>(*flat);
-        throw std::runtime_error("HIP GPU supports IndexFlat and IndexIVFFlat. Got an unsupported index type.");
+        throw std::runtime_error("HIP GPU supports IndexFlat, IndexIVFFlat and IndexIVFScalarQuantizer (QT_8bit, flat "
+                                 "quantizer). Got an unsupported index type.");
     }
     std::unique_ptr<faiss::Index> GpuToCpu(faiss::Index *gpu_index) override {
         if (auto *v = dynamic_cast<HipIndexIVFFlat *>(gpu_index)) {
@@ -217,6 +289,37 @@ public:
             cpu->ntotal = off[nlist];
             return cpu;
         }
+#ifdef HIPANN_HAVE_IVFSQ
+        if (auto *v = dynamic_cast<HipIndexIVFSQ *>(gpu_index)) {
+            const int nlist = (int)v->nlist(), d = (int)v->d;
+            char err[512] = {0};
+            std::vector<int64_t> off(nlist + 1);
+            check(hipann_ivfsq_export(v->handle(), nullptr, nullptr, nullptr, off.data(), nullptr, nullptr, err, sizeof err),
+                  err);
+            std::vector<float> cen((size_t)nlist * d), trained(2 * (size_t)d);
+            std::vector<int64_t> ids((size_t)off[nlist]);
+            std::vector<uint8_t> codes((size_t)off[nlist] * d);
+            check(hipann_ivfsq_export(v->handle(), cen.data(), trained.data(), trained.data() + d, off.data(), ids.data(),
+                                      codes.data(), err, sizeof err),
+                  err);
+            auto *quantizer = new faiss::IndexFlat(d, v->metric_type);
+            quantizer->add(nlist, cen.data());
+            auto cpu = std::make_unique<faiss::IndexIVFScalarQuantizer>(quantizer, d, nlist, faiss::ScalarQuantizer::QT_8bit,
+                                                                        v->metric_type, v->by_residual());
+            cpu->own_fields = true;
+            cpu->sq.trained = trained;
+            cpu->is_trained = true;
+            cpu->nprobe = v->nprobe();
+            for (int l = 0; l < nlist; ++l) {
+                const size_t len = (size_t)(off[l + 1] - off[l]);
+                if (!len) continue;
+                cpu->invlists->add_entries(l, len, reinterpret_cast<const faiss::idx_t *>(ids.data() + off[l]),
+                                           codes.data() + (size_t)off[l] * d);
+            }
+            cpu->ntotal = off[nlist];
+            return cpu;
+        }
+#endif
         if (auto *f = dynamic_cast<HipIndexFlat *>(gpu_index)) {  // index_metal_to_cpu
             auto cpu = std::make_unique<faiss::IndexFlat>(f->d, f->metric_type);
             std::vector<float> xb((size_t)f->ntotal * f->d);

@@ -1003,6 +1003,47 @@ void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, i
 
 
 
+std::unique_ptr<IvfIndex> ivf_make_core(int d, int metric, int nlist, int nprobe, const float *centroids,
+                                        const int64_t *list_offsets, const int64_t *ids, int device) {
+    auto ix = std::make_unique<IvfIndex>();
+    ix->d = d, ix->metric = metric, ix->nlist = nlist, ix->nprobe = nprobe;
+    ix->owner.assign(nlist, 0);
+    auto sh = std::make_unique<IvfShard>();
+    sh->device = device;
+    sh->stream = make_stream(device);
+    DeviceGuard g(device);
+    const int64_t n = list_offsets[nlist];
+    sh->centroids_buf.ensure(sizeof(float) * (size_t)nlist * d, device);
+    sh->ids_buf.ensure(sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1), device);
+    HIPANN_CHECK(hipMemcpyAsync(sh->centroids_buf.p, centroids, sizeof(float) * (size_t)nlist * d, hipMemcpyHostToDevice,
+                                sh->stream));
+    if (n) HIPANN_CHECK(hipMemcpyAsync(sh->ids_buf.p, ids, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, sh->stream));
+    HIPANN_CHECK(hipStreamSynchronize(sh->stream));
+    sh->centroids = sh->centroids_buf.get<float>();
+    sh->ids = sh->ids_buf.get<int64_t>();
+    const std::vector<int64_t> off(list_offsets, list_offsets + nlist + 1);
+    upload_list_meta(*sh, off, dense_lengths(off, nlist), nlist);
+    sh->quant = make_quantizer(d, metric, sh->centroids, nlist, device, sh->stream);
+    ix->shards.push_back(std::move(sh));
+    return ix;
+}
+
+IvfPlanView ivf_coarse_plan(IvfIndex &ix, IvfShard &sh, int np, int64_t nq, const float *xq, int group, hipStream_t st) {
+    const IvfSearchOpts opts{};
+    IvfBatch b{ix, sh, nq, xq, 1, 1, nullptr, nullptr, st, opts, np, {}, false, *sh.quant->shards[0]};
+    ivf_plan_scratch(b);
+    CcntReset ccnt_reset{b.ccnt_cur, ix.nlist, st, true};
+    b.m.form = kFormDirect;
+    b.m.group = group;
+    b.m.exact = true;  // the plan resets the flag count
+    sh.nflag.ensure(sizeof(int), sh.device);
+    sh.qbound.ensure(sizeof(unsigned) * (size_t)nq, sh.device);
+    b.qbound = sh.qbound.get<unsigned>();
+    ivf_coarse_and_plan(b);
+    ccnt_reset.armed = false;
+    return b.plan();
+}
+
 // Grow a shard's CSR so that list l can take add[l] more rows: every list gets capacity max(cap, need + max(need / 4,
 // 64)) rows — geometric growth (O(1) amortised copies per appended row, the doubling of MetalIndexFlat::add,
 // MetalIndexFlat.mm:255-269, at ×1.25: a 10M × 768 table at ×2 would hold 61 GB of codes);

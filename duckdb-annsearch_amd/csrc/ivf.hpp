@@ -21,4 +21,11 @@ struct IvfSearchOpts {
 };
 void ivf_shard_search(IvfIndex &ix, IvfShard &sh, int64_t nq, const float *xq, int k, int kout, float *D, int64_t *I,
                       hipStream_t st, const IvfSearchOpts &opts = {});
+// IVF SQ8 (ivf_sq8.cpp) shares the IVFFlat coarse step and plan.  ivf_make_core: an IvfIndex on one device with
+// centroids, labels, list offsets and the coarse quantizer, and no fp32 rows.  ivf_coarse_plan: the coarse step (probe
+// lists in sh.coarse_i) and launch_ivf_plan for scan items of `group` queries; qbound (nq words, +inf) and *nflag (0)
+// are reset by the plan.
+std::unique_ptr<IvfIndex> ivf_make_core(int d, int metric, int nlist, int nprobe, const float *centroids,
+                                        const int64_t *list_offsets, const int64_t *ids, int device);
+IvfPlanView ivf_coarse_plan(IvfIndex &ix, IvfShard &sh, int np, int64_t nq, const float *xq, int group, hipStream_t st);
 }  // namespace hipann

@@ -261,7 +261,7 @@ struct FenceScope {
     }
 };
 
-enum class Kind { Flat = 1, IVF = 2 };
+enum class Kind { Flat = 1, IVF = 2, IVFSQ = 3 };
 
 // One contiguous row range of a Flat index resident on one device.
 struct FlatShard {
@@ -504,6 +504,38 @@ struct IvfIndex : IndexBase {
                  (int64_t)s->codes_h.bytes + (int64_t)s->codes_t.bytes + (int64_t)s->codes_i8.bytes + (int64_t)s->xs8.bytes +
                  (int64_t)s->xr8.bytes;
         return b;
+    }
+};
+
+// IVF SQ8 (hipann_ivfsq_*, ivf_sq8.cpp / ivf_sq8.hip): an IndexIVFScalarQuantizer with QT_8bit codes on one device.
+// `core` is an IvfIndex without fp32 rows — centroids, labels, list offsets, the coarse quantizer and the plan's
+// scratch, so the coarse step and launch_ivf_plan are the IVFFlat ones.  The codes live only in the tiled layout the
+// scan streams (ivf_sq8.hip); export and the direct-form function read that layout.
+struct IvfSqIndex : IndexBase {
+    std::unique_ptr<IvfIndex> core;
+    int by_residual = 1;
+    int nstep = 0;               // 32-dim MFMA K steps per row of the tiled codes (d padded)
+    int64_t total_pass = 0;      // 32-row passes of all lists
+    DevBuf vmin, vdiff, sb;      // the trained quantizer (d each); s = vdiff/255 and b = vmin + s/2, 32·nstep each
+    DevBuf codes_t, tpass_off;   // tiled u8 codes; int64 nlist + 1 pass offsets
+    DevBuf rown;                 // L2: N(row) = ‖s∘c‖² + 2 g·(s∘c)
+    float cmax = 0.f;            // max over rows of ‖c‖ (the certificate's Cauchy-Schwarz term)
+    double gmax = 0.0, mnorm = 0.0;  // max ‖g_l‖ (by_residual) and ‖(|vmin_i| + |vdiff_i|·256/255)_i‖: the bound's magnitudes
+    // per-call scratch: query images and (1/t, E, 2E), pair constants, per-(slot, wave) candidate lists, flags,
+    // the direct kernel's slot lists, staged queries and results, the probe lists of a sliced call
+    DevBuf qimg, par, pair_a, cand_d, cand_i, flagged, dl_d, dl_i, q, out_d, out_i, probes, fb_total;
+    HostBuf h_q, h_d, h_i;
+    bool probes_kept = false;    // the last call ran in query slices: its probe lists are in `probes`
+    int64_t last_nq = 0;
+    int last_np = 0;
+    IvfSqIndex() : IndexBase(Kind::IVFSQ) {}
+    int64_t ntotal() const override { return core ? core->ntotal() : 0; }
+    // the tiled codes, N(row), labels, centroids and their norms, list offsets and lengths, the quantizer and pass offsets
+    int64_t memory_bytes() const override {
+        if (!core) return 0;
+        const int64_t n = ntotal(), nl = core->nlist;
+        return (int64_t)codes_t.bytes + (int64_t)rown.bytes + n * 8 + nl * d * 4 + (metric == kL2 ? nl * 4 : 0) +
+               (nl + 1) * 8 + nl * 4 + (int64_t)d * 8 + (int64_t)sb.bytes + (int64_t)tpass_off.bytes;
     }
 };
 
@@ -761,6 +793,44 @@ void launch_ivf_range_offsets(const int *counts, const int *slot_off, int64_t nq
                               int64_t *plim, int64_t *lims, hipStream_t st);
 void launch_ivf_range_fill(const IvfRangeArgs &a, const IvfPlanView &plan, const int64_t *ids, const int64_t *soff,
                            float *D, int64_t *I, hipStream_t st);
+// ivf_sq8.hip — IVF SQ8.  Create-time: the tiled codes, N(row) and max ‖c‖².  Per call: query preparation, pair
+// constants, the code scan over the plan's items, the rerank + certificate, the direct kernel and its merge.
+struct IvfSqView {
+    int d = 0, nstep = 0, metric = kL2, by_residual = 1, nlist = 0;
+    const float *centroids = nullptr, *vmin = nullptr, *vdiff = nullptr, *sb = nullptr, *rown = nullptr;
+    const unsigned char *codes_t = nullptr;
+    const int64_t *tpass_off = nullptr, *ids = nullptr;
+    int64_t nrows = 0;
+};
+constexpr int kSqWaves = 8;    // waves per scan block = candidate sub-lists per (query, probe, chunk) slot
+constexpr int kSqKeep = 16;    // entries per sub-list: the scan path serves k <= kSqKeep
+constexpr int kSqDirectK = 64; // the direct kernel's per-slot list for k <= 64; above: every row of the slot
+int ivf_sq_nstep(int d);
+int ivf_sq_group(int d);  // queries per scan item (a multiple of 16; 0: the query terms do not fit the LDS)
+void launch_ivf_sq_tile(const unsigned char *codes, const int64_t *list_off, const int *list_len,
+                        const int64_t *tpass_off, int nlist, int64_t total_pass, int d, int nstep, unsigned char *dst,
+                        hipStream_t st);
+void launch_ivf_sq_untile(const IvfSqView &v, const int64_t *list_off, const int *list_len, int64_t total_pass,
+                          unsigned char *codes, hipStream_t st);
+void launch_ivf_sq_row_terms(const unsigned char *codes, const IvfSqView &v, const int64_t *list_off, int nlist,
+                             float *rown, unsigned *cmax2, hipStream_t st);
+void launch_ivf_sq_query_prep(const float *Q, int64_t nq, const IvfSqView &v, float cmax, float wbase, void *qimg,
+                              float *par, hipStream_t st);
+void launch_ivf_sq_pair_terms(const float *Q, int64_t nq, int nprobe, const int64_t *probes, const IvfSqView &v,
+                              float *pair_a, hipStream_t st);
+void launch_ivf_sq_scan(const IvfSqView &v, const IvfPlanView &plan, int group, int64_t max_items, const void *qimg,
+                        const float *par, const float *pair_a, unsigned *qbound, float *cand_d, int *cand_i,
+                        hipStream_t st);
+void launch_ivf_sq_rerank(const IvfSqView &v, const IvfPlanView &plan, const int64_t *probes, const float *Q, int64_t nq,
+                          int k, const float *par, const float *cand_d, const int *cand_i, int *nflag, int *flagged,
+                          unsigned long long *fb_total, float *D, int64_t *I, hipStream_t st);
+// the direct kernel over the slots of the flagged queries (nflag / flagged set) or of all nq; kslot = kSqDirectK
+// (per-slot lists of the 64 best (distance, label); dl_i: int64) or ivf_chunk_rows() (every row; dl_i: int shard rows)
+void launch_ivf_sq_direct(const IvfSqView &v, const IvfPlanView &plan, const int64_t *probes, const float *Q, int64_t nq,
+                          int max_nch, int kslot, const int *nflag, const int *flagged, float *dl_d, void *dl_i,
+                          hipStream_t st);
+void launch_ivf_sq_merge(const IvfSqView &v, const IvfPlanView &plan, int64_t nq, int k, const int *nflag,
+                         const int *flagged, const float *dl_d, const void *dl_i, float *D, int64_t *I, hipStream_t st);
 // bounded passes of the 64-dim K-step kernel (flat_b16k64.hip): candidate buffers, their bound and select
 // (k64_on: the caller's HIPANN_B16_K64 switch)
 bool flat_bf16_resumable(int64_t nq, int d, int k, bool k64_on);

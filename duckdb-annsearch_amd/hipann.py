@@ -132,6 +132,12 @@ def lib() -> C.CDLL:
             "hipann_ivf_get_filter_image": ([vp], i32),
             "hipann_ivf_last_filter_image": ([vp], i32),
             "hipann_ivf_last_seeded": ([vp], i32),
+            "hipann_ivfsq_create": ([i32, i32, i32, i32, i32, f, f, f, i64p, i64p, C.POINTER(C.c_uint8), i32, cp, i32], vp),
+            "hipann_ivfsq_search": ([vp, i32, i64, f, i64, f, i64p, cp, i32], i32),
+            "hipann_ivfsq_search_device": ([vp, i32, i64, vp, i64, vp, vp, vp, cp, i32], i32),
+            "hipann_ivfsq_last_probes": ([vp, i64p, i64, cp, i32], i32),
+            "hipann_ivfsq_export": ([vp, f, f, f, i64p, i64p, C.POINTER(C.c_uint8), cp, i32], i32),
+            "hipann_ivfsq_rerank_fallbacks": ([vp], i64),
             "hipann_ntotal": ([vp], i64),
             "hipann_dim": ([vp], i32),
             "hipann_metric": ([vp], i32),
@@ -647,6 +653,80 @@ class HipIndexIVFFlat(_Handle):
         return P
 
 
+class HipIndexIVFSQ8(_Handle):
+    """IVF SQ8 on MI355X — faiss::IndexIVFScalarQuantizer with QT_8bit codes (index_factory "IVFn,SQ8"), built from
+    the trained pieces of the CPU index: centroids, the quantizer's vmin / vdiff, by_residual and the CSR lists of
+    uint8 codes (hip_ann.h, hipann_ivfsq_*: decode, distance and order are stated there)."""
+
+    def __init__(self, centroids, vmin, vdiff, list_offsets, ids, codes, nprobe: int = 1, metric: int = METRIC_L2,
+                 by_residual: bool = True, device: int = 0):
+        cen = _f32_2d(centroids)
+        nlist, d = cen.shape
+        vmn = np.ascontiguousarray(vmin, np.float32).reshape(-1)
+        vdf = np.ascontiguousarray(vdiff, np.float32).reshape(-1)
+        off = np.ascontiguousarray(list_offsets, np.int64)
+        idv = np.ascontiguousarray(ids, np.int64)
+        cod = np.ascontiguousarray(codes, np.uint8).reshape(-1, d)
+        if vmn.shape != (d,) or vdf.shape != (d,) or off.shape != (nlist + 1,) or cod.shape[0] != len(idv):
+            raise ValueError("inconsistent quantizer or inverted lists")
+        eb = _err()
+        h = lib().hipann_ivfsq_create(d, metric, nlist, nprobe, 1 if by_residual else 0, _ptr(cen, C.c_float),
+                                      _ptr(vmn, C.c_float), _ptr(vdf, C.c_float), _ptr(off, C.c_int64),
+                                      _ptr(idv, C.c_int64), _ptr(cod, C.c_uint8), device, eb, 1024)
+        if not h:
+            raise HipAnnError(eb.value.decode())
+        super().__init__(h, d, metric)
+        self.nlist = nlist
+        self.nprobe = nprobe
+        self.by_residual = bool(by_residual)
+
+    def search(self, x, k: int, nprobe: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """The k best rows of the probed lists by (distance, id); ``nprobe``: the per-call value (None: the
+        index's; above nlist: nlist)."""
+        x = _f32_2d(x, self.d)
+        n = x.shape[0]
+        D = np.empty((n, max(k, 0)), np.float32)
+        I = np.empty((n, max(k, 0)), np.int64)
+        eb = _err()
+        _check(lib().hipann_ivfsq_search(self._h, 0 if nprobe is None else int(nprobe), n, _ptr(x, C.c_float), k,
+                                         _ptr(D, C.c_float), _ptr(I, C.c_int64), eb, 1024), eb)
+        return D, I
+
+    def search_device(self, nq: int, xq_ptr: int, k: int, d_ptr: int, i_ptr: int, nprobe: Optional[int] = None,
+                      stream: int = 0) -> None:
+        eb = _err()
+        _check(lib().hipann_ivfsq_search_device(self._h, 0 if nprobe is None else int(nprobe), nq, C.c_void_p(xq_ptr),
+                                                k, C.c_void_p(d_ptr), C.c_void_p(i_ptr), C.c_void_p(stream or None),
+                                                eb, 1024), eb)
+
+    def last_probes(self, nq: int, nprobe: Optional[int] = None) -> np.ndarray:
+        """The last call's probe lists (``nprobe``: that call's per-call value, when it had one)."""
+        P = np.empty((nq, min(self.nprobe if nprobe is None else int(nprobe), self.nlist)), np.int64)
+        eb = _err()
+        _check(lib().hipann_ivfsq_last_probes(self._h, _ptr(P, C.c_int64), P.size, eb, 1024), eb)
+        return P
+
+    def export(self) -> dict:
+        """The index as it was created (hipann_ivfsq_export) — what GpuToCpu rebuilds the CPU index from."""
+        off = np.empty(self.nlist + 1, np.int64)
+        eb = _err()
+        _check(lib().hipann_ivfsq_export(self._h, None, None, None, _ptr(off, C.c_int64), None, None, eb, 1024), eb)
+        n = int(off[-1])
+        cen = np.empty((self.nlist, self.d), np.float32)
+        vmn, vdf = np.empty(self.d, np.float32), np.empty(self.d, np.float32)
+        ids = np.empty(n, np.int64)
+        codes = np.empty((n, self.d), np.uint8)
+        _check(lib().hipann_ivfsq_export(self._h, _ptr(cen, C.c_float), _ptr(vmn, C.c_float), _ptr(vdf, C.c_float),
+                                         _ptr(off, C.c_int64), _ptr(ids, C.c_int64), _ptr(codes, C.c_uint8), eb, 1024),
+               eb)
+        return {"type": "IVFSQ8", "centroids": cen, "vmin": vmn, "vdiff": vdf, "list_offsets": off, "ids": ids,
+                "codes": codes, "nprobe": self.nprobe, "metric": self.metric_type, "by_residual": self.by_residual}
+
+    def rerank_fallbacks(self) -> int:
+        """Queries the scan's certificate flagged since creation (re-run on the device by the direct kernel)."""
+        return int(lib().hipann_ivfsq_rerank_fallbacks(self._h))
+
+
 KMEANS_INIT_RANDOM, KMEANS_INIT_PLUSPLUS = 0, 1
 
 
@@ -714,17 +794,23 @@ class GpuBackend:
                 return HipIndexIVFFlat(cpu_index["centroids"], cpu_index["list_offsets"], cpu_index["ids"],
                                        cpu_index["codes"], cpu_index.get("nprobe", 1),
                                        cpu_index.get("metric", METRIC_L2))
+            if kind == "IVFSQ8":
+                return HipIndexIVFSQ8(cpu_index["centroids"], cpu_index["vmin"], cpu_index["vdiff"],
+                                      cpu_index["list_offsets"], cpu_index["ids"], cpu_index["codes"],
+                                      cpu_index.get("nprobe", 1), cpu_index.get("metric", METRIC_L2),
+                                      cpu_index.get("by_residual", True))
             if kind == "Flat":
                 return HipIndexFlat(cpu_index["d"], cpu_index.get("metric", METRIC_L2), cpu_index["xb"])
         except HipAnnError as e:
             raise RuntimeError(str(e)) from e
-        raise RuntimeError("HIP GPU supports IndexFlat and IndexIVFFlat. Got an unsupported index type.")
+        raise RuntimeError("HIP GPU supports IndexFlat, IndexIVFFlat and IndexIVFScalarQuantizer (QT_8bit). "
+                           "Got an unsupported index type.")
 
     def gpu_to_cpu(self, gpu_index) -> dict:
         if isinstance(gpu_index, HipIndexFlat):
             return {"type": "Flat", "d": gpu_index.d, "metric": gpu_index.metric_type,
                     "xb": gpu_index.reconstruct_n(0, gpu_index.ntotal)}
-        if isinstance(gpu_index, HipIndexIVFFlat):  # gpu_backend_metal.mm:62-67 (index_metal_to_cpu_ivf)
+        if isinstance(gpu_index, (HipIndexIVFFlat, HipIndexIVFSQ8)):  # gpu_backend_metal.mm:62-67 (index_metal_to_cpu_ivf)
             return gpu_index.export()
         raise RuntimeError("Index is not a HIP index -- cannot convert to CPU")
 

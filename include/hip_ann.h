@@ -417,6 +417,44 @@ int64_t hipann_ivf_i8_passes_tiled(void *index);
 int64_t hipann_ivf_rerank_fallbacks(void *index);
 
 /* ---------------------------------------------------------------------------------------------
+ * IVF SQ8 (faiss::IndexIVFScalarQuantizer with QT_8bit — index_factory "IVFn,SQ8"): one byte per dimension
+ *
+ * The index: d, metric, nlist, the centroids g_l (nlist·d fp32), the trained quantizer vmin[d] / vdiff[d] (fp32,
+ * FAISS's `trained` vector of the non-uniform 8-bit quantizer), by_residual (FAISS's default is 1 for both metrics) and
+ * CSR lists: list_offsets (nlist + 1), ids (n), codes (n·d uint8, row-major, list order).
+ * Decode, in fp32 and in this order: dec_i = vmin_i + ((float)c_i + 0.5f) / 255.0f * vdiff_i; a row of list l stands
+ * for dec + (by_residual ? g_l : 0).
+ * Distance returned: the direct form in fp32 over the decoded row — L2: Σ_i (t_i − dec_i)², t = q − g_l (by_residual)
+ * or q; IP: (by_residual ? q·g_l : 0) + Σ_i q_i·dec_i — computed by one device function for every path, so a row
+ * carries the same bits whichever path returned it.
+ * Probes: the k = nprobe search of a Flat index over the centroids (hipann_ivf_search_np's coarse step: the metric's
+ * order, ties by list id); nprobe <= 0: the index's value; above nlist: nlist.
+ * Results: per query the k best rows of the probed lists by (distance, id), ascending for L2, descending for IP; slots
+ * past the number of probed rows hold (+inf | −inf, −1).  k <= 0 is an error; k <= HIPANN_MAX_K.  The same call
+ * returns the same bits on every run.  k <= 16 runs the code scan on the matrix cores with an exact rerank and a
+ * per-query certificate; queries the certificate flags, larger k and d above 4352 run the direct kernel on the
+ * device (no host readback: the _device call stays asynchronous).
+ * The handle is single-device (per-handle mutex, one stream plus scratch, err_buf as everywhere) and serves
+ * hipann_ntotal / _dim / _metric / _memory_bytes / _free / _set_kernel_timing / _last_kernel_ms (which = 0: the code
+ * scan); every other entry point rejects it with −1.  There is no add, remove or range search.
+ * ------------------------------------------------------------------------------------------- */
+void *hipann_ivfsq_create(int d, int metric, int nlist, int nprobe, int by_residual,
+                          const float *centroids, const float *vmin, const float *vdiff,
+                          const int64_t *list_offsets, const int64_t *ids, const uint8_t *codes,
+                          int device, char *err_buf, int err_len);
+int hipann_ivfsq_search(void *index, int nprobe, int64_t nq, const float *xq, int64_t k,
+                        float *D, int64_t *I, char *err_buf, int err_len);
+int hipann_ivfsq_search_device(void *index, int nprobe, int64_t nq, const float *xq_dev, int64_t k,
+                               float *D_dev, int64_t *I_dev, void *stream, char *err_buf, int err_len);
+/* The last call's probe lists (nq × min(nprobe, nlist) int64). */
+int hipann_ivfsq_last_probes(void *index, int64_t *probes, int64_t cap, char *err_buf, int err_len);
+/* GpuToCpu: the index as it was created (the codes are un-tiled on the device); any output may be NULL. */
+int hipann_ivfsq_export(void *index, float *centroids, float *vmin, float *vdiff, int64_t *list_offsets,
+                        int64_t *ids, uint8_t *codes, char *err_buf, int err_len);
+/* Queries the certificate flagged since the index was created (reading the count synchronises the device). */
+int64_t hipann_ivfsq_rerank_fallbacks(void *index);
+
+/* ---------------------------------------------------------------------------------------------
  * Common
  * ------------------------------------------------------------------------------------------- */
 
