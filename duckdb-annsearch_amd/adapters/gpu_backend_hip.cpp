@@ -181,8 +181,8 @@ private:
 };
 
 #ifdef HIPANN_HAVE_IVFSQ
-// IndexIVFScalarQuantizer with QT_8bit codes ("IVFn,SQ8"): hipann_ivfsq_* (hip_ann.h).  Search only: the GPU copy is
-// rebuilt from the CPU index after an add.
+// IndexIVFScalarQuantizer with QT_8bit codes ("IVFn,SQ8"): hipann_ivfsq_* (hip_ann.h).  Search and add; a removal
+// rebuilds the GPU copy from the CPU index.
 class HipIndexIVFSQ : public faiss::Index {
 public:
     static bool supported(const faiss::IndexIVFScalarQuantizer &cpu) {
@@ -216,8 +216,13 @@ public:
         nprobe_ = cpu.nprobe;
         by_residual_ = cpu.by_residual;
     }
-    void add(faiss::idx_t, const float *) override {
-        throw std::runtime_error("HipIndexIVFSQ::add: add to the CPU index and upload again");
+    // IndexIVF::add / add_with_ids on the GPU copy: hipann_ivfsq_add assigns the rows with the GPU coarse quantizer,
+    // encodes them on the device and appends them to their lists (labels ntotal + i, or xids).
+    void add(faiss::idx_t n, const float *x) override { add_with_ids(n, x, nullptr); }
+    void add_with_ids(faiss::idx_t n, const float *x, const faiss::idx_t *xids) override {
+        char err[512] = {0};
+        check(hipann_ivfsq_add(handle_->h, n, x, reinterpret_cast<const int64_t *>(xids), err, sizeof err), err);
+        ntotal += n;
     }
     void search(faiss::idx_t n, const float *x, faiss::idx_t k, float *distances, faiss::idx_t *labels,
                 const faiss::SearchParameters *params = nullptr) const override {

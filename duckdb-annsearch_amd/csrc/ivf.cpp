@@ -1028,6 +1028,15 @@ std::unique_ptr<IvfIndex> ivf_make_core(int d, int metric, int nlist, int nprobe
     return ix;
 }
 
+std::unique_ptr<FlatIndex> ivf_make_quantizer(int d, int metric, const float *centroids_dev, int nlist, int device,
+                                              hipStream_t st) {
+    return make_quantizer(d, metric, centroids_dev, nlist, device, st);
+}
+
+void ivf_set_list_meta(IvfShard &sh, const std::vector<int64_t> &off, const std::vector<int64_t> &len, int nlist) {
+    upload_list_meta(sh, off, len, nlist);
+}
+
 IvfPlanView ivf_coarse_plan(IvfIndex &ix, IvfShard &sh, int np, int64_t nq, const float *xq, int group, hipStream_t st) {
     const IvfSearchOpts opts{};
     IvfBatch b{ix, sh, nq, xq, 1, 1, nullptr, nullptr, st, opts, np, {}, false, *sh.quant->shards[0]};

@@ -179,9 +179,222 @@ void sq_search_device(IvfSqIndex &ix, int nprobe, int64_t nq, const float *xq, i
     }
 }
 
+// ---- train: the assignment in blocks of 65536 rows (by_residual), then the column min / max ----
+void sq_train_device(int d, int metric, int nlist, int by_residual, const float *cen_dev, int64_t n, const float *x_dev,
+                     int device, float *vmin_dev, float *vdiff_dev, hipStream_t st) {
+    DeviceGuard g(device);
+    DevBuf assign, cd, bits;
+    bits.ensure(sizeof(unsigned) * 2 * (size_t)d, device);
+    std::unique_ptr<FlatIndex> quant;
+    if (by_residual) {
+        const int64_t bs = 65536;
+        assign.ensure(sizeof(int64_t) * (size_t)n, device);
+        cd.ensure(sizeof(float) * (size_t)std::min(n, bs), device);
+        quant = ivf_make_quantizer(d, metric, cen_dev, nlist, device, st);
+        for (int64_t r0 = 0; r0 < n; r0 += bs)
+            flat_shard_search(*quant, *quant->shards[0], std::min(bs, n - r0), x_dev + r0 * d, 1, 1, cd.get<float>(),
+                              assign.get<int64_t>() + r0, st);
+    }
+    launch_ivf_sq_minmax(x_dev, n, d, assign.get<int64_t>(), by_residual ? cen_dev : nullptr, nlist,
+                         bits.get<unsigned>(), vmin_dev, vdiff_dev, st);
+    std::vector<float> h((size_t)2 * d);
+    HIPANN_CHECK(hipMemcpyAsync(h.data(), vmin_dev, sizeof(float) * d, hipMemcpyDeviceToHost, st));
+    HIPANN_CHECK(hipMemcpyAsync(h.data() + d, vdiff_dev, sizeof(float) * d, hipMemcpyDeviceToHost, st));
+    HIPANN_CHECK(hipStreamSynchronize(st));  // (the scratch above is released on return)
+    const char *bad = ivf_sq_check_trained(h.data(), h.data() + d, d);
+    HIPANN_REQUIRE(!bad, bad);
+}
+
+// ---- add: n rows on the index's device; labels on the device (lab_dev), on the host (lab_host) or ntotal + i ----
+// Stages, on st: the statistics-only pass of the encode kernel (non-finite rows) and the assignment in blocks of 65536
+// rows; ONE readback of both; on the host the per-list counts and every row's physical destination (rows of a later
+// block follow an earlier block's: i ascends); when a list overflows its slack, the grown layout — every new buffer
+// is allocated before anything of the index changes, then one regroup launch and the swap; one pinned upload
+// [destination | label per row | list starts]; the encode kernel; the max ‖c‖² word back and the list metadata.
+// an add's staging goes back when the call ends, however it ends, unless it is small (IvfSqIndex::kAddStagingKeep)
+struct AddStagingScope {
+    IvfSqIndex &ix;
+    ~AddStagingScope() {
+        try { ix.release_add_staging(); } catch (...) {}
+    }
+};
+
+void sq_add_rows(IvfSqIndex &ix, int64_t n, const float *x_dev, const int64_t *lab_dev, const int64_t *lab_host,
+                 hipStream_t st) {
+    IvfShard &sh = *ix.core->shards[0];
+    DeviceGuard g(sh.device);
+    RoctxRange rr("hipann.ivfsq.add");
+    const int nlist = ix.core->nlist, d = ix.d, dev = sh.device;
+    HIPANN_REQUIRE(sh.live + n < (int64_t)0x7fffffff, "more than 2^31-1 rows");
+    const int64_t bs = 65536, base = sh.live;
+    ix.add_assign.ensure(sizeof(int64_t) * (size_t)(n + 1), dev);
+    ix.add_cd.ensure(sizeof(float) * (size_t)std::min(n, bs), dev);
+    ix.h_add.ensure(sizeof(int64_t) * (size_t)(n + 1));
+    int64_t *assign_dev = ix.add_assign.get<int64_t>();
+    unsigned *bad_dev = reinterpret_cast<unsigned *>(assign_dev + n);
+    unsigned *cmax2 = reinterpret_cast<unsigned *>(ix.fb_total.get<unsigned long long>() + 1);
+    HIPANN_CHECK(hipMemsetAsync(bad_dev, 0, sizeof(int64_t), st));
+    launch_ivf_sq_encode_append(x_dev, n, sq_view(ix), nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                                nullptr, bad_dev, st);
+    for (int64_t r0 = 0; r0 < n; r0 += bs)
+        flat_shard_search(*sh.quant, *sh.quant->shards[0], std::min(bs, n - r0), x_dev + r0 * d, 1, 1,
+                          ix.add_cd.get<float>(), assign_dev + r0, st);
+    HIPANN_CHECK(hipMemcpyAsync(ix.h_add.p, assign_dev, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
+    HIPANN_CHECK(hipStreamSynchronize(st));
+    const int64_t *assign = ix.h_add.get<int64_t>();
+    HIPANN_REQUIRE(assign[n] == 0, "IVF SQ8 add: every entry of the rows must be finite");
+    std::vector<int64_t> add(nlist, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        HIPANN_REQUIRE(assign[i] >= 0 && assign[i] < nlist, "coarse assignment out of range");
+        ++add[assign[i]];
+    }
+    const bool grow = ivf_sq_must_grow(sh.h_off, sh.h_len, add);
+    const std::vector<int64_t> off = grow ? ivf_sq_grown_offsets(sh.h_off, sh.h_len, add) : sh.h_off;
+    const std::vector<int64_t> tp = ivf_sq_pass_offsets(off.data(), nlist);
+    const int64_t N = off[nlist];
+    HIPANN_REQUIRE(N < (int64_t)0x7fffffff, "more than 2^31-1 physical rows");
+    // everything the call allocates, before anything of the index changes
+    DevBuf codes_new, ids_new, rown_new, tp_new;
+    if (grow) {
+        codes_new.ensure((size_t)tp[nlist] * ix.nstep * 1024, dev);
+        ids_new.ensure(sizeof(int64_t) * (size_t)N, dev);
+        if (ix.metric == kL2) rown_new.ensure(sizeof(float) * (size_t)N, dev);
+        tp_new.ensure(sizeof(int64_t) * (size_t)(nlist + 1), dev);
+    }
+    const size_t up_n = (size_t)2 * n + 2 * ((size_t)nlist + 1);
+    ix.add_up.ensure(sizeof(int64_t) * up_n, dev);
+    ix.h_up.ensure(sizeof(int64_t) * up_n);
+    int64_t *dst = ix.h_up.get<int64_t>(), *lab = dst + n, *hoff = lab + n, *htp = hoff + nlist + 1;
+    std::vector<int64_t> len = sh.h_len;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t l = assign[i];
+        dst[i] = off[l] + len[l]++;
+        lab[i] = lab_host ? lab_host[i] : base + i;
+    }
+    std::copy(off.begin(), off.end(), hoff);
+    std::copy(tp.begin(), tp.end(), htp);
+    HIPANN_CHECK(hipMemcpyAsync(ix.add_up.p, ix.h_up.p, sizeof(int64_t) * up_n, hipMemcpyHostToDevice, st));
+    const int64_t *ddst = ix.add_up.get<int64_t>(), *dlab = ddst + n, *doff = dlab + n, *dtp = doff + nlist + 1;
+    if (grow) {
+        HIPANN_CHECK(hipMemcpyAsync(tp_new.p, dtp, sizeof(int64_t) * (size_t)(nlist + 1), hipMemcpyDeviceToDevice, st));
+        launch_ivf_sq_regroup(sq_view(ix), sh.list_off.get<int64_t>(), sh.list_len.get<int>(), tp_new.get<int64_t>(), doff,
+                              tp[nlist], N, codes_new.get<unsigned char>(), ids_new.get<int64_t>(),
+                              rown_new.get<float>(), st);
+        HIPANN_CHECK(hipStreamSynchronize(st));  // the old buffers are freed when the locals above go
+        auto take = [](DevBuf &a, DevBuf &b) {
+            std::swap(a.p, b.p);
+            std::swap(a.bytes, b.bytes);
+            std::swap(a.device, b.device);
+        };
+        take(ix.codes_t, codes_new);
+        take(sh.ids_buf, ids_new);
+        if (ix.metric == kL2) take(ix.rown, rown_new);
+        take(ix.tpass_off, tp_new);
+        sh.ids = sh.ids_buf.get<int64_t>();
+        ix.total_pass = tp[nlist];
+    }
+    launch_ivf_sq_encode_append(x_dev, n, sq_view(ix), assign_dev, ddst, lab_dev ? lab_dev : dlab, base, doff,
+                                ix.codes_t.get<unsigned char>(), ix.rown.get<float>(), sh.ids_buf.get<int64_t>(), cmax2,
+                                nullptr, st);
+    float *c2 = reinterpret_cast<float *>(ix.h_add.p);
+    HIPANN_CHECK(hipMemcpyAsync(c2, cmax2, sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPANN_CHECK(hipStreamSynchronize(st));
+    // the certificate's Cauchy-Schwarz term covers the new rows from here on (the create-time formula)
+    ix.cmax = std::max(ix.cmax, std::sqrt(*c2) * 1.0001f);
+    ivf_set_list_meta(sh, off, len, nlist);
+}
+
 }  // namespace
 
 extern "C" {
+
+int hipann_ivfsq_train_device(int d, int metric, int nlist, int by_residual, const float *centroids_dev, int64_t n,
+                              const float *x_dev, int device, float *vmin_dev, float *vdiff_dev, void *stream, char *eb,
+                              int el) {
+    return guard<int>(eb, el, -1, [&]() -> int {
+        int ndevs = 0;
+        if (hipGetDeviceCount(&ndevs) != hipSuccess || ndevs <= 0) throw HipError("hipann: no HIP device");
+        const char *bad = ivf_sq_check_train(d, metric, nlist, by_residual, centroids_dev != nullptr, n, x_dev != nullptr,
+                                             vmin_dev && vdiff_dev);
+        HIPANN_REQUIRE(!bad, bad);
+        HIPANN_REQUIRE(device >= 0 && device < ndevs, "invalid device");
+        sq_train_device(d, metric, nlist, by_residual ? 1 : 0, centroids_dev, n, x_dev, device, vmin_dev, vdiff_dev,
+                        static_cast<hipStream_t>(stream));
+        return 0;
+    });
+}
+
+int hipann_ivfsq_train(int d, int metric, int nlist, int by_residual, const float *centroids, int64_t n, const float *x,
+                       int device, float *vmin, float *vdiff, char *eb, int el) {
+    return guard<int>(eb, el, -1, [&]() -> int {
+        int ndevs = 0;
+        if (hipGetDeviceCount(&ndevs) != hipSuccess || ndevs <= 0) throw HipError("hipann: no HIP device");
+        const char *bad = ivf_sq_check_train(d, metric, nlist, by_residual, centroids != nullptr, n, x != nullptr,
+                                             vmin && vdiff);
+        HIPANN_REQUIRE(!bad, bad);
+        HIPANN_REQUIRE(device >= 0 && device < ndevs, "invalid device");
+        DeviceGuard g(device);
+        DevBuf rows, cen, out;
+        rows.ensure(sizeof(float) * (size_t)n * d, device);
+        out.ensure(sizeof(float) * 2 * (size_t)d, device);
+        HIPANN_CHECK(hipMemcpy(rows.p, x, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice));
+        if (by_residual) {
+            cen.ensure(sizeof(float) * (size_t)nlist * d, device);
+            HIPANN_CHECK(hipMemcpy(cen.p, centroids, sizeof(float) * (size_t)nlist * d, hipMemcpyHostToDevice));
+        }
+        hipStream_t st = nullptr;
+        HIPANN_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        try {
+            sq_train_device(d, metric, nlist, by_residual ? 1 : 0, cen.get<float>(), n, rows.get<float>(), device,
+                            out.get<float>(), out.get<float>() + d, st);
+        } catch (...) {
+            (void)hipStreamSynchronize(st);
+            (void)hipStreamDestroy(st);
+            throw;
+        }
+        HIPANN_CHECK(hipStreamDestroy(st));
+        HIPANN_CHECK(hipMemcpy(vmin, out.p, sizeof(float) * d, hipMemcpyDeviceToHost));
+        HIPANN_CHECK(hipMemcpy(vdiff, out.get<float>() + d, sizeof(float) * d, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+int hipann_ivfsq_add_device(void *h, int64_t n, const float *xb_dev, const int64_t *ids_dev, void *stream, char *eb,
+                            int el) {
+    return guard<int>(eb, el, -1, [&]() -> int {
+        IvfSqIndex *ix = as_sq(h);
+        HIPANN_REQUIRE(ix, "not an IVF SQ8 index");
+        HIPANN_REQUIRE(n >= 0 && (n == 0 || xb_dev), "invalid arguments");
+        if (n == 0) return 0;
+        std::lock_guard<std::mutex> lk(ix->mu);
+        IvfShard &sh = *ix->core->shards[0];
+        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : sh.stream;
+        FenceScope fs(sh.fence, st, sh.device);
+        AddStagingScope staging{*ix};
+        sq_add_rows(*ix, n, xb_dev, ids_dev, nullptr, st);
+        return 0;
+    });
+}
+
+int hipann_ivfsq_add(void *h, int64_t n, const float *xb, const int64_t *ids, char *eb, int el) {
+    return guard<int>(eb, el, -1, [&]() -> int {
+        IvfSqIndex *ix = as_sq(h);
+        HIPANN_REQUIRE(ix, "not an IVF SQ8 index");
+        HIPANN_REQUIRE(n >= 0 && (n == 0 || xb), "invalid arguments");
+        if (n == 0) return 0;
+        std::lock_guard<std::mutex> lk(ix->mu);
+        IvfShard &sh = *ix->core->shards[0];
+        DeviceGuard g(sh.device);
+        FenceScope fs(sh.fence, sh.stream, sh.device);
+        AddStagingScope staging{*ix};
+        // the whole call's rows on the device (n·d·4 bytes of staging: the refusal of a non-finite row comes before
+        // any row is appended, so no block can be committed ahead of a later block's check)
+        ix->add_rows.ensure(sizeof(float) * (size_t)n * ix->d, sh.device);
+        HIPANN_CHECK(hipMemcpyAsync(ix->add_rows.p, xb, sizeof(float) * (size_t)n * ix->d, hipMemcpyHostToDevice, sh.stream));
+        sq_add_rows(*ix, n, ix->add_rows.get<float>(), nullptr, ids, sh.stream);
+        return 0;
+    });
+}
 
 void *hipann_ivfsq_create(int d, int metric, int nlist, int nprobe, int by_residual, const float *centroids,
                           const float *vmin, const float *vdiff, const int64_t *list_offsets, const int64_t *ids,
@@ -318,18 +531,24 @@ int hipann_ivfsq_export(void *h, float *centroids, float *vmin, float *vdiff, in
         DeviceGuard g(sh.device);
         HIPANN_CHECK(hipDeviceSynchronize());
         const int nlist = ix->core->nlist, d = ix->d;
-        const int64_t n = sh.n;
-        if (list_offsets) std::memcpy(list_offsets, sh.h_off.data(), sizeof(int64_t) * (nlist + 1));
+        // dense CSR: the cumulative live lengths (the lists' append slack is not exported)
+        const int64_t n = sh.live;
+        std::vector<int64_t> doff((size_t)nlist + 1, 0);
+        for (int l = 0; l < nlist; ++l) doff[l + 1] = doff[l] + sh.h_len[l];
+        if (list_offsets) std::memcpy(list_offsets, doff.data(), sizeof(int64_t) * (nlist + 1));
         if (centroids) HIPANN_CHECK(hipMemcpy(centroids, sh.centroids, sizeof(float) * (size_t)nlist * d, hipMemcpyDeviceToHost));
         if (vmin) HIPANN_CHECK(hipMemcpy(vmin, ix->vmin.p, sizeof(float) * d, hipMemcpyDeviceToHost));
         if (vdiff) HIPANN_CHECK(hipMemcpy(vdiff, ix->vdiff.p, sizeof(float) * d, hipMemcpyDeviceToHost));
-        if (ids && n) HIPANN_CHECK(hipMemcpy(ids, sh.ids, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost));
-        if (codes && n) {
-            DevBuf raw;
-            raw.ensure((size_t)n * d, sh.device);
-            launch_ivf_sq_untile(sq_view(*ix), sh.list_off.get<int64_t>(), sh.list_len.get<int>(), ix->total_pass,
-                                 raw.get<unsigned char>(), sh.stream);
-            HIPANN_CHECK(hipMemcpyAsync(codes, raw.p, (size_t)n * d, hipMemcpyDeviceToHost, sh.stream));
+        if ((ids || codes) && n) {
+            DevBuf raw, rid, dof;
+            if (codes) raw.ensure((size_t)n * d, sh.device);
+            if (ids) rid.ensure(sizeof(int64_t) * (size_t)n, sh.device);
+            dof.ensure(sizeof(int64_t) * doff.size(), sh.device);
+            HIPANN_CHECK(hipMemcpyAsync(dof.p, doff.data(), sizeof(int64_t) * doff.size(), hipMemcpyHostToDevice, sh.stream));
+            launch_ivf_sq_untile(sq_view(*ix), sh.list_off.get<int64_t>(), sh.list_len.get<int>(), dof.get<int64_t>(),
+                                 ix->total_pass, raw.get<unsigned char>(), rid.get<int64_t>(), sh.stream);
+            if (codes) HIPANN_CHECK(hipMemcpyAsync(codes, raw.p, (size_t)n * d, hipMemcpyDeviceToHost, sh.stream));
+            if (ids) HIPANN_CHECK(hipMemcpyAsync(ids, rid.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, sh.stream));
             HIPANN_CHECK(hipStreamSynchronize(sh.stream));
         }
         return 0;
@@ -353,12 +572,17 @@ int64_t hipann_ivfsq_rerank_fallbacks(void *h) {
 }
 
 // measurement hook (tools/ivf_sq8_bench.py): "rechecked" = candidates the rerank has recomputed in the direct form since
-// creation; 0 on success
+// creation; "cmax" = the handle's current bound of max ‖c‖ (tests: it follows an add); 0 on success
 int hipann_debug_ivfsq_info(void *h, const char *name, double *out) {
     try {
         IvfSqIndex *ix = as_sq(h);
-        if (!ix || !name || !out || std::strcmp(name, "rechecked") != 0) return -1;
+        if (!ix || !name || !out) return -1;
         std::lock_guard<std::mutex> lk(ix->mu);
+        if (std::strcmp(name, "cmax") == 0) {
+            *out = (double)ix->cmax;
+            return 0;
+        }
+        if (std::strcmp(name, "rechecked") != 0) return -1;
         DeviceGuard g(ix->core->shards[0]->device);
         HIPANN_CHECK(hipDeviceSynchronize());
         unsigned long long v = 0;

@@ -41,8 +41,8 @@
 //   the fp32 roundings of s, b, u, A or P, N, the key's two additions, the decode and the direct form's d terms, each
 //   a few 2⁻²⁴ of products of magnitudes <= W = ‖q‖ + max‖g_l‖ + ‖(|vmin_i| + |vdiff_i|·256/255)_i‖:  <= (d + 16)·2⁻²²·W²
 //   E = 1.01·(2·(first two lines) + third line).
-// Proof obligations: (1) cmax and max‖g_l‖ are maxima over every row and list of the index (fixed at create; there is
-// no add); (2) a row is dropped only (a) against B_q + 2E at a time when some wave list held 16 rows with key <= B_q,
+// Proof obligations: (1) cmax and max‖g_l‖ are maxima over every row and list of the index (taken at create; an add
+// raises cmax by its rows' ‖c‖ before it returns, ivf_sq8_build.hip, and the centroids never change); (2) a row is dropped only (a) against B_q + 2E at a time when some wave list held 16 rows with key <= B_q,
 // which it still holds or has replaced by better ones at the end, so τ <= B_q for k <= 16 and the row's key > τ + 2E;
 // or (b) from a full wave list, with key >= that list's final 16th key; the rerank flags the query unless every full
 // sub-list's 16th key is > τ + 2E.  Then every dropped row has key > τ + 2E, so dist > τ + E, while the k rows with
@@ -54,6 +54,7 @@
 //
 // Resources (hipcc 7, gfx950, -O3): see DESIGN.md §5; no kernel here uses scratch.
 #include "runtime.hpp"
+#include "ivf_sq8_dev.hpp"
 #include "wave_topk.hpp"
 
 #include <algorithm>
@@ -85,19 +86,6 @@ int ivf_sq_group(int d) {
     int qt = SQ_QT;
     while (qt > 0 && sq_lds_bytes(nstep, 16 * qt) > SQ_LDS_MAX) --qt;
     return 16 * qt;
-}
-
-__device__ __forceinline__ unsigned sq_order_bits(float v) {
-    const unsigned b = __float_as_uint(v);
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float sq_order_float(unsigned o) {
-    return __uint_as_float((o >> 31) ? (o & 0x7fffffffu) : ~o);
-}
-
-// byte offset of (row rr of the pass, dim e) inside a pass of the tiled codes
-__device__ __forceinline__ int sq_tile_off(int rr, int e) {
-    return ((e >> 5) * 64 + ((e >> 3) & 3) * 16 + (rr & 15)) * 16 + (rr >> 4) * 8 + (e & 7);
 }
 
 // The direct form of one row against one query, by the whole wave (every lane returns the sum): lane-strided over
@@ -167,22 +155,28 @@ ivf_sq_tile(const unsigned char *__restrict__ codes, const int64_t *__restrict__
     }
 }
 
+// one block per pass: the pass's live rows -> row-major codes and labels at out_off[list] + the row's place in its list
+// (out_off = the dense offsets: the export of lists that carry append slack); codes or ids_out may be null
 __global__ void __launch_bounds__(256)
 ivf_sq_untile(const unsigned char *__restrict__ src, const int64_t *__restrict__ list_off,
-              const int *__restrict__ list_len, const int64_t *__restrict__ tpass_off, int nlist, int d, int nstep,
-              unsigned char *__restrict__ codes) {
+              const int *__restrict__ list_len, const int64_t *__restrict__ tpass_off,
+              const int64_t *__restrict__ out_off, const int64_t *__restrict__ ids, int nlist, int d, int nstep,
+              unsigned char *__restrict__ codes, int64_t *__restrict__ ids_out) {
     const int64_t pass = blockIdx.x;
     int lo = 0, hi = nlist - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (tpass_off[mid] <= pass) lo = mid; else hi = mid - 1;
     }
-    const int64_t r0 = list_off[lo] + (pass - tpass_off[lo]) * 32, r1 = list_off[lo] + list_len[lo];
+    const int64_t rel = (pass - tpass_off[lo]) * 32, o0 = out_off[lo] + rel;
+    const int64_t left = (int64_t)list_len[lo] - rel;
+    const int live = left < 32 ? (int)left : 32;  // (<= 0: a slack pass)
     const unsigned char *in = src + pass * (int64_t)nstep * 1024;
-    for (int t = threadIdx.x; t < 32 * d; t += 256) {
+    for (int t = threadIdx.x; codes && t < 32 * d; t += 256) {
         const int rr = t / d, e = t - rr * d;
-        if (r0 + rr < r1) codes[(r0 + rr) * (int64_t)d + e] = in[sq_tile_off(rr, e)];
+        if (rr < live) codes[(o0 + rr) * (int64_t)d + e] = in[sq_tile_off(rr, e)];
     }
+    if (ids_out && (int)threadIdx.x < live) ids_out[o0 + threadIdx.x] = ids[list_off[lo] + rel + threadIdx.x];
 }
 
 // one wave per row: N(row) (L2) and the running max of ‖c‖² (bits of a non-negative float order as integers)
@@ -743,11 +737,11 @@ void launch_ivf_sq_tile(const unsigned char *codes, const int64_t *list_off, con
     HIPANN_CHECK(hipGetLastError());
 }
 
-void launch_ivf_sq_untile(const IvfSqView &v, const int64_t *list_off, const int *list_len, int64_t total_pass,
-                          unsigned char *codes, hipStream_t st) {
+void launch_ivf_sq_untile(const IvfSqView &v, const int64_t *list_off, const int *list_len, const int64_t *out_off,
+                          int64_t total_pass, unsigned char *codes, int64_t *ids_out, hipStream_t st) {
     if (total_pass <= 0) return;
     hipLaunchKernelGGL(ivf_sq_untile, dim3((unsigned)total_pass), dim3(256), 0, st, v.codes_t, list_off, list_len,
-                       v.tpass_off, v.nlist, v.d, v.nstep, codes);
+                       v.tpass_off, out_off, v.ids, v.nlist, v.d, v.nstep, codes, ids_out);
     HIPANN_CHECK(hipGetLastError());
 }
 

@@ -79,6 +79,44 @@ inline std::vector<int64_t> ivf_sq_pass_offsets(const int64_t *list_offsets, int
     return tp;
 }
 
+// nullptr when the arguments of hipann_ivfsq_train describe a training set, else what is wrong with them
+inline const char *ivf_sq_check_train(int d, int metric, int nlist, int by_residual, bool have_centroids, int64_t n,
+                                      bool have_rows, bool have_out) {
+    if (d <= 0 || nlist <= 0) return "d and nlist must be > 0";
+    if (metric != 0 && metric != 1) return "metric must be 0 (L2) or 1 (IP)";
+    if (n < 1) return "training needs at least one row";
+    if (!have_rows || !have_out || (by_residual && !have_centroids)) return "null rows / centroids / vmin / vdiff";
+    return nullptr;
+}
+
+// nullptr when a trained quantizer is usable, else the error
+inline const char *ivf_sq_check_trained(const float *vmin, const float *vdiff, int d) {
+    for (int i = 0; i < d; ++i)
+        if (!std::isfinite(vmin[i]) || !std::isfinite(vdiff[i])) return "trained vmin / vdiff must be finite";
+    return nullptr;
+}
+
+// true when list l cannot take add[l] more rows in its slack for some l
+inline bool ivf_sq_must_grow(const std::vector<int64_t> &off, const std::vector<int64_t> &len,
+                             const std::vector<int64_t> &add) {
+    for (size_t l = 0; l < len.size(); ++l)
+        if (len[l] + add[l] > off[l + 1] - off[l]) return true;
+    return false;
+}
+
+// The list starts after growth (IVFFlat's rule, ivf_relayout): every list leaves with capacity max(cap, need +
+// max(need / 4, 64)) rows, need = len + add, rounded up to whole 32-row passes.
+inline std::vector<int64_t> ivf_sq_grown_offsets(const std::vector<int64_t> &off, const std::vector<int64_t> &len,
+                                                 const std::vector<int64_t> &add) {
+    std::vector<int64_t> out(off.size(), 0);
+    for (size_t l = 0; l < len.size(); ++l) {
+        const int64_t cap = off[l + 1] - off[l], need = len[l] + add[l];
+        const int64_t ncap = std::max(cap, need + std::max<int64_t>(need / 4, 64));
+        out[l + 1] = out[l] + (ncap + 31) / 32 * 32;
+    }
+    return out;
+}
+
 // the most (probe, chunk) slots a query can own: the chunk counts of its nprobe longest lists
 inline int64_t ivf_sq_query_slots(const std::vector<int64_t> &len, int np, int chunk_rows) {
     std::vector<int64_t> nch;

@@ -58,7 +58,12 @@ struct HostBuf {
     HostBuf() = default;
     HostBuf(const HostBuf &) = delete;
     HostBuf &operator=(const HostBuf &) = delete;
-    ~HostBuf() { if (p) (void)hipHostFree(p); }
+    ~HostBuf() { release(); }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
     // (returns true when it allocated: the contents are undefined then)
     bool ensure(size_t need, unsigned flags = hipHostMallocDefault) {
         if (need <= bytes && p) return false;
@@ -528,12 +533,25 @@ struct IvfSqIndex : IndexBase {
     bool probes_kept = false;    // the last call ran in query slices: its probe lists are in `probes`
     int64_t last_nq = 0;
     int last_np = 0;
+    // an add's staging (hipann_ivfsq_add): the host rows, [assignment | non-finite flag], the assignment's distances
+    // (discarded), [destination | label per row | new list offsets]; pinned: the readback, the upload.  Kept between
+    // calls only while small (release_add_staging): a run of chunk adds reuses them, a bulk add gives its bytes back
+    DevBuf add_rows, add_assign, add_cd, add_up;
+    HostBuf h_add, h_up;
+    static constexpr size_t kAddStagingKeep = (size_t)64 << 20;  // per buffer
+    void release_add_staging() {
+        for (DevBuf *b : {&add_rows, &add_assign, &add_cd, &add_up})
+            if (b->bytes > kAddStagingKeep) b->release();
+        for (HostBuf *b : {&h_add, &h_up})
+            if (b->bytes > kAddStagingKeep) b->release();
+    }
     IvfSqIndex() : IndexBase(Kind::IVFSQ) {}
     int64_t ntotal() const override { return core ? core->ntotal() : 0; }
-    // the tiled codes, N(row), labels, centroids and their norms, list offsets and lengths, the quantizer and pass offsets
+    // the tiled codes, N(row), labels (slack rows included), centroids and their norms, list offsets and lengths, the
+    // quantizer and pass offsets
     int64_t memory_bytes() const override {
         if (!core) return 0;
-        const int64_t n = ntotal(), nl = core->nlist;
+        const int64_t n = core->shards[0]->n, nl = core->nlist;
         return (int64_t)codes_t.bytes + (int64_t)rown.bytes + n * 8 + nl * d * 4 + (metric == kL2 ? nl * 4 : 0) +
                (nl + 1) * 8 + nl * 4 + (int64_t)d * 8 + (int64_t)sb.bytes + (int64_t)tpass_off.bytes;
     }
@@ -810,8 +828,9 @@ int ivf_sq_group(int d);  // queries per scan item (a multiple of 16; 0: the que
 void launch_ivf_sq_tile(const unsigned char *codes, const int64_t *list_off, const int *list_len,
                         const int64_t *tpass_off, int nlist, int64_t total_pass, int d, int nstep, unsigned char *dst,
                         hipStream_t st);
-void launch_ivf_sq_untile(const IvfSqView &v, const int64_t *list_off, const int *list_len, int64_t total_pass,
-                          unsigned char *codes, hipStream_t st);
+// the live rows' codes (row-major) and labels at out_off[list] + the row's place in its list; either output may be null
+void launch_ivf_sq_untile(const IvfSqView &v, const int64_t *list_off, const int *list_len, const int64_t *out_off,
+                          int64_t total_pass, unsigned char *codes, int64_t *ids_out, hipStream_t st);
 void launch_ivf_sq_row_terms(const unsigned char *codes, const IvfSqView &v, const int64_t *list_off, int nlist,
                              float *rown, unsigned *cmax2, hipStream_t st);
 void launch_ivf_sq_query_prep(const float *Q, int64_t nq, const IvfSqView &v, float cmax, float wbase, void *qimg,

@@ -138,6 +138,10 @@ def lib() -> C.CDLL:
             "hipann_ivfsq_last_probes": ([vp, i64p, i64, cp, i32], i32),
             "hipann_ivfsq_export": ([vp, f, f, f, i64p, i64p, C.POINTER(C.c_uint8), cp, i32], i32),
             "hipann_ivfsq_rerank_fallbacks": ([vp], i64),
+            "hipann_ivfsq_train": ([i32, i32, i32, i32, f, i64, f, i32, f, f, cp, i32], i32),
+            "hipann_ivfsq_train_device": ([i32, i32, i32, i32, vp, i64, vp, i32, vp, vp, vp, cp, i32], i32),
+            "hipann_ivfsq_add": ([vp, i64, f, i64p, cp, i32], i32),
+            "hipann_ivfsq_add_device": ([vp, i64, vp, vp, vp, cp, i32], i32),
             "hipann_ntotal": ([vp], i64),
             "hipann_dim": ([vp], i32),
             "hipann_metric": ([vp], i32),
@@ -706,8 +710,25 @@ class HipIndexIVFSQ8(_Handle):
         _check(lib().hipann_ivfsq_last_probes(self._h, _ptr(P, C.c_int64), P.size, eb, 1024), eb)
         return P
 
+    def add(self, x, ids=None) -> None:
+        """IndexIVFScalarQuantizer::add / add_with_ids on the GPU copy (hipann_ivfsq_add): rows assigned by the GPU
+        coarse quantizer, encoded on the device and appended to their lists in insertion order; labels ``ids`` or
+        ntotal + i.  A row with a non-finite entry fails the call before anything changes."""
+        x = _f32_2d(x, self.d)
+        idv = None if ids is None else np.ascontiguousarray(ids, np.int64)
+        if idv is not None and idv.shape != (x.shape[0],):
+            raise ValueError("ids must hold one label per row")
+        eb = _err()
+        _check(lib().hipann_ivfsq_add(self._h, x.shape[0], _ptr(x, C.c_float), _ptr(idv, C.c_int64), eb, 1024), eb)
+
+    def add_device(self, n: int, x_ptr: int, ids_ptr: int = 0, stream: int = 0) -> None:
+        """hipann_ivfsq_add_device: the same with the rows (n x d fp32) and the labels (0: ntotal + i) in HBM."""
+        eb = _err()
+        _check(lib().hipann_ivfsq_add_device(self._h, n, C.c_void_p(x_ptr), C.c_void_p(ids_ptr or None),
+                                             C.c_void_p(stream or None), eb, 1024), eb)
+
     def export(self) -> dict:
-        """The index as it was created (hipann_ivfsq_export) — what GpuToCpu rebuilds the CPU index from."""
+        """The index as dense CSR (hipann_ivfsq_export) — what GpuToCpu rebuilds the CPU index from."""
         off = np.empty(self.nlist + 1, np.int64)
         eb = _err()
         _check(lib().hipann_ivfsq_export(self._h, None, None, None, _ptr(off, C.c_int64), None, None, eb, 1024), eb)
@@ -725,6 +746,29 @@ class HipIndexIVFSQ8(_Handle):
     def rerank_fallbacks(self) -> int:
         """Queries the scan's certificate flagged since creation (re-run on the device by the direct kernel)."""
         return int(lib().hipann_ivfsq_rerank_fallbacks(self._h))
+
+
+def ivfsq_train(x, centroids, metric: int = METRIC_L2, by_residual: bool = True,
+                device: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """hipann_ivfsq_train: ScalarQuantizer::train for QT_8bit (min/max) on the GPU over the rows given — of the
+    residuals to each row's assigned centroid when ``by_residual``.  Returns (vmin, vdiff) for HipIndexIVFSQ8."""
+    cen = _f32_2d(centroids)
+    nlist, d = cen.shape
+    x = _f32_2d(x, d)
+    vmn, vdf = np.empty(d, np.float32), np.empty(d, np.float32)
+    eb = _err()
+    _check(lib().hipann_ivfsq_train(d, metric, nlist, 1 if by_residual else 0, _ptr(cen, C.c_float), x.shape[0],
+                                    _ptr(x, C.c_float), device, _ptr(vmn, C.c_float), _ptr(vdf, C.c_float), eb, 1024), eb)
+    return vmn, vdf
+
+
+def ivfsq_train_device(d: int, nlist: int, n: int, x_ptr: int, centroids_ptr: int, vmin_ptr: int, vdiff_ptr: int,
+                       metric: int = METRIC_L2, by_residual: bool = True, device: int = 0, stream: int = 0) -> None:
+    """hipann_ivfsq_train_device: the same with the rows, the centroids and both outputs (d fp32 each) in HBM."""
+    eb = _err()
+    _check(lib().hipann_ivfsq_train_device(d, metric, nlist, 1 if by_residual else 0, C.c_void_p(centroids_ptr), n,
+                                           C.c_void_p(x_ptr), device, C.c_void_p(vmin_ptr), C.c_void_p(vdiff_ptr),
+                                           C.c_void_p(stream or None), eb, 1024), eb)
 
 
 KMEANS_INIT_RANDOM, KMEANS_INIT_PLUSPLUS = 0, 1

@@ -436,8 +436,35 @@ int64_t hipann_ivf_rerank_fallbacks(void *index);
  * device (no host readback: the _device call stays asynchronous).
  * The handle is single-device (per-handle mutex, one stream plus scratch, err_buf as everywhere) and serves
  * hipann_ntotal / _dim / _metric / _memory_bytes / _free / _set_kernel_timing / _last_kernel_ms (which = 0: the code
- * scan); every other entry point rejects it with −1.  There is no add, remove or range search.
+ * scan); every other entry point rejects it with −1.  There is no remove or range search.
+ * Train (hipann_ivfsq_train): FAISS's ScalarQuantizer::train for QT_8bit with the default range statistic (min/max,
+ * argument 0) over the n >= 1 rows given (the caller samples): e = x − g_assign when by_residual (one fp32 subtraction
+ * per entry), else e = x; vmin_i = min e_i, vdiff_i = fl32(max e_i − min e_i).  The assignment is hipann_ivf_add's:
+ * the Flat k = 1 search over the centroids with the metric's order, ties by list id, in blocks of 65536 rows; min and
+ * max are exact, so the result is determined by the assignment.  A non-finite vmin / vdiff is an error ("finite").
+ * The _device form takes the rows, the centroids and both outputs in HBM and returns after the check.
+ * Add (hipann_ivfsq_add): rows are assigned as above and encoded per entry, in fp32 and in this order: e as above,
+ * xi = vdiff_i != 0 ? (e_i − vmin_i) / vdiff_i : 0 (the correctly rounded division) clamped to [0, 1],
+ * code_i = (uint8)(int)(255.0f * xi).  Rows are appended to their lists in insertion order (rows of a later
+ * 65536-row block follow an earlier block's) with labels ids[i] (NULL: ntotal + i).  A row holding a non-finite entry
+ * fails the call ("finite") before anything changes; the call is all-or-nothing (every buffer is allocated before the
+ * index changes); n == 0 returns 0; a handle created with zero rows can be added to.  Lists grow with slack
+ * (capacity max(cap, need + max(need / 4, 64)) rows in whole 32-row passes, every list at once), so most adds only
+ * encode; hipann_memory_bytes counts the slack.  The host form stages the call's n·d·4 bytes on the device; staging
+ * (device and pinned) above 64 MiB per buffer is freed before the call returns, smaller buffers are kept for the next
+ * add and are not part of hipann_memory_bytes.  Every
+ * search path, hipann_ntotal and hipann_ivfsq_export see the grown index, and an index created from that export
+ * returns the same bits for every search.
  * ------------------------------------------------------------------------------------------- */
+int hipann_ivfsq_train(int d, int metric, int nlist, int by_residual, const float *centroids,
+                       int64_t n, const float *x, int device, float *vmin, float *vdiff,
+                       char *err_buf, int err_len);
+int hipann_ivfsq_train_device(int d, int metric, int nlist, int by_residual, const float *centroids_dev,
+                              int64_t n, const float *x_dev, int device, float *vmin_dev, float *vdiff_dev,
+                              void *stream, char *err_buf, int err_len);
+int hipann_ivfsq_add(void *index, int64_t n, const float *xb, const int64_t *ids, char *err_buf, int err_len);
+int hipann_ivfsq_add_device(void *index, int64_t n, const float *xb_dev, const int64_t *ids_dev, void *stream,
+                            char *err_buf, int err_len);
 void *hipann_ivfsq_create(int d, int metric, int nlist, int nprobe, int by_residual,
                           const float *centroids, const float *vmin, const float *vdiff,
                           const int64_t *list_offsets, const int64_t *ids, const uint8_t *codes,
@@ -448,7 +475,8 @@ int hipann_ivfsq_search_device(void *index, int nprobe, int64_t nq, const float 
                                float *D_dev, int64_t *I_dev, void *stream, char *err_buf, int err_len);
 /* The last call's probe lists (nq × min(nprobe, nlist) int64). */
 int hipann_ivfsq_last_probes(void *index, int64_t *probes, int64_t cap, char *err_buf, int err_len);
-/* GpuToCpu: the index as it was created (the codes are un-tiled on the device); any output may be NULL. */
+/* GpuToCpu: the index as dense CSR (offsets = the cumulative live lengths, ids and codes without slack rows; the
+ * codes are un-tiled on the device) — a handle never added to: as it was created; any output may be NULL. */
 int hipann_ivfsq_export(void *index, float *centroids, float *vmin, float *vdiff, int64_t *list_offsets,
                         int64_t *ids, uint8_t *codes, char *err_buf, int err_len);
 /* Queries the certificate flagged since the index was created (reading the count synchronises the device). */
