@@ -181,8 +181,9 @@ private:
 };
 
 #ifdef HIPANN_HAVE_IVFSQ
-// IndexIVFScalarQuantizer with QT_8bit codes ("IVFn,SQ8"): hipann_ivfsq_* (hip_ann.h).  Search and add; a removal
-// rebuilds the GPU copy from the CPU index.
+// IndexIVFScalarQuantizer with QT_8bit codes ("IVFn,SQ8"): hipann_ivfsq_* (hip_ann.h).  Search, add and remove all
+// work on the resident copy: a DELETE or VACUUM calls remove_labels beside the CPU index's remove_ids and the two
+// stay equal (hipann_ivfsq_export: offsets, ids and codes, byte for byte), with no host walk of the inverted lists.
 class HipIndexIVFSQ : public faiss::Index {
 public:
     static bool supported(const faiss::IndexIVFScalarQuantizer &cpu) {
@@ -233,6 +234,17 @@ public:
         char err[512] = {0};
         check(hipann_ivfsq_search(handle_->h, np, n, x, k, distances, reinterpret_cast<int64_t *>(labels), err, sizeof err),
               err);
+    }
+    // IndexIVF::remove_ids with an IDSelectorBatch over `labels` on the GPU copy (hipann_ivfsq_remove_ids): FAISS's
+    // list order inside the tiled codes; ids, centroids and the quantizer unchanged, the freed rows are append slack.
+    // Returns the rows removed.  Adds after a removal must carry explicit ids (add_with_ids).
+    size_t remove_labels(const faiss::idx_t *labels, size_t n) {
+        char err[512] = {0};
+        const int64_t r = hipann_ivfsq_remove_ids(handle_->h, reinterpret_cast<const int64_t *>(labels), (int64_t)n, err,
+                                                  sizeof err);
+        if (r < 0) throw std::runtime_error(std::string("hipann_ivfsq_remove_ids: ") + err);
+        ntotal -= r;
+        return (size_t)r;
     }
     void reset() override { throw std::runtime_error("HipIndexIVFSQ::reset: rebuild from the CPU index"); }
     void set_nprobe(size_t np) { nprobe_ = np; }

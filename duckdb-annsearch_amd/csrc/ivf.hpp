@@ -54,4 +54,11 @@ void launch_ivf_sq_encode_append(const float *x, int64_t n, const IvfSqView &v, 
 void launch_ivf_sq_regroup(const IvfSqView &v, const int64_t *list_off, const int *list_len, const int64_t *tp_new,
                            const int64_t *off_new, int64_t npass_new, int64_t nrows_new, unsigned char *codes_new,
                            int64_t *ids_new, float *rown_new, hipStream_t st);
+// ivf_sq8_remove.hip — hipann_ivfsq_remove_ids: every live row whose id is in labels (device, sorted unique) leaves
+// its list in FAISS's order, moved inside the tiled layout (one block per list: mark, closed-form plan, move the 8-byte
+// pieces, label and N(row); the vacated rows back to zero slack; list_len and newlen[l] = the new length).  mark: one
+// byte, plan: one int per physical row; v.tpass_off: the lists' passes.
+void launch_ivf_sq_remove_rows(const int64_t *labels, int64_t m, const IvfSqView &v, const int64_t *list_off,
+                               int *list_len, unsigned char *codes_t, int64_t *ids, float *rown, unsigned char *mark,
+                               int *plan, int *newlen, hipStream_t st);
 }  // namespace hipann

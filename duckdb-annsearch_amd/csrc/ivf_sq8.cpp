@@ -304,6 +304,41 @@ void sq_add_rows(IvfSqIndex &ix, int64_t n, const float *x_dev, const int64_t *l
     ivf_set_list_meta(sh, off, len, nlist);
 }
 
+// ---- remove: every row whose label is in lab (sorted, unique) leaves its list, in FAISS's order ----
+// Stages, on st: the labels up; ALL scratch (labels, one mark byte and one plan int per physical row, one new length
+// per list) allocated before the launch, so a failed allocation leaves the handle as it was; the one kernel
+// (ivf_sq8_remove.hip); the new lengths back in one copy; the host mirror through ivf_set_list_meta.  List starts,
+// pass offsets and every buffer of the index stay: the freed rows are append slack.  cmax stays too — obligation (1)
+// of ivf_sq8.hip asks for an upper bound of ‖c‖ over the rows held, and the maximum over a superset of them is one.
+int64_t sq_remove_rows(IvfSqIndex &ix, const std::vector<int64_t> &lab, hipStream_t st) {
+    IvfShard &sh = *ix.core->shards[0];
+    if (!sh.live || lab.empty()) return 0;
+    DeviceGuard g(sh.device);
+    RoctxRange rr("hipann.ivfsq.remove");
+    const int nlist = ix.core->nlist, dev = sh.device;
+    const int64_t m = (int64_t)lab.size();
+    DevBuf labels, mark, plan, newlen;
+    labels.ensure(sizeof(int64_t) * (size_t)m, dev);
+    mark.ensure((size_t)sh.n, dev);
+    plan.ensure(sizeof(int) * (size_t)sh.n, dev);
+    newlen.ensure(sizeof(int) * (size_t)nlist, dev);
+    std::vector<int> hl((size_t)nlist);
+    std::vector<int64_t> len = sh.h_len;
+    HIPANN_CHECK(hipMemcpyAsync(labels.p, lab.data(), sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, st));
+    {
+        ScopedTiming t(ix.timer_main, st);
+        launch_ivf_sq_remove_rows(labels.get<int64_t>(), m, sq_view(ix), sh.list_off.get<int64_t>(),
+                                  sh.list_len.get<int>(), ix.codes_t.get<unsigned char>(), sh.ids_buf.get<int64_t>(),
+                                  ix.rown.get<float>(), mark.get<unsigned char>(), plan.get<int>(), newlen.get<int>(), st);
+    }
+    HIPANN_CHECK(hipMemcpyAsync(hl.data(), newlen.p, sizeof(int) * (size_t)nlist, hipMemcpyDeviceToHost, st));
+    HIPANN_CHECK(hipStreamSynchronize(st));  // (the scratch above is released on return)
+    const int64_t removed = ivf_sq_removed_lengths(len, hl.data());
+    HIPANN_REQUIRE(removed >= 0, "IVF SQ8 remove: a list's new length is out of range");
+    if (removed > 0) ivf_set_list_meta(sh, sh.h_off, len, nlist);  // h_len, live, max_nch and the device lengths
+    return removed;
+}
+
 }  // namespace
 
 extern "C" {
@@ -393,6 +428,19 @@ int hipann_ivfsq_add(void *h, int64_t n, const float *xb, const int64_t *ids, ch
         HIPANN_CHECK(hipMemcpyAsync(ix->add_rows.p, xb, sizeof(float) * (size_t)n * ix->d, hipMemcpyHostToDevice, sh.stream));
         sq_add_rows(*ix, n, ix->add_rows.get<float>(), nullptr, ids, sh.stream);
         return 0;
+    });
+}
+
+int64_t hipann_ivfsq_remove_ids(void *h, const int64_t *labels, int64_t n, char *eb, int el) {
+    return guard<int64_t>(eb, el, -1, [&]() -> int64_t {
+        IvfSqIndex *ix = as_sq(h);
+        HIPANN_REQUIRE(ix, "not an IVF SQ8 index");
+        HIPANN_REQUIRE(n >= 0 && (n == 0 || labels), "invalid labels");
+        if (n == 0) return 0;
+        std::lock_guard<std::mutex> lk(ix->mu);
+        IvfShard &sh = *ix->core->shards[0];
+        FenceScope fs(sh.fence, sh.stream, sh.device);
+        return sq_remove_rows(*ix, ivf_sq_label_set(labels, n), sh.stream);
     });
 }
 

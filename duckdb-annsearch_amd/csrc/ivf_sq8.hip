@@ -42,7 +42,9 @@
 //   a few 2⁻²⁴ of products of magnitudes <= W = ‖q‖ + max‖g_l‖ + ‖(|vmin_i| + |vdiff_i|·256/255)_i‖:  <= (d + 16)·2⁻²²·W²
 //   E = 1.01·(2·(first two lines) + third line).
 // Proof obligations: (1) cmax and max‖g_l‖ are maxima over every row and list of the index (taken at create; an add
-// raises cmax by its rows' ‖c‖ before it returns, ivf_sq8_build.hip, and the centroids never change); (2) a row is dropped only (a) against B_q + 2E at a time when some wave list held 16 rows with key <= B_q,
+// raises cmax by its rows' ‖c‖ before it returns, ivf_sq8_build.hip, a removal keeps it — an upper bound is all the
+// first line needs, and a maximum over a superset of the rows held is one, ivf_sq8_remove.hip — and the centroids
+// never change); (2) a row is dropped only (a) against B_q + 2E at a time when some wave list held 16 rows with key <= B_q,
 // which it still holds or has replaced by better ones at the end, so τ <= B_q for k <= 16 and the row's key > τ + 2E;
 // or (b) from a full wave list, with key >= that list's final 16th key; the rerank flags the query unless every full
 // sub-list's 16th key is > τ + 2E.  Then every dropped row has key > τ + 2E, so dist > τ + E, while the k rows with

@@ -117,6 +117,26 @@ inline std::vector<int64_t> ivf_sq_grown_offsets(const std::vector<int64_t> &off
     return out;
 }
 
+// hipann_ivfsq_remove_ids: the caller's labels as a set (FAISS's IDSelectorBatch), sorted for the kernel's search
+inline std::vector<int64_t> ivf_sq_label_set(const int64_t *labels, int64_t n) {
+    std::vector<int64_t> lab(labels, labels + n);
+    std::sort(lab.begin(), lab.end());
+    lab.erase(std::unique(lab.begin(), lab.end()), lab.end());
+    return lab;
+}
+
+// The lists' lengths after a removal, from the kernel's readback: the rows removed, or -1 when a new length is not
+// within [0, old length] (nothing of len has changed then).
+inline int64_t ivf_sq_removed_lengths(std::vector<int64_t> &len, const int *newlen) {
+    int64_t removed = 0;
+    for (size_t l = 0; l < len.size(); ++l) {
+        if (newlen[l] < 0 || newlen[l] > len[l]) return -1;
+        removed += len[l] - newlen[l];
+    }
+    for (size_t l = 0; l < len.size(); ++l) len[l] = newlen[l];
+    return removed;
+}
+
 // the most (probe, chunk) slots a query can own: the chunk counts of its nprobe longest lists
 inline int64_t ivf_sq_query_slots(const std::vector<int64_t> &len, int np, int chunk_rows) {
     std::vector<int64_t> nch;

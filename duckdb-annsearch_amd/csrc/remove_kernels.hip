@@ -11,6 +11,7 @@
 // order in closed form — with L live rows, r of them marked and L' = L − r, the marked positions below L' ascending
 // receive the unmarked positions at or above L' descending — moves the pairs (sources and destinations are
 // disjoint), zeroes the vacated rows and publishes the new length and the tiled passes it touched.
+#include "remove_dev.hpp"
 #include "runtime.hpp"
 
 #include <algorithm>
@@ -22,24 +23,6 @@ namespace {
 constexpr int kScanThreads = 256;
 constexpr int kScanPer = 4;                          // rows per thread of the prefix-sum kernels
 constexpr int kScanRows = kScanThreads * kScanPer;  // rows per block
-
-// exclusive position of a set flag among the block's flags (thread order) and their count; wsum: one int per wave
-__device__ __forceinline__ int block_flag_scan(bool f, int *wsum, int *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const unsigned long long b = __ballot(f);
-    const int pre = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[w] = __popcll(b);
-    __syncthreads();
-    int add = 0, tot = 0;
-    for (int i = 0; i < nw; ++i) {
-        const int c = wsum[i];
-        if (i < w) add += c;
-        tot += c;
-    }
-    __syncthreads();
-    *total = tot;
-    return pre + add;
-}
 
 // keep[labels[i] − first] = 0 (labels: the shard's removed rows, sorted, unique, local; keep was set to 1)
 __global__ void __launch_bounds__(256)
@@ -143,15 +126,6 @@ flat_remove_gather_f32(const float *__restrict__ v, const int64_t *__restrict__ 
                        float *__restrict__ out) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j < cnt) out[j] = v[idx[j]];
-}
-
-__device__ __forceinline__ bool label_member(const int64_t *__restrict__ labels, int64_t m, int64_t id) {
-    int64_t lo = 0, hi = m;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (labels[mid] < id) lo = mid + 1; else hi = mid;
-    }
-    return lo < m && labels[lo] == id;
 }
 
 // One block per list (grid-stride).  mark: one byte per physical row; plan: one int per physical row — the list's

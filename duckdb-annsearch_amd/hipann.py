@@ -142,6 +142,7 @@ def lib() -> C.CDLL:
             "hipann_ivfsq_train_device": ([i32, i32, i32, i32, vp, i64, vp, i32, vp, vp, vp, cp, i32], i32),
             "hipann_ivfsq_add": ([vp, i64, f, i64p, cp, i32], i32),
             "hipann_ivfsq_add_device": ([vp, i64, vp, vp, vp, cp, i32], i32),
+            "hipann_ivfsq_remove_ids": ([vp, i64p, i64, cp, i32], i64),
             "hipann_ntotal": ([vp], i64),
             "hipann_dim": ([vp], i32),
             "hipann_metric": ([vp], i32),
@@ -726,6 +727,17 @@ class HipIndexIVFSQ8(_Handle):
         eb = _err()
         _check(lib().hipann_ivfsq_add_device(self._h, n, C.c_void_p(x_ptr), C.c_void_p(ids_ptr or None),
                                              C.c_void_p(stream or None), eb, 1024), eb)
+
+    def remove_ids(self, labels) -> int:
+        """faiss::IndexIVF::remove_ids on the GPU copy (hipann_ivfsq_remove_ids): rows whose id is in ``labels`` leave
+        their lists in FAISS's order (each hole filled by the list's last entry), moved inside the tiled codes; the
+        freed rows are append slack, ``memory_bytes`` does not change.  Returns the rows removed.  Pass explicit ids to
+        every ``add`` after a removal."""
+        lab = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
+        eb = _err()
+        rc = int(lib().hipann_ivfsq_remove_ids(self._h, _ptr(lab, C.c_int64), lab.size, eb, 1024))
+        _check(min(rc, 0), eb)
+        return rc
 
     def export(self) -> dict:
         """The index as dense CSR (hipann_ivfsq_export) — what GpuToCpu rebuilds the CPU index from."""

@@ -436,7 +436,7 @@ int64_t hipann_ivf_rerank_fallbacks(void *index);
  * device (no host readback: the _device call stays asynchronous).
  * The handle is single-device (per-handle mutex, one stream plus scratch, err_buf as everywhere) and serves
  * hipann_ntotal / _dim / _metric / _memory_bytes / _free / _set_kernel_timing / _last_kernel_ms (which = 0: the code
- * scan); every other entry point rejects it with −1.  There is no remove or range search.
+ * scan; after hipann_ivfsq_remove_ids: its kernel); every other entry point rejects it with −1.  There is no range search.
  * Train (hipann_ivfsq_train): FAISS's ScalarQuantizer::train for QT_8bit with the default range statistic (min/max,
  * argument 0) over the n >= 1 rows given (the caller samples): e = x − g_assign when by_residual (one fp32 subtraction
  * per entry), else e = x; vmin_i = min e_i, vdiff_i = fl32(max e_i − min e_i).  The assignment is hipann_ivf_add's:
@@ -455,6 +455,22 @@ int64_t hipann_ivf_rerank_fallbacks(void *index);
  * add and are not part of hipann_memory_bytes.  Every
  * search path, hipann_ntotal and hipann_ivfsq_export see the grown index, and an index created from that export
  * returns the same bits for every search.
+ * Remove (hipann_ivfsq_remove_ids): faiss::IndexIVF::remove_ids with an IDSelectorBatch (DirectMap NoMap branch), the
+ * semantics of hipann_ivf_remove_ids.  Every row whose id is in labels[] (host, any order; duplicates and absent ids
+ * are ignored) leaves its list; per list, FAISS's order: j = 0, l = len; while (j < l) { if member(id[j]) { --l;
+ * entry[j] = entry[l]; } else ++j; } — so hipann_ivfsq_export after the call equals the CPU index's lists after the
+ * same call: offsets, ids and codes, byte for byte.  Ids of surviving rows, the centroids, vmin / vdiff, the lists'
+ * capacities and pass offsets do not change; the rows move inside the tiled codes on the device (one kernel; the cost
+ * is the id lookup, 8 bytes per live row, plus the rows moved and cleared, not the table).  Freed rows become append
+ * slack that a later hipann_ivfsq_add fills before it regroups; hipann_memory_bytes is unchanged.  Returns the rows
+ * removed, or −1.  Synchronous, under the handle's lock; n == 0 returns 0 and launches nothing.  All-or-nothing: every
+ * scratch buffer is allocated before the kernel is launched, and a failure leaves the handle answering as before.
+ * Extra HBM during the call, freed before it returns: 8 bytes per distinct label, 5 bytes per physical row (slack
+ * included: one mark byte, one plan int) and 4 per list.  The certificate's bound of max ‖c‖ is kept: a maximum over
+ * a superset of the rows is still an upper bound.  A handle that is not an IVF SQ8 handle gets −1, and
+ * hipann_ivf_remove_ids rejects an IVF SQ8 handle.
+ * NOTE: hipann_ivfsq_add with ids == NULL still labels its rows ntotal + i, as FAISS does; after a removal that can
+ * repeat a surviving id — pass explicit ids to every add that follows a remove.
  * ------------------------------------------------------------------------------------------- */
 int hipann_ivfsq_train(int d, int metric, int nlist, int by_residual, const float *centroids,
                        int64_t n, const float *x, int device, float *vmin, float *vdiff,
@@ -465,6 +481,7 @@ int hipann_ivfsq_train_device(int d, int metric, int nlist, int by_residual, con
 int hipann_ivfsq_add(void *index, int64_t n, const float *xb, const int64_t *ids, char *err_buf, int err_len);
 int hipann_ivfsq_add_device(void *index, int64_t n, const float *xb_dev, const int64_t *ids_dev, void *stream,
                             char *err_buf, int err_len);
+int64_t hipann_ivfsq_remove_ids(void *index, const int64_t *labels, int64_t n, char *err_buf, int err_len);
 void *hipann_ivfsq_create(int d, int metric, int nlist, int nprobe, int by_residual,
                           const float *centroids, const float *vmin, const float *vdiff,
                           const int64_t *list_offsets, const int64_t *ids, const uint8_t *codes,

@@ -48,6 +48,13 @@ int main() {
     CHECK(ivf_sq_query_slots(len, 1, 2048) == 3 && ivf_sq_query_slots(len, 2, 2048) == 5);
     CHECK(ivf_sq_query_slots(len, 9, 2048) == 6 && ivf_sq_query_slots({0, 0}, 2, 2048) == 1);
     CHECK(ivf_sq_slice_queries(1000, 6, 1536, 256 << 20) == 1000 && ivf_sq_slice_queries(1000, 64, 16384, 1 << 20) == 1);
-    std::printf(fails ? "%d checks failed\n" : "ivf_sq8 host checks passed\n", fails);
+    // hipann_ivfsq_remove_ids: the label set and the length bookkeeping
+    const int64_t raw[] = {9, -3, 9, 1LL << 40, -3, 0};
+    CHECK((ivf_sq_label_set(raw, 6) == std::vector<int64_t>{-3, 0, 9, 1LL << 40}) && ivf_sq_label_set(raw, 0).empty());
+    std::vector<int64_t> cur = len;
+    const int after[] = {0, 30, 2049, 0}, over[] = {0, 32, 2049, 0}, neg[] = {0, 31, -1, 0};
+    CHECK(ivf_sq_removed_lengths(cur, over) == -1 && ivf_sq_removed_lengths(cur, neg) == -1 && cur == len);
+    CHECK(ivf_sq_removed_lengths(cur, after) == 4098 && (cur == std::vector<int64_t>{0, 30, 2049, 0}));
+    std::printf(fails ?"%d checks failed\n" : "ivf_sq8 host checks passed\n", fails);
     return fails ? 1 : 0;
 }
