@@ -49,6 +49,7 @@
 //
 // Every kernel reads list_len, never list_off[l + 1]: the zero-filled append slack is never scanned, and a chunk past
 // a list's end or an empty list owns no slot.
+#include "ivf_range_dev.hpp"
 #include "rerank_rows.hpp"
 #include "runtime.hpp"
 
@@ -62,8 +63,6 @@ typedef unsigned rv_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RV_W = 8;         // waves per scan block
 constexpr int RV_P = 6;         // super-steps in flight per wave
-constexpr int RV_CH = 2048;     // rows per chunk (ivf_chunk_rows) = 64 passes = 64 mask words per slot
-constexpr int RV_WORDS = RV_CH / 32;
 constexpr int RV_QT = 6;        // query tiles of an item (96 queries)
 constexpr size_t RV_LDS_MAX = 160 * 1024;
 
@@ -352,26 +351,6 @@ ivf_range_scan_h(const uint4 *__restrict__ qsplit, const float2 *__restrict__ pa
     default: RV_CASE(6) break;
     }
 #undef RV_CASE
-}
-
-// The (pair, chunk) slot of a per-slot block or wave: pair = idx / max_nch, chunk = idx % max_nch; false when the pair
-// probes nothing on this shard or the chunk lies past its list's end.
-__device__ __forceinline__ bool rv_slot(int64_t idx, int max_nch, int64_t npairs, const int64_t *__restrict__ probes,
-                                        const int64_t *__restrict__ list_off, const int *__restrict__ list_len, int nlist,
-                                        const int *__restrict__ slot_off, int64_t &pair, int &slot, int64_t &r0,
-                                        int64_t &r1) {
-    pair = idx / max_nch;
-    const int chunk = (int)(idx - pair * max_nch);
-    if (pair >= npairs) return false;
-    const int64_t l = probes[pair];
-    if (l < 0 || l >= nlist) return false;
-    const int64_t len = list_len[l];
-    if ((int64_t)chunk * RV_CH >= len) return false;
-    slot = slot_off[pair] + chunk;
-    r0 = list_off[l] + (int64_t)chunk * RV_CH;
-    r1 = list_off[l] + len;
-    if (r1 > r0 + RV_CH) r1 = r0 + RV_CH;
-    return true;
 }
 
 // The direct form: one block of 4 waves per slot, the same mask words and count as the image scan.

@@ -7,6 +7,7 @@
 
 #include <cstring>
 #include <exception>
+#include <string>
 
 using namespace hipann;
 
@@ -177,6 +178,219 @@ void sq_search_device(IvfSqIndex &ix, int nprobe, int64_t nq, const float *xq, i
             ix.probes_kept = true;
         }
     }
+}
+
+// ---- range search (ivf_sq8_range.hip): one query slice, the stages in their order on the stream ----
+// The slots' masks take 256 bytes per (query, probe, chunk) slot, a query's slots bounded by the chunk counts of its
+// nprobe longest lists (ivf_sq_query_slots); above 64 MiB of masks the batch runs in query slices with lims chained on
+// the device — IVFFlat's rule (ivf.cpp kRangeMaskBudget), restated.  The masks, counts, offsets, lims and the stage
+// events are the core shard's range scratch (rg_*), under the handle's lock.
+constexpr int64_t kSqRangeMaskBudget = (int64_t)64 << 20;
+
+struct SqRangeSlice {
+    IvfSqRangeArgs a;
+    IvfPlanView plan{};
+    int64_t slots = 0;  // the host's bound of the slice's slots
+};
+
+// a timed call's stage marks (scan | offsets | fill: begin and end each), read by hipann_debug_ivfsq_info
+void sq_range_mark(bool on, IvfShard &sh, int i, hipStream_t st) {
+    if (!on) return;
+    if (!sh.rg_ev[i]) HIPANN_CHECK(hipEventCreate(&sh.rg_ev[i]));
+    HIPANN_CHECK(hipEventRecord(sh.rg_ev[i], st));
+    if (i == 0) sh.rg_ev_fill = false;
+    if (i == 5) sh.rg_ev_fill = true;
+}
+
+// the scan serves dimensions whose query terms fit the LDS (the top-k scan's limit); the others the direct kernel
+void sq_range_mode(SqBatch &b) {
+    b.scan = ivf_sq_group(b.ix.d) >= 16;
+    b.group = (b.scan ? ivf_sq_range_group(b.ix.d) : 16) << 8;
+    b.slots = b.nq * ivf_sq_query_slots(b.sh.h_len, b.np, ivf_chunk_rows());
+    HIPANN_REQUIRE(b.slots < (int64_t)0x7fffffff, "IVF SQ8 range search: too many slots");
+}
+
+// the masks and counts of every (query, probe, chunk) slot: the threshold scan of the codes, or the direct kernel
+void sq_range_scan(SqBatch &b, SqRangeSlice &r, float radius) {
+    IvfSqIndex &ix = b.ix;
+    IvfShard &sh = b.sh;
+    r.slots = b.slots;
+    r.plan = b.plan;
+    sh.rg_mask.ensure((size_t)b.slots * 256, sh.device);
+    sh.rg_cnt.ensure(sizeof(int) * (size_t)b.slots, sh.device);
+    if (!sh.rg_stat.p) {
+        sh.rg_stat.ensure(2 * sizeof(unsigned long long), sh.device);
+        HIPANN_CHECK(hipMemsetAsync(sh.rg_stat.p, 0, 2 * sizeof(unsigned long long), b.st));
+    }
+    IvfSqRangeArgs &a = r.a;
+    a.Q = b.xq, a.nq = b.nq, a.radius = radius, a.probes = sh.coarse_i.get<int64_t>(), a.max_nch = std::max(sh.max_nch, 1);
+    a.mask = sh.rg_mask.get<unsigned>(), a.counts = sh.rg_cnt.get<int>();
+    RoctxRange rr("hipann.ivfsq.range_scan");
+    ScopedTiming t(ix.timer_main, b.st);
+    sq_range_mark(ix.timer_main.on, sh, 0, b.st);
+    if (b.scan) {
+        a.qimg = ix.qimg.p, a.par = ix.par.get<float>(), a.pair_a = ix.pair_a.get<float>();
+        a.stat = sh.rg_stat.get<unsigned long long>();
+        launch_ivf_sq_range_scan(a, b.v, b.plan, b.group,
+                                 ivf_max_items(b.nq, b.np, ix.core->nlist, sh.max_nch, sh.n, b.group), b.st);
+    } else {
+        launch_ivf_sq_range_direct(a, b.v, b.plan, b.st);
+    }
+    sq_range_mark(ix.timer_main.on, sh, 1, b.st);
+}
+
+// slot offsets, pair limits and the slice's lims (chain: continuing from lims[0], the slice before)
+void sq_range_offsets(SqBatch &b, SqRangeSlice &r, int64_t *lims_dev, bool chain) {
+    IvfShard &sh = b.sh;
+    sh.rg_soff.ensure(sizeof(int64_t) * ((size_t)r.slots + 1), sh.device);
+    sh.rg_plim.ensure(sizeof(int64_t) * ((size_t)b.nq * b.np + 1), sh.device);
+    sq_range_mark(b.ix.timer_main.on, sh, 2, b.st);
+    launch_ivf_range_offsets(r.a.counts, r.plan.slot_off, b.nq, b.np, chain, sh.rg_soff.get<int64_t>(),
+                             sh.rg_plim.get<int64_t>(), lims_dev, b.st);
+    sq_range_mark(b.ix.timer_main.on, sh, 3, b.st);
+}
+
+// (distance, id) of the slice's admitted rows at their offsets in D / I
+void sq_range_fill(IvfSqIndex &ix, const SqRangeSlice &r, float *D, int64_t *I, hipStream_t st) {
+    IvfShard &sh = *ix.core->shards[0];
+    RoctxRange rr("hipann.ivfsq.range_fill");
+    sq_range_mark(ix.timer_main.on, sh, 4, st);  // (hipann_last_kernel_ms reports the threshold scan alone)
+    launch_ivf_sq_range_fill(r.a, sq_view(ix), r.plan, sh.rg_soff.get<int64_t>(), D, I, st);
+    sq_range_mark(ix.timer_main.on, sh, 5, st);
+}
+
+// Query preparation, coarse step, plan, scan and offsets of one slice: lims_dev (nq + 1, device) is written, the slice
+// is ready to fill.
+SqRangeSlice sq_range_count(IvfSqIndex &ix, int np, int64_t nq, const float *xq, float radius, int64_t *lims_dev,
+                            bool chain, hipStream_t st) {
+    IvfShard &sh = *ix.core->shards[0];
+    SqBatch b{ix, sh, sq_view(ix), nq, xq, 1, np, nullptr, nullptr, st};
+    SqRangeSlice r;
+    sq_range_mode(b);
+    sq_prepare_queries(b);
+    sq_coarse_and_plan(b);
+    sq_range_scan(b, r, radius);
+    sq_range_offsets(b, r, lims_dev, chain);
+    return r;
+}
+
+int64_t sq_range_slice_queries(const IvfSqIndex &ix, int np) {
+    const int64_t qslots = ivf_sq_query_slots(ix.core->shards[0]->h_len, np, ivf_chunk_rows());
+    return std::max<int64_t>(1, (ix.range_mask_budget > 0 ? ix.range_mask_budget : kSqRangeMaskBudget) / (qslots * 256));
+}
+
+// a sliced batch's probe lists, kept for hipann_ivfsq_last_probes (the coarse step's buffer holds one slice's)
+void sq_range_keep_probes(IvfSqIndex &ix, int64_t q0, int64_t nqs, int np, hipStream_t st) {
+    HIPANN_CHECK(hipMemcpyAsync(ix.probes.get<int64_t>() + q0 * np, ix.core->shards[0]->coarse_i.p,
+                                sizeof(int64_t) * (size_t)nqs * np, hipMemcpyDeviceToDevice, st));
+    ix.probes_kept = true;
+}
+
+// Host variant.  Per query slice: count, one synchronisation for the slice's lims, fill, the rows back.
+int sq_range_host(IvfSqIndex &ix, int nprobe, int64_t nq, const float *xq, float radius, int64_t *lims, float **D,
+                  int64_t **I) {
+    HIPANN_REQUIRE(lims && D && I, "null output");
+    HIPANN_REQUIRE(nq >= 0 && (nq == 0 || xq), "invalid arguments");
+    HIPANN_REQUIRE(radius == radius, "radius is NaN");
+    *D = nullptr, *I = nullptr;
+    std::fill(lims, lims + nq + 1, (int64_t)0);
+    IvfShard &sh = *ix.core->shards[0];
+    DeviceGuard g(sh.device);
+    const int np = ivf_sq_call_nprobe(nprobe, ix.core->nprobe, ix.core->nlist);
+    ix.last_nq = sh.live == 0 ? 0 : nq;
+    ix.last_np = np;
+    ix.probes_kept = false;
+    if (nq == 0 || sh.live == 0) return 0;
+    const hipStream_t st = sh.stream;
+    const size_t qbytes = (size_t)nq * ix.d * sizeof(float);
+    ix.h_q.ensure(qbytes);
+    std::memcpy(ix.h_q.p, xq, qbytes);
+    ix.q.ensure(qbytes, sh.device);
+    const int64_t qs = sq_range_slice_queries(ix, np);
+    if (qs < nq) ix.probes.ensure(sizeof(int64_t) * (size_t)nq * np, sh.device);
+    FenceScope fs(sh.fence, st, sh.device);
+    HIPANN_CHECK(hipMemcpyAsync(ix.q.p, ix.h_q.p, qbytes, hipMemcpyHostToDevice, st));
+    float *od = nullptr;
+    int64_t *oi = nullptr;
+    int64_t run = 0;
+    try {
+        for (int64_t q0 = 0; q0 < nq; q0 += qs) {
+            const int64_t nqs = std::min(qs, nq - q0);
+            const size_t lbytes = sizeof(int64_t) * (size_t)(nqs + 1);
+            sh.rg_lims.ensure(lbytes, sh.device);
+            sh.h_rg.ensure(lbytes);
+            const SqRangeSlice r = sq_range_count(ix, np, nqs, ix.q.get<float>() + q0 * ix.d, radius,
+                                                  sh.rg_lims.get<int64_t>(), false, st);
+            HIPANN_CHECK(hipMemcpyAsync(sh.h_rg.p, sh.rg_lims.p, lbytes, hipMemcpyDeviceToHost, st));
+            if (qs < nq) sq_range_keep_probes(ix, q0, nqs, np, st);
+            HIPANN_CHECK(hipStreamSynchronize(st));
+            const int64_t *hl = sh.h_rg.get<int64_t>();
+            const int64_t total = hl[nqs];
+            for (int64_t i = 0; i < nqs; ++i) lims[q0 + i] = run + hl[i];
+            if (total == 0) continue;
+            float *nd = static_cast<float *>(std::realloc(od, sizeof(float) * (size_t)(run + total)));
+            if (nd) od = nd;
+            int64_t *ni = static_cast<int64_t *>(std::realloc(oi, sizeof(int64_t) * (size_t)(run + total)));
+            if (ni) oi = ni;
+            HIPANN_REQUIRE(nd && ni, "range search: out of host memory");
+            sh.rg_d.ensure(sizeof(float) * (size_t)total, sh.device);
+            sh.rg_i.ensure(sizeof(int64_t) * (size_t)total, sh.device);
+            sq_range_fill(ix, r, sh.rg_d.get<float>(), sh.rg_i.get<int64_t>(), st);
+            HIPANN_CHECK(hipMemcpyAsync(od + run, sh.rg_d.p, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, st));
+            HIPANN_CHECK(hipMemcpyAsync(oi + run, sh.rg_i.p, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost, st));
+            HIPANN_CHECK(hipStreamSynchronize(st));
+            run += total;
+        }
+        lims[nq] = run;
+    } catch (...) {
+        std::free(od);
+        std::free(oi);
+        throw;
+    }
+    *D = od, *I = oi;
+    return 0;
+}
+
+// Device variant.  One slice: count, read the total back, fill.  Several: every slice counts first (lims chained from
+// slice to slice), the total is read back, and only a result that fits runs the slices again, each with its fill.
+int sq_range_device(IvfSqIndex &ix, int nprobe, int64_t nq, const float *xq, float radius, int64_t *lims_dev, float *D,
+                    int64_t *I, int64_t cap, hipStream_t st) {
+    IvfShard &sh = *ix.core->shards[0];
+    DeviceGuard g(sh.device);
+    FenceScope fs(sh.fence, st, sh.device);
+    const int np = ivf_sq_call_nprobe(nprobe, ix.core->nprobe, ix.core->nlist);
+    ix.last_nq = sh.live == 0 ? 0 : nq;
+    ix.last_np = np;
+    ix.probes_kept = false;
+    if (nq == 0 || sh.live == 0) {
+        HIPANN_CHECK(hipMemsetAsync(lims_dev, 0, sizeof(int64_t) * (size_t)(nq + 1), st));
+        return 0;
+    }
+    const int64_t qs = sq_range_slice_queries(ix, np);
+    const bool sliced = qs < nq;
+    if (sliced) ix.probes.ensure(sizeof(int64_t) * (size_t)nq * np, sh.device);
+    SqRangeSlice one;
+    for (int64_t q0 = 0; q0 < nq; q0 += qs) {
+        const int64_t nqs = std::min(qs, nq - q0);
+        one = sq_range_count(ix, np, nqs, xq + q0 * ix.d, radius, lims_dev + q0, q0 > 0, st);
+        if (sliced) sq_range_keep_probes(ix, q0, nqs, np, st);
+    }
+    sh.h_rg.ensure(sizeof(int64_t));
+    HIPANN_CHECK(hipMemcpyAsync(sh.h_rg.p, lims_dev + nq, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPANN_CHECK(hipStreamSynchronize(st));  // the one readback: the total, against cap
+    const int64_t total = *sh.h_rg.get<int64_t>();
+    if (total > cap) return 1;
+    if (total == 0) return 0;
+    if (!sliced) {
+        sq_range_fill(ix, one, D, I, st);
+        return 0;
+    }
+    for (int64_t q0 = 0; q0 < nq; q0 += qs) {
+        const int64_t nqs = std::min(qs, nq - q0);
+        const SqRangeSlice r = sq_range_count(ix, np, nqs, xq + q0 * ix.d, radius, lims_dev + q0, q0 > 0, st);
+        sq_range_fill(ix, r, D, I, st);
+    }
+    return 0;
 }
 
 // ---- train: the assignment in blocks of 65536 rows (by_residual), then the column min / max ----
@@ -552,6 +766,31 @@ int hipann_ivfsq_search(void *h, int nprobe, int64_t nq, const float *xq, int64_
     });
 }
 
+int hipann_ivfsq_range_search(void *h, int nprobe, int64_t nq, const float *xq, float radius, int64_t *lims, float **D,
+                              int64_t **I, char *eb, int el) {
+    return guard<int>(eb, el, -1, [&]() -> int {
+        IvfSqIndex *ix = as_sq(h);
+        HIPANN_REQUIRE(ix, "not an IVF SQ8 index");
+        std::lock_guard<std::mutex> lk(ix->mu);
+        return sq_range_host(*ix, nprobe, nq, xq, radius, lims, D, I);
+    });
+}
+
+int hipann_ivfsq_range_search_device(void *h, int nprobe, int64_t nq, const float *xq_dev, float radius,
+                                     int64_t *lims_dev, float *D_dev, int64_t *I_dev, int64_t cap, void *stream, char *eb,
+                                     int el) {
+    return guard<int>(eb, el, -1, [&]() -> int {
+        IvfSqIndex *ix = as_sq(h);
+        HIPANN_REQUIRE(ix, "not an IVF SQ8 index");
+        std::lock_guard<std::mutex> lk(ix->mu);
+        HIPANN_REQUIRE(nq >= 0 && lims_dev && (nq == 0 || xq_dev) && cap >= 0 && (cap == 0 || (D_dev && I_dev)),
+                       "invalid arguments");
+        HIPANN_REQUIRE(radius == radius, "radius is NaN");
+        return sq_range_device(*ix, nprobe, nq, xq_dev, radius, lims_dev, D_dev, I_dev, cap,
+                               static_cast<hipStream_t>(stream));
+    });
+}
+
 int hipann_ivfsq_last_probes(void *h, int64_t *probes, int64_t cap, char *eb, int el) {
     return guard<int>(eb, el, -1, [&]() -> int {
         IvfSqIndex *ix = as_sq(h);
@@ -619,8 +858,11 @@ int64_t hipann_ivfsq_rerank_fallbacks(void *h) {
     }
 }
 
-// measurement hook (tools/ivf_sq8_bench.py): "rechecked" = candidates the rerank has recomputed in the direct form since
-// creation; "cmax" = the handle's current bound of max ‖c‖ (tests: it follows an add); 0 on success
+// measurement hook (tools/ivf_sq8_bench.py, tools/ivf_sq8_range_bench.py): "rechecked" = candidates the rerank has
+// recomputed in the direct form since creation; "cmax" = the handle's current bound of max ‖c‖ (tests: it follows an
+// add); "range_survivors" / "range_admitted" and "range_scan_ms" / "range_offsets_ms" / "range_fill_ms": the range
+// scan's filter counters and the last timed range call's stages; "range_mask_budget" is an input (tests: the query slices
+// of a range call at a small size); 0 on success
 int hipann_debug_ivfsq_info(void *h, const char *name, double *out) {
     try {
         IvfSqIndex *ix = as_sq(h);
@@ -630,8 +872,38 @@ int hipann_debug_ivfsq_info(void *h, const char *name, double *out) {
             *out = (double)ix->cmax;
             return 0;
         }
-        if (std::strcmp(name, "rechecked") != 0) return -1;
-        DeviceGuard g(ix->core->shards[0]->device);
+        IvfShard &sh = *ix->core->shards[0];
+        const std::string s(name);
+        if (s == "range_mask_budget") {  // in: the mask bytes above which a range call runs in query slices (0: 64 MiB)
+            HIPANN_REQUIRE(*out >= 0.0, "negative budget");
+            ix->range_mask_budget = (int64_t)*out;
+            return 0;
+        }
+        if (s == "range_survivors" || s == "range_admitted") {
+            // the range scan's filter since creation: rows sent to the recheck, rows the recheck admitted
+            unsigned long long v[2] = {0, 0};
+            if (sh.rg_stat.p) {
+                DeviceGuard g(sh.device);
+                HIPANN_CHECK(hipDeviceSynchronize());
+                HIPANN_CHECK(hipMemcpy(v, sh.rg_stat.p, sizeof(v), hipMemcpyDeviceToHost));
+            }
+            *out = (double)v[s == "range_admitted" ? 1 : 0];
+            return 0;
+        }
+        if (s == "range_scan_ms" || s == "range_offsets_ms" || s == "range_fill_ms") {
+            // the stages of the last range call made with timing on (its last slice); 0 for a stage that did not run
+            const int i = s == "range_scan_ms" ? 0 : s == "range_offsets_ms" ? 2 : 4;
+            float ms = 0.f;
+            if (sh.rg_ev[i] && sh.rg_ev[i + 1] && (i < 4 || sh.rg_ev_fill)) {
+                DeviceGuard g(sh.device);
+                HIPANN_CHECK(hipEventSynchronize(sh.rg_ev[i + 1]));
+                HIPANN_CHECK(hipEventElapsedTime(&ms, sh.rg_ev[i], sh.rg_ev[i + 1]));
+            }
+            *out = ms;
+            return 0;
+        }
+        if (s != "rechecked") return -1;
+        DeviceGuard g(sh.device);
         HIPANN_CHECK(hipDeviceSynchronize());
         unsigned long long v = 0;
         HIPANN_CHECK(hipMemcpy(&v, ix->fb_total.get<unsigned long long>() + 2, sizeof(v), hipMemcpyDeviceToHost));

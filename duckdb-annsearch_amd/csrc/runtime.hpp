@@ -531,6 +531,7 @@ struct IvfSqIndex : IndexBase {
     DevBuf qimg, par, pair_a, cand_d, cand_i, flagged, dl_d, dl_i, q, out_d, out_i, probes, fb_total;
     HostBuf h_q, h_d, h_i;
     bool probes_kept = false;    // the last call ran in query slices: its probe lists are in `probes`
+    int64_t range_mask_budget = 0;  // test hook: a range call's mask bytes per query slice (0: 64 MiB)
     int64_t last_nq = 0;
     int last_np = 0;
     // an add's staging (hipann_ivfsq_add): the host rows, [assignment | non-finite flag], the assignment's distances
@@ -850,6 +851,29 @@ void launch_ivf_sq_direct(const IvfSqView &v, const IvfPlanView &plan, const int
                           hipStream_t st);
 void launch_ivf_sq_merge(const IvfSqView &v, const IvfPlanView &plan, int64_t nq, int k, const int *nflag,
                          const int *flagged, const float *dl_d, const void *dl_i, float *D, int64_t *I, hipStream_t st);
+// ivf_sq8_range.hip — IVF SQ8 range search.  One query slice after the query preparation, the coarse step and the
+// plan: the threshold scan of the codes (or, where the query terms do not fit the LDS, the direct kernel) leaves
+// ivf_range.hip's 64-word admitted-row mask and count per (query, probe, chunk) slot; launch_ivf_range_offsets places
+// the slots; the fill writes (distance, id) at soff[slot] + rank.
+struct IvfSqRangeArgs {
+    const float *Q = nullptr;  // the slice's queries (fp32) and their count
+    int64_t nq = 0;
+    float radius = 0.f;
+    const int64_t *probes = nullptr;  // nq × nprobe probe lists (the direct kernel and the fill find their slots by pair)
+    int max_nch = 1;
+    // the scan: the queries' fp16 terms, (1/t, E, 2E, ‖q‖²) per query, A | P per pair (ivf_sq_query_prep, ivf_sq_pair_terms)
+    const void *qimg = nullptr;
+    const float *par = nullptr, *pair_a = nullptr;
+    unsigned *mask = nullptr;
+    int *counts = nullptr;
+    unsigned long long *stat = nullptr;  // (optional) += the filter's survivors, += the rows the recheck admitted
+};
+int ivf_sq_range_group(int d);  // queries per range scan item (a multiple of 16, at most 64)
+void launch_ivf_sq_range_scan(const IvfSqRangeArgs &a, const IvfSqView &v, const IvfPlanView &plan, int group,
+                              int64_t max_items, hipStream_t st);
+void launch_ivf_sq_range_direct(const IvfSqRangeArgs &a, const IvfSqView &v, const IvfPlanView &plan, hipStream_t st);
+void launch_ivf_sq_range_fill(const IvfSqRangeArgs &a, const IvfSqView &v, const IvfPlanView &plan, const int64_t *soff,
+                              float *D, int64_t *I, hipStream_t st);
 // bounded passes of the 64-dim K-step kernel (flat_b16k64.hip): candidate buffers, their bound and select
 // (k64_on: the caller's HIPANN_B16_K64 switch)
 bool flat_bf16_resumable(int64_t nq, int d, int k, bool k64_on);

@@ -135,6 +135,8 @@ def lib() -> C.CDLL:
             "hipann_ivfsq_create": ([i32, i32, i32, i32, i32, f, f, f, i64p, i64p, C.POINTER(C.c_uint8), i32, cp, i32], vp),
             "hipann_ivfsq_search": ([vp, i32, i64, f, i64, f, i64p, cp, i32], i32),
             "hipann_ivfsq_search_device": ([vp, i32, i64, vp, i64, vp, vp, vp, cp, i32], i32),
+            "hipann_ivfsq_range_search": ([vp, i32, i64, f, C.c_float, i64p, C.POINTER(f), C.POINTER(i64p), cp, i32], i32),
+            "hipann_ivfsq_range_search_device": ([vp, i32, i64, vp, C.c_float, vp, vp, vp, i64, vp, cp, i32], i32),
             "hipann_ivfsq_last_probes": ([vp, i64p, i64, cp, i32], i32),
             "hipann_ivfsq_export": ([vp, f, f, f, i64p, i64p, C.POINTER(C.c_uint8), cp, i32], i32),
             "hipann_ivfsq_rerank_fallbacks": ([vp], i64),
@@ -703,6 +705,37 @@ class HipIndexIVFSQ8(_Handle):
         _check(lib().hipann_ivfsq_search_device(self._h, 0 if nprobe is None else int(nprobe), nq, C.c_void_p(xq_ptr),
                                                 k, C.c_void_p(d_ptr), C.c_void_p(i_ptr), C.c_void_p(stream or None),
                                                 eb, 1024), eb)
+
+    def range_search(self, x, radius: float, nprobe: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """faiss::IndexIVF::range_search with the SQ8 scanner: ``(lims, D, I)``; query q's rows are
+        ``[lims[q], lims[q+1])`` of D / I — every row of its probed lists whose decoded distance is < radius (L2) or
+        > radius (IP), in probe order, then list order.  ``nprobe``: the per-call value (None: the index's)."""
+        x = _f32_2d(x, self.d)
+        n = x.shape[0]
+        lims = np.zeros(n + 1, np.int64)
+        dp, ip = C.POINTER(C.c_float)(), C.POINTER(C.c_int64)()
+        eb = _err()
+        _check(lib().hipann_ivfsq_range_search(self._h, 0 if nprobe is None else int(nprobe), n, _ptr(x, C.c_float),
+                                               radius, _ptr(lims, C.c_int64), C.byref(dp), C.byref(ip), eb, 1024), eb)
+        total = int(lims[n])
+        try:
+            D = np.ctypeslib.as_array(dp, (total,)).copy() if total else np.empty(0, np.float32)
+            I = np.ctypeslib.as_array(ip, (total,)).copy() if total else np.empty(0, np.int64)
+        finally:
+            lib().hipann_range_free(dp, ip)
+        return lims, D, I
+
+    def range_search_device(self, nq: int, xq_ptr: int, radius: float, lims_ptr: int, d_ptr: int, i_ptr: int, cap: int,
+                            nprobe: Optional[int] = None, stream: int = 0) -> bool:
+        """hipann_ivfsq_range_search_device: ``lims_ptr`` (nq + 1 int64, device) is always written; ``d_ptr`` /
+        ``i_ptr`` (``cap`` entries) only when the result fits.  True when filled, False when ``lims[nq] > cap``."""
+        eb = _err()
+        rc = lib().hipann_ivfsq_range_search_device(self._h, 0 if nprobe is None else int(nprobe), nq,
+                                                    C.c_void_p(xq_ptr), radius, C.c_void_p(lims_ptr),
+                                                    C.c_void_p(d_ptr or None), C.c_void_p(i_ptr or None), cap,
+                                                    C.c_void_p(stream or None), eb, 1024)
+        _check(min(rc, 0), eb)
+        return rc == 0
 
     def last_probes(self, nq: int, nprobe: Optional[int] = None) -> np.ndarray:
         """The last call's probe lists (``nprobe``: that call's per-call value, when it had one)."""

@@ -436,7 +436,26 @@ int64_t hipann_ivf_rerank_fallbacks(void *index);
  * device (no host readback: the _device call stays asynchronous).
  * The handle is single-device (per-handle mutex, one stream plus scratch, err_buf as everywhere) and serves
  * hipann_ntotal / _dim / _metric / _memory_bytes / _free / _set_kernel_timing / _last_kernel_ms (which = 0: the code
- * scan; after hipann_ivfsq_remove_ids: its kernel); every other entry point rejects it with −1.  There is no range search.
+ * scan; after hipann_ivfsq_remove_ids: its kernel; after a range search: its threshold scan); every other entry point
+ * rejects it with −1 — hipann_ivf_range_search* and hipann_flat_range_search* among them.
+ * Range search (hipann_ivfsq_range_search): faiss::IndexIVF::range_search with the 8-bit scalar-quantizer scanner.
+ * The probe lists are those of hipann_ivfsq_search (nprobe <= 0: the index's; above nlist: nlist).  Per query, every
+ * live row of every probed list whose distance as defined above — the same device function, the same bits as every
+ * top-k path — passes the strict comparison, L2: dist < radius, IP: dist > radius, in probe order, then position in the
+ * list (hipann_ivfsq_export's order); labels are the lists' ids.  lims: nq + 1 int64 (host); *D / *I: host buffers the
+ * library allocates (NULL when nothing qualifies), released with hipann_range_free.  Any number of rows may qualify
+ * (HIPANN_MAX_K does not apply); an empty list contributes nothing; nq == 0 writes lims[0] = 0; an empty index returns
+ * all-zero lims; a NaN radius is an error; ±inf is legal; a query holding a NaN returns no rows.  The same call returns
+ * the same bits in the same order on every run.  The lists are scanned once: a threshold scan of the codes on the
+ * matrix cores whose filter — the top-k scan's key against radius plus the certificate's per-query bound E(q) — can
+ * only add rows, each survivor rechecked in the direct form; d above 4352 takes a direct-form kernel.  The scan leaves
+ * an admitted-row bitmask and a count per (query, probe, 2048-row chunk); a device prefix sum places the slots and a
+ * fill pass writes the rows.  The bitmasks take 256 bytes per slot (bounded per query by the chunks of its nprobe
+ * longest lists); above 64 MiB the batch runs in query slices.  hipann_ivfsq_last_probes reports this call's probe
+ * lists.  The _device form: lims_dev (nq + 1 int64) is always written; D_dev / I_dev (cap entries) are touched only
+ * when lims[nq] <= cap; it returns 0, 1 when the result did not fit (read lims[nq] and call again), or −1; asynchronous
+ * on `stream` except for the one readback of the total (a batch that runs in query slices counts every slice first and
+ * scans a second time only when the result fits).  Every handle that is not an IVF SQ8 handle gets −1.
  * Train (hipann_ivfsq_train): FAISS's ScalarQuantizer::train for QT_8bit with the default range statistic (min/max,
  * argument 0) over the n >= 1 rows given (the caller samples): e = x − g_assign when by_residual (one fp32 subtraction
  * per entry), else e = x; vmin_i = min e_i, vdiff_i = fl32(max e_i − min e_i).  The assignment is hipann_ivf_add's:
@@ -490,6 +509,11 @@ int hipann_ivfsq_search(void *index, int nprobe, int64_t nq, const float *xq, in
                         float *D, int64_t *I, char *err_buf, int err_len);
 int hipann_ivfsq_search_device(void *index, int nprobe, int64_t nq, const float *xq_dev, int64_t k,
                                float *D_dev, int64_t *I_dev, void *stream, char *err_buf, int err_len);
+int hipann_ivfsq_range_search(void *index, int nprobe, int64_t nq, const float *xq, float radius,
+                              int64_t *lims, float **D, int64_t **I, char *err_buf, int err_len);
+int hipann_ivfsq_range_search_device(void *index, int nprobe, int64_t nq, const float *xq_dev, float radius,
+                                     int64_t *lims_dev, float *D_dev, int64_t *I_dev, int64_t cap, void *stream,
+                                     char *err_buf, int err_len);
 /* The last call's probe lists (nq × min(nprobe, nlist) int64). */
 int hipann_ivfsq_last_probes(void *index, int64_t *probes, int64_t cap, char *err_buf, int err_len);
 /* GpuToCpu: the index as dense CSR (offsets = the cumulative live lengths, ids and codes without slack rows; the
