@@ -65,20 +65,26 @@ struct SqBatch {
     int64_t *const I;
     const hipStream_t st;
     bool scan = false;  // the code scan + rerank (else the direct kernel for every query)
+    int kf = 0;         // the scan's sub-list depth (kSqKeep | kSqDeep) and its gate classes, ceil(k / kf)
+    int nclass = 1;
     int group = 0;
     IvfPlanView plan{};
     int64_t slots = 0;  // the host's bound of the slice's slots
 };
 
-// the scan serves k up to its filter depth and dimensions whose query terms fit the LDS
+// the scan serves k <= 16 at depth 16 and k <= 64 at depth 32, at dimensions whose query terms fit the LDS beside
+// the lists of that depth; everything else the direct kernel
 void sq_pick_mode(SqBatch &b) {
-    const int wide = ivf_sq_group(b.ix.d);
-    b.scan = b.k <= kSqKeep && wide >= 16;
+    const int kf = b.k <= kSqKeep ? kSqKeep : b.k <= kSqDirectK ? kSqDeep : 0;
+    const int wide = kf ? ivf_sq_group(b.ix.d, kf) : 0;
+    b.scan = wide >= 16;
+    b.kf = b.scan ? kf : 0;
+    b.nclass = b.scan ? (b.k + kf - 1) / kf : 1;
     b.group = b.scan ? wide << 8 : 16 << 8;
     b.slots = b.nq * ivf_sq_query_slots(b.sh.h_len, b.np, ivf_chunk_rows());
-    HIPANN_REQUIRE(b.slots < (int64_t)0x7fffffff / (kSqWaves * kSqKeep), "IVF SQ8: too many slots");
+    HIPANN_REQUIRE(b.slots < (int64_t)0x7fffffff / (kSqWaves * (b.scan ? kf : kSqKeep)), "IVF SQ8: too many slots");
     b.ix.last_form = b.scan ? 1 : 0;
-    b.ix.last_kfilt = b.scan ? kSqKeep : 0;
+    b.ix.last_kfilt = b.kf;
     b.ix.last_sublists = b.scan ? kSqWaves : 0;
 }
 
@@ -89,7 +95,9 @@ void sq_prepare_queries(SqBatch &b) {
     ix.qimg.ensure((size_t)b.nq * ix.nstep * 32 * 2, b.sh.device);
     ix.par.ensure((size_t)b.nq * 16, b.sh.device);
     const float wbase = (float)((ix.gmax + ix.mnorm) * 1.0001);
-    launch_ivf_sq_query_prep(b.xq, b.nq, b.v, ix.cmax, wbase, ix.qimg.p, ix.par.get<float>(), b.st);
+    if (b.nclass == 2) ix.qbound2.ensure(sizeof(unsigned) * (size_t)b.nq, b.sh.device);
+    launch_ivf_sq_query_prep(b.xq, b.nq, b.v, ix.cmax, wbase, ix.qimg.p, ix.par.get<float>(),
+                             b.nclass == 2 ? ix.qbound2.get<unsigned>() : nullptr, b.st);
 }
 
 // the IVFFlat coarse step and plan, then A(q, l) (IP: q·(g + b)) per pair
@@ -100,18 +108,18 @@ void sq_coarse_and_plan(SqBatch &b) {
     launch_ivf_sq_pair_terms(b.xq, b.nq, b.np, b.sh.coarse_i.get<int64_t>(), b.v, b.ix.pair_a.get<float>(), b.st);
 }
 
-// the code scan over the plan's items: kSqWaves sub-lists of kSqKeep (key, row) per slot
+// the code scan over the plan's items: kSqWaves sub-lists of b.kf (key, row) per slot
 void sq_scan(SqBatch &b) {
     IvfSqIndex &ix = b.ix;
-    const size_t entries = (size_t)b.slots * kSqWaves * kSqKeep;
+    const size_t entries = (size_t)b.slots * kSqWaves * b.kf;
     ix.cand_d.ensure(entries * sizeof(float), b.sh.device);
     ix.cand_i.ensure(entries * sizeof(int), b.sh.device);
     RoctxRange rr("hipann.ivfsq.scan");
     ScopedTiming t(ix.timer_main, b.st);
-    launch_ivf_sq_scan(b.v, b.plan, b.group,
+    launch_ivf_sq_scan(b.v, b.plan, b.group, b.kf, b.nclass,
                        ivf_max_items(b.nq, b.np, ix.core->nlist, b.sh.max_nch, b.sh.n, b.group), ix.qimg.p,
-                       ix.par.get<float>(), ix.pair_a.get<float>(), b.sh.qbound.get<unsigned>(), ix.cand_d.get<float>(),
-                       ix.cand_i.get<int>(), b.st);
+                       ix.par.get<float>(), ix.pair_a.get<float>(), b.sh.qbound.get<unsigned>(),
+                       ix.qbound2.get<unsigned>(), ix.cand_d.get<float>(), ix.cand_i.get<int>(), b.st);
 }
 
 // the candidates' direct-form distances and the certificate; flagged queries into sh.nflag / ix.flagged
@@ -119,7 +127,7 @@ void sq_rerank(SqBatch &b) {
     IvfSqIndex &ix = b.ix;
     ix.flagged.ensure(sizeof(int) * (size_t)b.nq, b.sh.device);
     ScopedTiming t(ix.timer_merge, b.st);
-    launch_ivf_sq_rerank(b.v, b.plan, b.sh.coarse_i.get<int64_t>(), b.xq, b.nq, b.k, ix.par.get<float>(),
+    launch_ivf_sq_rerank(b.v, b.plan, b.sh.coarse_i.get<int64_t>(), b.xq, b.nq, b.k, b.kf, b.nclass, ix.par.get<float>(),
                          ix.cand_d.get<float>(), ix.cand_i.get<int>(), b.sh.nflag.get<int>(), ix.flagged.get<int>(),
                          ix.fb_total.get<unsigned long long>(), b.D, b.I, b.st);
 }
@@ -155,7 +163,9 @@ void sq_search_device(IvfSqIndex &ix, int nprobe, int64_t nq, const float *xq, i
     ix.last_np = np;
     ix.probes_kept = false;
     if (nq <= 0) return;
+    const bool deep = k > kSqKeep && k <= kSqDirectK && ivf_sq_group(ix.d, kSqDeep) >= 16;
     const int64_t slot_bytes = k <= kSqKeep        ? (int64_t)(kSqWaves * kSqKeep * 8 + kSqDirectK * 12)
+                               : deep            ? (int64_t)(kSqWaves * kSqDeep * 8 + kSqDirectK * 12)
                                : k <= kSqDirectK ? (int64_t)kSqDirectK * 12
                                                  : (int64_t)ivf_chunk_rows() * 8;
     const int64_t step = ivf_sq_slice_queries(nq, ivf_sq_query_slots(sh.h_len, np, ivf_chunk_rows()), slot_bytes,
@@ -204,7 +214,7 @@ void sq_range_mark(bool on, IvfShard &sh, int i, hipStream_t st) {
 
 // the scan serves dimensions whose query terms fit the LDS (the top-k scan's limit); the others the direct kernel
 void sq_range_mode(SqBatch &b) {
-    b.scan = ivf_sq_group(b.ix.d) >= 16;
+    b.scan = ivf_sq_group(b.ix.d, kSqKeep) >= 16;
     b.group = (b.scan ? ivf_sq_range_group(b.ix.d) : 16) << 8;
     b.slots = b.nq * ivf_sq_query_slots(b.sh.h_len, b.np, ivf_chunk_rows());
     HIPANN_REQUIRE(b.slots < (int64_t)0x7fffffff, "IVF SQ8 range search: too many slots");
@@ -859,7 +869,8 @@ int64_t hipann_ivfsq_rerank_fallbacks(void *h) {
 }
 
 // measurement hook (tools/ivf_sq8_bench.py, tools/ivf_sq8_range_bench.py): "rechecked" = candidates the rerank has
-// recomputed in the direct form since creation; "cmax" = the handle's current bound of max ‖c‖ (tests: it follows an
+// recomputed in the direct form since creation; "filter_depth" = the sub-list depth of the last search call's scan
+// (16, 32, or 0 for the direct kernel); "cmax" = the handle's current bound of max ‖c‖ (tests: it follows an
 // add); "range_survivors" / "range_admitted" and "range_scan_ms" / "range_offsets_ms" / "range_fill_ms": the range
 // scan's filter counters and the last timed range call's stages; "range_mask_budget" is an input (tests: the query slices
 // of a range call at a small size); 0 on success
@@ -870,6 +881,10 @@ int hipann_debug_ivfsq_info(void *h, const char *name, double *out) {
         std::lock_guard<std::mutex> lk(ix->mu);
         if (std::strcmp(name, "cmax") == 0) {
             *out = (double)ix->cmax;
+            return 0;
+        }
+        if (std::strcmp(name, "filter_depth") == 0) {
+            *out = (double)ix->last_kfilt;
             return 0;
         }
         IvfShard &sh = *ix->core->shards[0];

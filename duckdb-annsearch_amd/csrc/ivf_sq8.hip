@@ -51,8 +51,26 @@
 // the smallest keys have dist <= τ + E: no dropped row is among the k best, and every kept row that is has key <=
 // τ + 2E and is rechecked; (3) the comparisons are written so that a NaN key is never admitted and a NaN or
 // non-finite E flags the query; (4) rows past the list's length and queries past the item's count are masked.
-// Flagged queries, k above 16 and dimensions whose query terms do not fit the LDS take ivf_sq_direct: sq_row_dist
-// over all rows of the probed lists, one wave per slot, with no host readback in between.
+//
+// The deep variant, 17 <= k <= 64.  sq_item / ivf_sq_scan / ivf_sq_rerank are templates on the depth KF of the wave
+// lists: KF = 16 is the kernel above, KF = 32 keeps a (wave, query) list in lanes 0..31 (insertion is still one
+// ballot, one popcount, one shuffle), a slot holds 8 sub-lists of 32, and the LDS per query is sq_stride·4 + 16 +
+// 8·KF·8 bytes (d = 768: 32 queries per item instead of 48; d <= 128: 64 still; above d = 3840 not even 16 fit).
+// One published 32nd key no longer bounds the k-th key when k > 32, so the wave lists are split into
+// J = ceil(k / KF) classes, class = wave % J, with one published word per (query, class): the shard's qbound for
+// class 0, qbound2 (the handle's own, reset to +inf by ivf_sq_query_prep) for class 1.  A full list min's its KF-th
+// key into its class's word; the gate is B_q = the max of the J words, +inf until every class has published.
+// Obligation (2a), amended: the list that attains a class's word held KF rows with key <= that word at that time,
+// and holds them or better ones at the end.  Lists of different classes are different lists, and their rows are
+// distinct — a row belongs to one pass, a pass to one wave, and a slot to exactly one item.  So at least
+// J·KF >= k distinct rows have key <= B_q at the end, hence τ <= B_q, and a row dropped at the gate has key >
+// τ + 2E.  (2b) with 16 replaced by KF: a row leaves a full wave list only with key >= that list's final KF-th key,
+// and the rerank flags the query unless every full sub-list's KF-th key is > τ + 2E.  (3) and (4) are unchanged.  The
+// rerank stays one wave per query: WaveList<1> holds 64 entries, so τ and the result list serve k <= 64.
+//
+// Flagged queries, k above 64 and dimensions whose query terms do not fit the LDS (d > 4352; for 17 <= k <= 64,
+// d > 3840) take ivf_sq_direct: sq_row_dist over all rows of the probed lists, one wave per slot, with no host
+// readback in between.
 //
 // Resources (hipcc 7, gfx950, -O3): see DESIGN.md §5; no kernel here uses scratch.
 #include "runtime.hpp"
@@ -65,6 +83,7 @@ namespace hipann {
 
 constexpr int SQ_W = kSqWaves;
 constexpr int SQ_KF = kSqKeep;
+constexpr int SQ_KD = kSqDeep;  // the deep variant's depth (17 <= k <= 64)
 constexpr int SQ_CH = 2048;  // rows per chunk (ivf_chunk_rows)
 constexpr int SQ_QT = 4;     // query tiles of an item at most
 constexpr size_t SQ_LDS_MAX = 160 * 1024;
@@ -74,13 +93,13 @@ int ivf_sq_nstep(int d) {
     const int raw = (d + 31) / 32, p = raw <= 4 ? 4 : 8;
     return (raw + p - 1) / p * p;
 }
-static size_t sq_lds_bytes(int nstep, int nq) {
-    return (size_t)nq * ((size_t)sq_stride(nstep) * 4 + 16 + (size_t)SQ_W * SQ_KF * 8);
+static size_t sq_lds_bytes(int nstep, int nq, int kf) {
+    return (size_t)nq * ((size_t)sq_stride(nstep) * 4 + 16 + (size_t)SQ_W * kf * 8);
 }
-int ivf_sq_group(int d) {
+int ivf_sq_group(int d, int kf) {
     const int nstep = ivf_sq_nstep(d);
     int qt = SQ_QT;
-    while (qt > 0 && sq_lds_bytes(nstep, 16 * qt) > SQ_LDS_MAX) --qt;
+    while (qt > 0 && sq_lds_bytes(nstep, 16 * qt, kf) > SQ_LDS_MAX) --qt;
     return 16 * qt;
 }
 
@@ -170,10 +189,11 @@ ivf_sq_row_terms(const unsigned char *__restrict__ codes, int64_t n, int d, cons
 template <bool IP>
 __global__ void __launch_bounds__(256)
 ivf_sq_query_prep(const float *__restrict__ Q, int64_t nq, int d, int nstep, const float *__restrict__ sb, float cmax,
-                  float wbase, _Float16 *__restrict__ qimg, float4 *__restrict__ par) {
+                  float wbase, _Float16 *__restrict__ qimg, float4 *__restrict__ par, unsigned *__restrict__ qbound2) {
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= nq) return;
     const int lane = threadIdx.x & 63;
+    if (qbound2 && lane == 0) qbound2[q] = 0xff800000u;  // (+inf: the deep scan's second gate class has not published)
     const float *qp = Q + q * (int64_t)d;
     const float *s = sb, *b = sb + 32 * nstep;
     float umax = 0.f, qq = 0.f, uu = 0.f;
@@ -246,27 +266,31 @@ ivf_sq_pair_terms(const float *__restrict__ Q, int64_t npairs, int nprobe, const
     if (lane == 0) pair_a[pair] = acc;
 }
 
-// A wave-uniform candidate into the sorted 16-entry list (lk, lr) of this wave (lanes 0..15 hold the entries).
+// A wave-uniform candidate into the sorted KF-entry list (lk, lr) of this wave (lanes 0..KF-1 hold the entries).
+template <int KF>
 __device__ __forceinline__ void sq_list_insert(float *lk, int *lr, float ck, int crow, int lane) {
-    const float ek = lane < SQ_KF ? lk[lane] : __builtin_inff();
-    const int er = lane < SQ_KF ? lr[lane] : SQ_PAD_ROW;
-    const int pos = __popcll(__ballot(lane < SQ_KF && lex_less(ek, er, ck, crow)));
-    if (pos >= SQ_KF) return;
+    const float ek = lane < KF ? lk[lane] : __builtin_inff();
+    const int er = lane < KF ? lr[lane] : SQ_PAD_ROW;
+    const int pos = __popcll(__ballot(lane < KF && lex_less(ek, er, ck, crow)));
+    if (pos >= KF) return;
     const float pk = shfl_up1_f(ek);
     const int pr = shfl_up1_i(er);
-    if (lane < SQ_KF) {
+    if (lane < KF) {
         if (lane == pos) { lk[lane] = ck; lr[lane] = crow; }
         else if (lane > pos) { lk[lane] = pk; lr[lane] = pr; }
     }
 }
 
-template <int QT, int P, bool IP>
+// KF: the depth of the wave lists.  KF > 16 (the deep variant): nclass gate classes, class = wave % nclass, class 1's
+// published words in qbound2 (null when nclass = 1).
+template <int QT, int P, bool IP, int KF>
 __device__ __forceinline__ void sq_item(int nstep, const uint4 *__restrict__ codes_t, int64_t tp0,
                                         const float *__restrict__ rown, int64_t r0, int64_t r1, int nqi, int gcap,
                                         const unsigned *__restrict__ qs, const float4 *__restrict__ qpar,
                                         float *lkeys, int *lrows, const int *__restrict__ bucket, int boff, int nprobe,
                                         const int *__restrict__ slot_off, int chunk, unsigned *__restrict__ qbound,
-                                        float *__restrict__ cand_d, int *__restrict__ cand_i) {
+                                        unsigned *__restrict__ qbound2, float *__restrict__ cand_d,
+                                        int *__restrict__ cand_i) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = lane & 15, g = lane >> 4;
@@ -274,8 +298,13 @@ __device__ __forceinline__ void sq_item(int nstep, const uint4 *__restrict__ cod
     const int npass_all = (int)ceil_div(r1 - r0, 32);
     const int npass = npass_all > wave ? (npass_all - wave + SQ_W - 1) / SQ_W : 0;
     const int ilast = npass > 0 ? npass - 1 : 0;
-    float *wk = lkeys + wave * gcap * SQ_KF;
-    int *wr = lrows + wave * gcap * SQ_KF;
+    float *wk = lkeys + wave * gcap * KF;
+    int *wr = lrows + wave * gcap * KF;
+    // the word this wave's full lists publish into: its class's
+    unsigned *qpub = qbound;
+    if constexpr (KF > SQ_KF) {
+        if (qbound2 && (wave & 1)) qpub = qbound2;
+    }
 
     // the row stream: unconditional loads (past the wave's last step they re-read it)
     const uint4 *rp = codes_t;
@@ -307,7 +336,7 @@ __device__ __forceinline__ void sq_item(int nstep, const uint4 *__restrict__ cod
         }
     }
     // this wave's lists start empty
-    for (int t = lane; t < nqi * SQ_KF; t += 64) {
+    for (int t = lane; t < nqi * KF; t += 64) {
         wk[t] = __builtin_inff();
         wr[t] = SQ_PAD_ROW;
     }
@@ -337,6 +366,14 @@ __device__ __forceinline__ void sq_item(int nstep, const uint4 *__restrict__ cod
                 gb[qt][v] = q < nqi ? __hip_atomic_load(qbound + bucket[boff + q] / nprobe, __ATOMIC_RELAXED,
                                                         __HIP_MEMORY_SCOPE_AGENT)
                                     : 0xff800000u;
+                if constexpr (KF > SQ_KF) {
+                    // two classes: the gate is the larger word (order-preserving bits), +inf until both have published
+                    if (qbound2 && q < nqi) {
+                        const unsigned g2 = __hip_atomic_load(qbound2 + bucket[boff + q] / nprobe, __ATOMIC_RELAXED,
+                                                              __HIP_MEMORY_SCOPE_AGENT);
+                        gb[qt][v] = gb[qt][v] > g2 ? gb[qt][v] : g2;
+                    }
+                }
             }
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt)
@@ -371,7 +408,7 @@ __device__ __forceinline__ void sq_item(int nstep, const uint4 *__restrict__ cod
         for (int qt = 0; qt < QT; ++qt)
 #pragma clang loop unroll(full)
             for (int v = 0; v < 4; ++v) {
-                // thr = min(own list's 16th key, published bound + 2E): margins sit with the constants in LDS
+                // thr = min(own list's KF-th key, published bound + 2E): margins sit with the constants in LDS
                 // (−2/t | −1/t, A | −P, 2E) of the query
                 const int q = qt * 16 + 4 * g + v;
                 const float4 kc = qpar[q < nqi ? q : 0];
@@ -391,7 +428,7 @@ __device__ __forceinline__ void sq_item(int nstep, const uint4 *__restrict__ cod
                             const int mm = __builtin_ctz(bits);
                             bits &= bits - 1;
                             const float ck = readlane_f(key, 16 * gg + mm);
-                            sq_list_insert(wk + ql * SQ_KF, wr + ql * SQ_KF, ck, (int)(prow0 + 16 * r + mm), lane);
+                            sq_list_insert<KF>(wk + ql * KF, wr + ql * KF, ck, (int)(prow0 + 16 * r + mm), lane);
                         }
                     }
                 }
@@ -404,11 +441,11 @@ __device__ __forceinline__ void sq_item(int nstep, const uint4 *__restrict__ cod
                 for (int v = 0; v < 4; ++v) {
                     const int q = qt * 16 + 4 * g + v;
                     if (q < nqi) {
-                        const float k16 = wk[q * SQ_KF + SQ_KF - 1];
+                        const float k16 = wk[q * KF + KF - 1];  // (the list's KF-th key)
                         const bool fresh = k16 < thr[qt][v];
                         thr[qt][v] = k16;
                         if (m == 0 && fresh) {
-                            atomicMin(qbound + bucket[boff + q] / nprobe, sq_order_bits(k16));
+                            atomicMin(qpub + bucket[boff + q] / nprobe, sq_order_bits(k16));
                         }
                     }
                 }
@@ -417,22 +454,22 @@ __device__ __forceinline__ void sq_item(int nstep, const uint4 *__restrict__ cod
         for (int r = 0; r < 2; ++r) xnr[r] = xnr_next[r];
     }
     // the wave's lists -> the (slot, wave) sub-lists
-    for (int t = lane; t < nqi * SQ_KF; t += 64) {
-        const int q = t / SQ_KF, e = t - q * SQ_KF;
-        const int64_t dst = (((int64_t)slot_off[bucket[boff + q]] + chunk) * SQ_W + wave) * SQ_KF + e;
+    for (int t = lane; t < nqi * KF; t += 64) {
+        const int q = t / KF, e = t - q * KF;
+        const int64_t dst = (((int64_t)slot_off[bucket[boff + q]] + chunk) * SQ_W + wave) * KF + e;
         cand_d[dst] = wk[t];
         cand_i[dst] = wr[t];
     }
 }
 
-template <int P, bool IP>
+template <int P, bool IP, int KF>
 __global__ void __launch_bounds__(64 * SQ_W, 2)
 ivf_sq_scan(const uint4 *__restrict__ qimg, const float4 *__restrict__ par, const float *__restrict__ pair_a, int nstep,
             const uint4 *__restrict__ codes_t, const int64_t *__restrict__ tpass_off, const float *__restrict__ rown,
             const int64_t *__restrict__ list_off, const int *__restrict__ list_len, const int *__restrict__ cnt,
             const int *__restrict__ bucket_off, const int *__restrict__ item_off, const int *__restrict__ bucket,
             const int *__restrict__ slot_off, int nlist, int nprobe, int group, unsigned *__restrict__ qbound,
-            float *__restrict__ cand_d, int *__restrict__ cand_i) {
+            unsigned *__restrict__ qbound2, float *__restrict__ cand_d, int *__restrict__ cand_i) {
     extern __shared__ __attribute__((aligned(16))) float smem_sq[];
     const int total = item_off[nlist];
     if ((int)blockIdx.x >= total) return;
@@ -457,7 +494,7 @@ ivf_sq_scan(const uint4 *__restrict__ qimg, const float4 *__restrict__ par, cons
     const int stride = sq_stride(nstep);
     float4 *qpar = reinterpret_cast<float4 *>(qs + gcap * stride);
     float *lkeys = reinterpret_cast<float *>(qpar + gcap);
-    int *lrows = reinterpret_cast<int *>(lkeys + SQ_W * gcap * SQ_KF);
+    int *lrows = reinterpret_cast<int *>(lkeys + SQ_W * gcap * KF);
     const int per_q = nstep * 4;
     for (int t = threadIdx.x; t < nqi * per_q; t += 64 * SQ_W) {
         const int q = t / per_q, r2 = t - q * per_q;
@@ -471,8 +508,8 @@ ivf_sq_scan(const uint4 *__restrict__ qimg, const float4 *__restrict__ par, cons
         qpar[t] = make_float4(IP ? -p.x : -2.f * p.x, IP ? -a : a, p.z, 0.f);
     }
 #define SQ_CASE(QTV)                                                                                                 \
-    sq_item<QTV, P, IP>(nstep, codes_t, tp0, rown, r0, r1, nqi, gcap, qs, qpar, lkeys, lrows, bucket, boff, nprobe, \
-                        slot_off, chunk, qbound, cand_d, cand_i);
+    sq_item<QTV, P, IP, KF>(nstep, codes_t, tp0, rown, r0, r1, nqi, gcap, qs, qpar, lkeys, lrows, bucket, boff,    \
+                            nprobe, slot_off, chunk, qbound, qbound2, cand_d, cand_i);
     switch (nqt) {
     case 0: case 1: SQ_CASE(1) break;
     case 2: SQ_CASE(2) break;
@@ -482,8 +519,9 @@ ivf_sq_scan(const uint4 *__restrict__ qimg, const float4 *__restrict__ par, cons
 #undef SQ_CASE
 }
 
-// One wave per query (k <= 16): τ, the certificate, the recheck of every candidate within 2E of τ.
-template <bool IP>
+// One wave per query (k <= 16 at KF = 16, k <= 64 at KF = 32): τ, the certificate, the recheck of every candidate
+// within 2E of τ.  A slot holds SQ_W sub-lists of KF entries; a sub-list is full when its entry KF − 1 is not a pad.
+template <bool IP, int KF>
 __global__ void __launch_bounds__(256)
 ivf_sq_rerank(const float *__restrict__ Q, int64_t nq, int d, int nstep, int k, const float4 *__restrict__ par,
               const float *__restrict__ cand_d, const int *__restrict__ cand_i, const int *__restrict__ slot_off,
@@ -495,7 +533,7 @@ ivf_sq_rerank(const float *__restrict__ Q, int64_t nq, int d, int nstep, int k, 
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= nq) return;
     const int lane = threadIdx.x & 63;
-    constexpr int SL = SQ_W * SQ_KF;  // entries per slot
+    constexpr int SL = SQ_W * KF;  // entries per slot
     const int64_t e0 = (int64_t)slot_off[q * nprobe] * SL, e1 = (int64_t)slot_off[(q + 1) * nprobe] * SL;
     WaveList<1, int> L;
     L.init();
@@ -504,7 +542,7 @@ ivf_sq_rerank(const float *__restrict__ Q, int64_t nq, int d, int nstep, int k, 
     for (int64_t c0 = e0; c0 < e1; c0 += 64) {  // (SL is a multiple of 64)
         const float key = cand_d[c0 + lane];
         const int row = cand_i[c0 + lane];
-        if ((lane & (SQ_KF - 1)) == SQ_KF - 1 && row != SQ_PAD_ROW) {
+        if ((lane & (KF - 1)) == KF - 1 && row != SQ_PAD_ROW) {
             anyfull = true;
             minfull = fminf(minfull, key);
         }
@@ -681,12 +719,12 @@ void launch_ivf_sq_row_terms(const unsigned char *codes, const IvfSqView &v, con
 }
 
 void launch_ivf_sq_query_prep(const float *Q, int64_t nq, const IvfSqView &v, float cmax, float wbase, void *qimg,
-                              float *par, hipStream_t st) {
+                              float *par, unsigned *qbound2, hipStream_t st) {
     if (nq <= 0) return;
     const dim3 grid((unsigned)ceil_div(nq, 4)), block(256);
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, grid, block, 0, st, Q, nq, v.d, v.nstep, v.sb, cmax, wbase,
-                           static_cast<_Float16 *>(qimg), reinterpret_cast<float4 *>(par));
+                           static_cast<_Float16 *>(qimg), reinterpret_cast<float4 *>(par), qbound2);
     };
     if (v.metric == kIP) go(ivf_sq_query_prep<true>);
     else go(ivf_sq_query_prep<false>);
@@ -707,16 +745,18 @@ void launch_ivf_sq_pair_terms(const float *Q, int64_t nq, int nprobe, const int6
     HIPANN_CHECK(hipGetLastError());
 }
 
-void launch_ivf_sq_scan(const IvfSqView &v, const IvfPlanView &plan, int group, int64_t max_items, const void *qimg,
-                        const float *par, const float *pair_a, unsigned *qbound, float *cand_d, int *cand_i,
-                        hipStream_t st) {
+void launch_ivf_sq_scan(const IvfSqView &v, const IvfPlanView &plan, int group, int kf, int nclass, int64_t max_items,
+                        const void *qimg, const float *par, const float *pair_a, unsigned *qbound, unsigned *qbound2,
+                        float *cand_d, int *cand_i, hipStream_t st) {
     if (max_items <= 0) return;
+    HIPANN_REQUIRE(kf == SQ_KF || kf == SQ_KD, "IVF SQ8 scan: filter depth");
+    HIPANN_REQUIRE(nclass == 1 || (nclass == 2 && kf == SQ_KD && qbound2), "IVF SQ8 scan: gate classes");
     HIPANN_REQUIRE(ivf_chunk_rows() == SQ_CH, "IVF SQ8 scan: chunks of 2048 rows");
     HIPANN_REQUIRE(max_items < (int64_t)0x7fffffff, "too many IVF work items");
     const int wide = ivf_group_wide(group);
     HIPANN_REQUIRE(wide >= 16 && wide <= 16 * SQ_QT && wide % 16 == 0 && ivf_group_narrow(group) == 0,
                    "IVF SQ8 scan: unsupported group");
-    const size_t smem = sq_lds_bytes(v.nstep, wide);
+    const size_t smem = sq_lds_bytes(v.nstep, wide, kf);
     HIPANN_REQUIRE(smem <= SQ_LDS_MAX, "IVF SQ8 scan: LDS image too large");
     HIPANN_REQUIRE(v.metric == kIP || v.rown, "IVF SQ8 scan: L2 needs the row terms");
     const dim3 grid((unsigned)max_items), block(64 * SQ_W);
@@ -729,20 +769,27 @@ void launch_ivf_sq_scan(const IvfSqView &v, const IvfPlanView &plan, int group, 
         hipLaunchKernelGGL(kern, grid, block, smem, st, static_cast<const uint4 *>(qimg),
                            reinterpret_cast<const float4 *>(par), pair_a, v.nstep,
                            reinterpret_cast<const uint4 *>(v.codes_t), v.tpass_off, v.rown, HIPANN_PLAN_ARGS(plan), group,
-                           qbound, cand_d, cand_i);
+                           qbound, nclass == 2 ? qbound2 : nullptr, cand_d, cand_i);
     };
     const bool p8 = v.nstep % 8 == 0;
-    static bool ready[4] = {false, false, false, false};
-    if (v.metric == kIP) { if (p8) go(ivf_sq_scan<8, true>, ready[0]); else go(ivf_sq_scan<4, true>, ready[1]); }
-    else { if (p8) go(ivf_sq_scan<8, false>, ready[2]); else go(ivf_sq_scan<4, false>, ready[3]); }
+    static bool ready[8] = {false, false, false, false, false, false, false, false};
+    if (kf == SQ_KF) {
+        if (v.metric == kIP) { if (p8) go(ivf_sq_scan<8, true, SQ_KF>, ready[0]); else go(ivf_sq_scan<4, true, SQ_KF>, ready[1]); }
+        else { if (p8) go(ivf_sq_scan<8, false, SQ_KF>, ready[2]); else go(ivf_sq_scan<4, false, SQ_KF>, ready[3]); }
+    } else {
+        if (v.metric == kIP) { if (p8) go(ivf_sq_scan<8, true, SQ_KD>, ready[4]); else go(ivf_sq_scan<4, true, SQ_KD>, ready[5]); }
+        else { if (p8) go(ivf_sq_scan<8, false, SQ_KD>, ready[6]); else go(ivf_sq_scan<4, false, SQ_KD>, ready[7]); }
+    }
     HIPANN_CHECK(hipGetLastError());
 }
 
 void launch_ivf_sq_rerank(const IvfSqView &v, const IvfPlanView &plan, const int64_t *probes, const float *Q, int64_t nq,
-                          int k, const float *par, const float *cand_d, const int *cand_i, int *nflag, int *flagged,
+                          int k, int kf, int nclass, const float *par, const float *cand_d, const int *cand_i, int *nflag, int *flagged,
                           unsigned long long *fb_total, float *D, int64_t *I, hipStream_t st) {
     if (nq <= 0) return;
-    HIPANN_REQUIRE(k >= 1 && k <= SQ_KF, "IVF SQ8 rerank: k above the filter depth");
+    HIPANN_REQUIRE(kf == SQ_KF || kf == SQ_KD, "IVF SQ8 rerank: filter depth");
+    // (the scan's gate bounds the k-th key only while nclass·kf rows stand behind it; the result list holds 64)
+    HIPANN_REQUIRE(k >= 1 && k <= nclass * kf && k <= kSqDirectK, "IVF SQ8 rerank: k above the filter depth");
     const dim3 grid((unsigned)ceil_div(nq, 4)), block(256);
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, grid, block, 0, st, Q, nq, v.d, v.nstep, k, reinterpret_cast<const float4 *>(par), cand_d,
@@ -750,8 +797,8 @@ void launch_ivf_sq_rerank(const IvfSqView &v, const IvfPlanView &plan, const int
                            v.by_residual ? v.centroids : nullptr, v.vmin, v.vdiff, v.codes_t, v.tpass_off, v.ids, nflag,
                            flagged, fb_total, D, I);
     };
-    if (v.metric == kIP) go(ivf_sq_rerank<true>);
-    else go(ivf_sq_rerank<false>);
+    if (kf == SQ_KF) { if (v.metric == kIP) go(ivf_sq_rerank<true, SQ_KF>); else go(ivf_sq_rerank<false, SQ_KF>); }
+    else { if (v.metric == kIP) go(ivf_sq_rerank<true, SQ_KD>); else go(ivf_sq_rerank<false, SQ_KD>); }
     HIPANN_CHECK(hipGetLastError());
 }
 

@@ -529,6 +529,7 @@ struct IvfSqIndex : IndexBase {
     // per-call scratch: query images and (1/t, E, 2E), pair constants, per-(slot, wave) candidate lists, flags,
     // the direct kernel's slot lists, staged queries and results, the probe lists of a sliced call
     DevBuf qimg, par, pair_a, cand_d, cand_i, flagged, dl_d, dl_i, q, out_d, out_i, probes, fb_total;
+    DevBuf qbound2;              // per query: the deep scan's second gate class (the first is the shard's qbound)
     HostBuf h_q, h_d, h_i;
     bool probes_kept = false;    // the last call ran in query slices: its probe lists are in `probes`
     int64_t range_mask_budget = 0;  // test hook: a range call's mask bytes per query slice (0: 64 MiB)
@@ -822,10 +823,12 @@ struct IvfSqView {
     int64_t nrows = 0;
 };
 constexpr int kSqWaves = 8;    // waves per scan block = candidate sub-lists per (query, probe, chunk) slot
-constexpr int kSqKeep = 16;    // entries per sub-list: the scan path serves k <= kSqKeep
+constexpr int kSqKeep = 16;    // entries per sub-list: the scan path serves k <= kSqKeep at this depth
+constexpr int kSqDeep = 32;    // entries per sub-list of the deep variant: kSqKeep < k <= kSqDirectK, two gate classes above 32
 constexpr int kSqDirectK = 64; // the direct kernel's per-slot list for k <= 64; above: every row of the slot
 int ivf_sq_nstep(int d);
-int ivf_sq_group(int d);  // queries per scan item (a multiple of 16; 0: the query terms do not fit the LDS)
+// queries per scan item at sub-lists of kf entries (a multiple of 16; 0: the query terms do not fit the LDS)
+int ivf_sq_group(int d, int kf);
 void launch_ivf_sq_tile(const unsigned char *codes, const int64_t *list_off, const int *list_len,
                         const int64_t *tpass_off, int nlist, int64_t total_pass, int d, int nstep, unsigned char *dst,
                         hipStream_t st);
@@ -834,15 +837,17 @@ void launch_ivf_sq_untile(const IvfSqView &v, const int64_t *list_off, const int
                           int64_t total_pass, unsigned char *codes, int64_t *ids_out, hipStream_t st);
 void launch_ivf_sq_row_terms(const unsigned char *codes, const IvfSqView &v, const int64_t *list_off, int nlist,
                              float *rown, unsigned *cmax2, hipStream_t st);
+// qbound2 (optional, nq words): reset to +inf, the deep scan's second gate class
 void launch_ivf_sq_query_prep(const float *Q, int64_t nq, const IvfSqView &v, float cmax, float wbase, void *qimg,
-                              float *par, hipStream_t st);
+                              float *par, unsigned *qbound2, hipStream_t st);
 void launch_ivf_sq_pair_terms(const float *Q, int64_t nq, int nprobe, const int64_t *probes, const IvfSqView &v,
                               float *pair_a, hipStream_t st);
-void launch_ivf_sq_scan(const IvfSqView &v, const IvfPlanView &plan, int group, int64_t max_items, const void *qimg,
-                        const float *par, const float *pair_a, unsigned *qbound, float *cand_d, int *cand_i,
-                        hipStream_t st);
+// kf: the sub-lists' depth (kSqKeep | kSqDeep); nclass: gate classes, ceil(k / kf) (2: qbound2 holds class 1's words)
+void launch_ivf_sq_scan(const IvfSqView &v, const IvfPlanView &plan, int group, int kf, int nclass, int64_t max_items,
+                        const void *qimg, const float *par, const float *pair_a, unsigned *qbound, unsigned *qbound2,
+                        float *cand_d, int *cand_i, hipStream_t st);
 void launch_ivf_sq_rerank(const IvfSqView &v, const IvfPlanView &plan, const int64_t *probes, const float *Q, int64_t nq,
-                          int k, const float *par, const float *cand_d, const int *cand_i, int *nflag, int *flagged,
+                          int k, int kf, int nclass, const float *par, const float *cand_d, const int *cand_i, int *nflag, int *flagged,
                           unsigned long long *fb_total, float *D, int64_t *I, hipStream_t st);
 // the direct kernel over the slots of the flagged queries (nflag / flagged set) or of all nq; kslot = kSqDirectK
 // (per-slot lists of the 64 best (distance, label); dl_i: int64) or ivf_chunk_rows() (every row; dl_i: int shard rows)

@@ -431,9 +431,10 @@ int64_t hipann_ivf_rerank_fallbacks(void *index);
  * order, ties by list id); nprobe <= 0: the index's value; above nlist: nlist.
  * Results: per query the k best rows of the probed lists by (distance, id), ascending for L2, descending for IP; slots
  * past the number of probed rows hold (+inf | −inf, −1).  k <= 0 is an error; k <= HIPANN_MAX_K.  The same call
- * returns the same bits on every run.  k <= 16 runs the code scan on the matrix cores with an exact rerank and a
- * per-query certificate; queries the certificate flags, larger k and d above 4352 run the direct kernel on the
- * device (no host readback: the _device call stays asynchronous).
+ * returns the same bits on every run.  k <= 64 runs the code scan on the matrix cores with an exact rerank and a
+ * per-query certificate (wave lists 16 deep for k <= 16, 32 deep for 17 <= k <= 64); queries the certificate flags,
+ * larger k and d above 4352 (above 3840 for 17 <= k <= 64) run the direct kernel on the device (no host readback:
+ * the _device call stays asynchronous).
  * The handle is single-device (per-handle mutex, one stream plus scratch, err_buf as everywhere) and serves
  * hipann_ntotal / _dim / _metric / _memory_bytes / _free / _set_kernel_timing / _last_kernel_ms (which = 0: the code
  * scan; after hipann_ivfsq_remove_ids: its kernel; after a range search: its threshold scan); every other entry point
